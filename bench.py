@@ -2,7 +2,12 @@
 """bench.py — throughput of the MI355X hot path (stereo KLT front-end + MSCKF update) on synthetic
 EuRoC-shaped streams.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline; --dump-outputs DIR also writes what the timed
+path computed in its last step as DIR/<name>.npy.  --full adds what the headline does not need: per-kernel HIP-event
+timing and the roofline, a second timed window with the Gram + Cholesky compression, the CPU-oracle baseline and the
+comparison of the GPU results and trajectories with it.
 
 One process per GPU.  With --gpus N > 1 and no WORLD_SIZE in the environment this process only SPAWNS the N ranks
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1 rendezvous) before importing torch or touching HIP, relays
@@ -52,6 +57,8 @@ PROFILE_NAMES = {"k_pyr_down": "k_pyr_down3", "k_ekf_small": "k_ekf_small_update
 
 COMPRESSION_MODES = {"auto": 0, "gram": 1, "tsqr": 2, "householder": 3}      # mskf_ekf_cfg.compression_mode (include/mskf_types.h)
 
+T0_NS, FRAME_DT_NS = 1403715273262142976, 50000000        # stamp of frame 0 and frame period of every sequence (EuRoC's 20 Hz)
+
 # BASELINE.json configs: image, clone window, grid rows x cols x min x max, streams per GPU, groups
 CONFIGS = {
     "c2": dict(width=752, height=480, clones=30, grid="8x10x5x6", streams=1536, groups=8, loop=60, cpu_frames=150, cpu_all_frames=80,
@@ -85,9 +92,13 @@ def parse(argv=None):
     ap.add_argument("--grid", type=str, default=None, help="rows x cols x min x max features per cell")
     ap.add_argument("--prime", type=int, default=None, help="untimed frames before warmup: gravity init + clone window fill")
     ap.add_argument("--loop", type=int, default=None, help="frames per trajectory period")
-    ap.add_argument("--cpu-frames", type=int, default=None, help="frames of the 1-core CPU-oracle baseline sample (0 = skip)")
-    ap.add_argument("--cpu-all-frames", type=int, default=None, help="frames per stream of the all-cores CPU-oracle leg (0 = skip)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: per-kernel timing and roofline, "
+                    "the second (Gram + Cholesky) window, the CPU-oracle baseline and the comparison with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last "
+                    "step as DIR/<name>.npy (local stream 0 of every group: features, IMU state; stream 0's trajectory)")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="frames of the 1-core CPU-oracle baseline sample (--full; 0 = skip)")
+    ap.add_argument("--cpu-all-frames", type=int, default=None, help="frames per stream of the all-cores CPU-oracle leg (--full; 0 = skip)")
+    ap.add_argument("--no-cpu", action="store_true", help="no CPU-oracle baseline in a --full run")
     ap.add_argument("--backend", default=os.environ.get("MSKF_BENCH_BACKEND", "nccl"), help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--compression", choices=["householder", "auto", "gram", "tsqr"], default="householder",
                     help="QR compression of the stacked Jacobian (msckf_vio.cpp:795-821): householder = the reference's own rule, Householder QR when "
@@ -95,18 +106,22 @@ def parse(argv=None):
                          "Householder TSQR where the device decides it is needed; gram = Gram only; tsqr = Householder always")
     ap.add_argument("--gram-steps", type=int, default=-1,
                     help="steps of the SECOND timed window, run with the Gram + regularised Cholesky compression (--compression auto) instead of the "
-                         "reference's Householder QR (value_gram_cholesky in the JSON line); -1 = min(steps, 12) when the first window ran with "
-                         "--compression householder, 0 = off")
+                         "reference's Householder QR (value_gram_cholesky in the JSON line; --full only); -1 = min(steps, 12) when the first "
+                         "window ran with --compression householder, 0 = off")
     ap.add_argument("--host-images", action="store_true", help="stereo pairs stay in host memory: PCIe-inclusive rate (not the headline value)")
     ap.add_argument("--host-render", action="store_true", help="render the synthetic sequences on the host (round 3's way) instead of on the device")
     ap.add_argument("--rehearse", action="store_true", help="CPU rehearsal of the multi-rank plumbing (launcher, rendezvous, reductions, "
                     "JSON line) without any device work: for the gloo tests only, the line it prints says so")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     preset = CONFIGS[args.config]
     for k in ("width", "height", "clones", "grid", "streams", "groups", "loop", "cpu_frames", "cpu_all_frames"):
         if getattr(args, k) is None:
             setattr(args, k, preset[k] if k not in ("streams", "groups") else int(os.environ.get("MSKF_BENCH_" + k.upper(), preset[k])))
-    if args.gram_steps < 0:
+    if not args.full:
+        args.gram_steps = 0
+    elif args.gram_steps < 0:
         args.gram_steps = min(args.steps, 12) if (args.compression == "householder" and not args.no_pipeline) else 0
     if args.prime is None:
         # static start, gravity / bias initialisation, clone window full — and one whole period of the looping trajectory, so that
@@ -192,6 +207,43 @@ def imu_array(syn, n):
         s = syn.imu(j)
         out[j] = (s.time_stamp, tuple(s.angular_velocity), tuple(s.linear_acceleration))
     return out
+
+
+def collect_outputs(run, args, n_groups, per_group, pipe):
+    """What the timed path computed in its last step (--dump-outputs): local stream 0 of every group after the group's frame
+    prime + W + K - 1 (its stagger offset added) - live feature ids, lifetimes, cam0 / cam1 pixels, IMU state - and the
+    trajectory of stream 0 up to that frame.  The pipelined run snapshots these when a group finishes that frame; its groups
+    go on stepping until the window has closed, so the state they end in is not what is dumped."""
+    import numpy as np
+    ids, life, c0, c1, imu = [], [], [], [], []
+    for g in range(n_groups):
+        if pipe:
+            i_, l_, a_, b_, s_ = run.mark_dump(g)
+        else:
+            i_, l_, a_, b_, _ = run.dump(g * per_group)
+            s_ = run.imu_state(g * per_group)
+        ids.append(i_)
+        life.append(l_)
+        c0.append(np.stack([a_["x"], a_["y"]], 1))
+        c1.append(np.stack([b_["x"], b_["y"]], 1))
+        imu.append(s_)
+    last = args.prime + args.warmup + args.steps - 1          # group 0 has no stagger offset
+    poses = run.poses(0)
+    poses = poses[poses["t"] <= (T0_NS + (last + 0.5) * FRAME_DT_NS) * 1e-9]
+    return {"feature_ids": np.concatenate(ids).astype(np.float64),           # ids count up from 0 per stream: exact in float64
+            "feature_lifetimes": np.concatenate(life).astype(np.float64),
+            "feature_cam0_px": np.concatenate(c0).astype(np.float32),
+            "feature_cam1_px": np.concatenate(c1).astype(np.float32),
+            "features_per_group": np.array([len(x) for x in ids], np.float64),
+            "imu_state": np.stack(imu).astype(np.float64),
+            "pose_stream0": np.column_stack([poses["t"], poses["p"], poses["q"]]).astype(np.float64)}
+
+
+def write_outputs(outputs, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def state_hash(ids, life, c0, c1, imu_state):
@@ -339,6 +391,92 @@ def host_cores_available():
     return min(quota, aff) if quota else aff
 
 
+def kernel_figures(timing, args, per_group):
+    """--full: roofline of the dominant kernel, FP64 matrix-core rate of k_ekf_gemm and per-kernel times, from the HIP events
+    of the timed window and the committed counter passes."""
+    # ---- roofline of the dominant kernel (largest HIP-event time inside the timed region)
+    dom = max(timing, key=lambda k: timing[k][0])
+    # "k_ekf_feature_blocks" is the event span over up to five launches of an update (triangulation, pair blocks and the three
+    # block classes): no single kernel of it runs longer than a third of the span.  It is the dominant KERNEL only when the
+    # span is more than three times the longest single-kernel entry; otherwise that entry is.
+    if dom == "k_ekf_feature_blocks":
+        single = max((k for k in timing if k != dom), key=lambda k: timing[k][0])
+        if timing[dom][0] < 3.0 * timing[single][0]:
+            dom = single
+    ms, launches, units = timing[dom]
+    avg_s = max(ms * 1e-3 / max(launches, 1), 1e-12)
+    if dom in ("k_ekf_feature_blocks", "k_ekf_gemm", "k_ekf_chol_lds", "k_ekf_trsm", "k_ekf_tsqr"):
+        achieved = units / max(launches, 1) / avg_s / 1e12           # units = algorithmic FP64 flops (SURVEY §8d)
+        roof = {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": achieved / FP64_PEAK_TFLOPS, "traffic": None}
+        if dom == "k_ekf_tsqr":
+            roof["note"] = "a chain of Householder reflectors on the FP64 vector units, priced against the FP64 peak (vector = matrix = 78.6 TFLOP/s on MI355X)"
+    else:
+        # k_pyr_down (one launch for levels 1..3): level 0 read once + the three levels written = (64 / 21 + 1) bytes per output pixel
+        per_unit = {"k_track4": LK_BYTES_PER_TRACK, "k_pyr_down": 64.0 / 21.0 + 1.0, "k_detect_cells": 1}.get(dom, 0)
+        achieved = units / max(launches, 1) * per_unit / avg_s / 1e9
+        roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": None}
+    # HBM traffic per launch of that kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE run
+    # separately); only comparable when a launch covers the same number of streams
+    try:
+        pmc_all = json.load(open(PMC_TRAFFIC_FILE))
+        pmc = pmc_all["kernels"].get(PROFILE_NAMES.get(dom, dom))
+        spl = pmc_all.get("streams_per_launch", 96)
+        if pmc and args.config == pmc_all.get("config", "c2"):
+            # every stream of a launch reads its own images: traffic per launch is proportional to the streams in it
+            roof["traffic"] = (pmc["fetch_kb_per_launch"] + pmc["write_kb_per_launch"]) * 1024.0 * per_group / spl
+            roof["traffic_note"] = ("bytes/launch, raw FETCH_SIZE+WRITE_SIZE of %s (collected at %d streams per launch, scaled to %d; "
+                                    "no gfx950 correction applied: dword loads, not the calibrated 16 B/lane stream)"
+                                    % (os.path.relpath(PMC_TRAFFIC_FILE, ROOT), spl, per_group))
+    except Exception:
+        pass
+    roof["avg_launch_us"] = avg_s * 1e6
+    roof["units_per_launch"] = units / max(launches, 1)
+    # HBM is not what bounds the track kernel (traffic is half its algorithmic bytes, it runs at a few per cent of the HBM
+    # peak): its governing roof is VALU issue.  Instructions per wave and waves per launch from the committed SQ counter pass
+    # (rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES, collected at `streams_per_launch` streams, scaled to this run's launches).
+    try:
+        sq_all = json.load(open(PMC_SQ_FILE))
+        sq = sq_all["kernels"].get(PROFILE_NAMES.get(dom, dom))
+        spl = sq_all.get("streams_per_launch", 96)
+        if sq and args.config == sq_all.get("config", "c2"):
+            wave_insts = sq["valu_insts_per_wave"] * sq["waves_per_dispatch"] * per_group / spl
+            roof["valu_issue"] = {"bound": "valu", "insts_per_wave": sq["valu_insts_per_wave"], "waves_per_launch": sq["waves_per_dispatch"] * per_group / spl,
+                                  "achieved": wave_insts / avg_s, "peak": VALU_ISSUE_PEAK, "unit": "wave-instructions/s",
+                                  "frac": wave_insts / avg_s / VALU_ISSUE_PEAK, "source": os.path.relpath(PMC_SQ_FILE, ROOT)}
+            if dom == "k_track4" and roof["units_per_launch"] > 0:
+                # wave-instructions per point track (a wavefront carries four points: round 2's 7026 per wave = 1757 per point)
+                roof["valu_issue"]["insts_per_point_track"] = wave_insts / roof["units_per_launch"]
+    except Exception:
+        pass
+    kernels = {k: {"ms": round(v[0], 3), "launches": v[1], "avg_us": round(v[0] * 1e3 / max(v[1], 1), 2)} for k, v in timing.items() if v[1]}
+    # FP64 matrix-core rate of the dense update kernels alone (SURVEY §8d: the meaningful MFMA number is per kernel)
+    gm = timing.get("k_ekf_gemm", (0, 0, 0))
+    mfma = {"kernel": "k_ekf_gemm", "tflops": (gm[2] / (gm[0] * 1e-3) / 1e12) if gm[0] > 0 else None, "peak": FP64_PEAK_TFLOPS}
+    if mfma["tflops"] is not None:
+        mfma["frac"] = mfma["tflops"] / FP64_PEAK_TFLOPS
+        mfma["note"] = "tflops / frac are over SURVEY 8(d)'s ALGORITHMIC flops (dense-d formulas); executed_* are what the matrix cores did"
+    # executed flops: SQ_INSTS_VALU_MFMA_MOPS_F64 of the committed counter pass, per launch and mode, weighted by the modes'
+    # dispatch counts, scaled from that pass's streams per launch to this run's; over the launch time measured in THIS run
+    try:
+        mm = json.load(open(PMC_MFMA_FILE))
+        spl = mm.get("streams_per_launch", 96)
+        modes = {k: v for k, v in mm["kernels"].items() if k.startswith("k_ekf_gemm")}
+        nd = sum(v["dispatches"] for v in modes.values())
+        if nd and gm[1] > 0 and args.config == mm.get("config", "c2"):
+            gflop = sum(v["fp64_mfma_gflop_per_dispatch"] * v["dispatches"] for v in modes.values()) / nd * per_group / spl
+            t_launch = gm[0] * 1e-3 / gm[1]
+            mfma["executed_gflop_per_launch"] = gflop
+            mfma["executed_tflops"] = gflop * 1e9 / t_launch / 1e12
+            mfma["executed_frac"] = mfma["executed_tflops"] / FP64_PEAK_TFLOPS
+            mfma["executed_alone"] = {k: {"tflops": v["tflops"], "mfma_busy_pct_simd": v["mfma_busy_pct_simd"]} for k, v in modes.items()}
+            mfma["source"] = os.path.relpath(PMC_MFMA_FILE, ROOT)
+    except Exception:
+        pass
+    return {"roofline": roof, "mfma": mfma, "kernels": kernels}
+
+
 # ------------------------------------------------------------------------------------------ one rank
 def gather_hashes(h, world, device):
     import torch
@@ -406,6 +544,21 @@ def emit(line):
     out.flush()
 
 
+def build_libraries():
+    """Rebuild whatever native library is older than its sources, as a working tree expects.  A checkout that build() prepared
+    may belong to another user, who cannot take the build locks: its libraries are used as build() left them (a missing one
+    fails when it is loaded).  Returns the oracle module, whose loaders would otherwise try to build again."""
+    from msckf_stereo_c_amd import build
+    from oracle import oracle_py
+    try:
+        build.build_all()
+        oracle_py.build()
+    except PermissionError as e:
+        sys.stderr.write("bench.py: the build folders are not writable here (%s): using the libraries as built\n" % e)
+        oracle_py._built = True
+    return oracle_py
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse(argv)
@@ -446,10 +599,8 @@ def main(argv=None):
         else:
             dist.init_process_group(backend=args.backend)
 
-    from msckf_stereo_c_amd import build, runner as R
-    build.build_all()
-    from oracle import oracle_py            # synthetic generator + (rank 0) the cpu_baseline leg only
-    oracle_py.build()
+    from msckf_stereo_c_amd import runner as R
+    oracle_py = build_libraries()           # synthetic generator + (rank 0) the cpu_baseline leg only
 
     fe, ekf = make_cfgs(args)
     per_group = max(1, args.streams // args.groups)
@@ -495,7 +646,7 @@ def main(argv=None):
     # pose_out.txt / path_ / points3d_ growth (msckf_vio.cpp:1296-1302, Q20) is off for the batch; the streams whose
     # trajectories are compared with the CPU oracle after the run keep theirs
     run.keep_trajectory(False)
-    n_pose_streams = min(per_group, max(1, int(host_cores_available()))) if (rank == 0 and not args.no_cpu) else 1
+    n_pose_streams = min(per_group, max(1, int(host_cores_available()))) if (rank == 0 and args.full and not args.no_cpu) else 1
     for s_ in range(n_pose_streams):
         run.keep_trajectory(True, s_)
     cooldown = (args.steps + 8) if n_groups > 1 else 0      # frames a group may step beyond its own W + K while the window is open
@@ -508,7 +659,7 @@ def main(argv=None):
         u = s % args.unique
         cam0 = base + (u * 2 + 0) * n_keys * frame_bytes
         cam1 = base + (u * 2 + 1) * n_keys * frame_bytes
-        run.set_sequence(s, cam0, cam1, on_device, frame_bytes, 25, args.loop, 1403715273262142976, 50000000, imus[u])
+        run.set_sequence(s, cam0, cam1, on_device, frame_bytes, 25, args.loop, T0_NS, FRAME_DT_NS, imus[u])
 
     red_dev = "cuda" if args.backend == "nccl" else "cpu"
 
@@ -521,8 +672,9 @@ def main(argv=None):
     run.run(0, args.prime, pipelined=pipe)                       # untimed: gravity/bias init, clone window fills, group offsets
     progress(rank, "primed: %d frames per stream" % args.prime)
     # per-kernel HIP events on every 5th launch of a kind (5 is coprime to the launches per step of every kind, so all of a
-    # step's launches are sampled in turn); MSKF_BENCH_TIMING_PERIOD=1 times every launch, MSKF_BENCH_NO_KERNEL_TIMING=1 none
-    timing_period = 0 if os.environ.get("MSKF_BENCH_NO_KERNEL_TIMING") else int(os.environ.get("MSKF_BENCH_TIMING_PERIOD", "5"))
+    # step's launches are sampled in turn); MSKF_BENCH_TIMING_PERIOD=1 times every launch, MSKF_BENCH_NO_KERNEL_TIMING=1 none.
+    # --full only: the headline does not need them
+    timing_period = 0 if (not args.full or os.environ.get("MSKF_BENCH_NO_KERNEL_TIMING")) else int(os.environ.get("MSKF_BENCH_TIMING_PERIOD", "5"))
     cpu_quota, thr0 = cgroup_cpu()
     if pipe:
         # W warm-up + K timed steps in ONE pipelined run: the group pipelines (front-end | filter threads) are not torn
@@ -575,6 +727,8 @@ def main(argv=None):
         s_imu = run.imu_state(0)
     hashes = gather_hashes(state_hash(s_ids, s_life, s_c0, s_c1, s_imu), world, red_dev)
     id_mismatch = sum(1 for h in hashes if h != hashes[0])
+    if args.dump_outputs and rank == 0:                      # before the second window moves the streams on
+        write_outputs(collect_outputs(run, args, n_groups, per_group, pipe), args.dump_outputs)
     frames_by_group = [run.frames_done(g) - run.group_offset(g) - args.prime for g in range(n_groups)] if pipe else []
 
     # sanity of the workload actually processed (steady state reached, filter alive)
@@ -613,86 +767,7 @@ def main(argv=None):
 
     if rank == 0:
         value = frames_total / elapsed
-        # ---- roofline of the dominant kernel (largest HIP-event time inside the timed region)
-        dom = max(timing, key=lambda k: timing[k][0])
-        # "k_ekf_feature_blocks" is the event span over up to five launches of an update (triangulation, pair blocks and the three
-        # block classes): no single kernel of it runs longer than a third of the span.  It is the dominant KERNEL only when the
-        # span is more than three times the longest single-kernel entry; otherwise that entry is.
-        if dom == "k_ekf_feature_blocks":
-            single = max((k for k in timing if k != dom), key=lambda k: timing[k][0])
-            if timing[dom][0] < 3.0 * timing[single][0]:
-                dom = single
-        ms, launches, units = timing[dom]
-        avg_s = max(ms * 1e-3 / max(launches, 1), 1e-12)
-        if dom in ("k_ekf_feature_blocks", "k_ekf_gemm", "k_ekf_chol_lds", "k_ekf_trsm", "k_ekf_tsqr"):
-            achieved = units / max(launches, 1) / avg_s / 1e12           # units = algorithmic FP64 flops
-            roof = {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": achieved / FP64_PEAK_TFLOPS, "traffic": None}
-            if dom == "k_ekf_tsqr":
-                roof["note"] = "a chain of Householder reflectors on the FP64 vector units, priced against the FP64 peak (vector = matrix = 78.6 TFLOP/s on MI355X)"
-        else:
-            # k_pyr_down (one launch for levels 1..3): level 0 read once + the three levels written = (64 / 21 + 1) bytes per output pixel
-            per_unit = {"k_track4": LK_BYTES_PER_TRACK, "k_pyr_down": 64.0 / 21.0 + 1.0, "k_detect_cells": 1}.get(dom, 0)
-            achieved = units / max(launches, 1) * per_unit / avg_s / 1e9
-            roof = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": achieved / HBM_PEAK_GBS, "traffic": None}
-        # HBM traffic per launch of that kernel from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE run
-        # separately); only comparable when a launch covers the same number of streams
-        try:
-            pmc_all = json.load(open(PMC_TRAFFIC_FILE))
-            pmc = pmc_all["kernels"].get(PROFILE_NAMES.get(dom, dom))
-            spl = pmc_all.get("streams_per_launch", 96)
-            if pmc and args.config == pmc_all.get("config", "c2"):
-                # every stream of a launch reads its own images: traffic per launch is proportional to the streams in it
-                roof["traffic"] = (pmc["fetch_kb_per_launch"] + pmc["write_kb_per_launch"]) * 1024.0 * per_group / spl
-                roof["traffic_note"] = ("bytes/launch, raw FETCH_SIZE+WRITE_SIZE of %s (collected at %d streams per launch, scaled to %d; "
-                                        "no gfx950 correction applied: dword loads, not the calibrated 16 B/lane stream)"
-                                        % (os.path.relpath(PMC_TRAFFIC_FILE, ROOT), spl, per_group))
-        except Exception:
-            pass
-        roof["avg_launch_us"] = avg_s * 1e6
-        roof["units_per_launch"] = units / max(launches, 1)
-        # HBM is not what bounds the track kernel (traffic is half its algorithmic bytes, it runs at a few per cent of the HBM
-        # peak): its governing roof is VALU issue.  Instructions per wave and waves per launch from the committed SQ counter pass
-        # (rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES, collected at `streams_per_launch` streams, scaled to this run's launches).
-        try:
-            sq_all = json.load(open(PMC_SQ_FILE))
-            sq = sq_all["kernels"].get(PROFILE_NAMES.get(dom, dom))
-            spl = sq_all.get("streams_per_launch", 96)
-            if sq and args.config == sq_all.get("config", "c2"):
-                wave_insts = sq["valu_insts_per_wave"] * sq["waves_per_dispatch"] * per_group / spl
-                roof["valu_issue"] = {"bound": "valu", "insts_per_wave": sq["valu_insts_per_wave"], "waves_per_launch": sq["waves_per_dispatch"] * per_group / spl,
-                                      "achieved": wave_insts / avg_s, "peak": VALU_ISSUE_PEAK, "unit": "wave-instructions/s",
-                                      "frac": wave_insts / avg_s / VALU_ISSUE_PEAK, "source": os.path.relpath(PMC_SQ_FILE, ROOT)}
-                if dom == "k_track4" and roof["units_per_launch"] > 0:
-                    # wave-instructions per point track (a wavefront carries four points: round 2's 7026 per wave = 1757 per point)
-                    roof["valu_issue"]["insts_per_point_track"] = wave_insts / roof["units_per_launch"]
-        except Exception:
-            pass
-        kernels = {k: {"ms": round(v[0], 3), "launches": v[1], "avg_us": round(v[0] * 1e3 / max(v[1], 1), 2)} for k, v in timing.items() if v[1]}
-        # FP64 matrix-core rate of the dense update kernels alone (the meaningful MFMA number is per kernel)
-        gm = timing.get("k_ekf_gemm", (0, 0, 0))
-        mfma = {"kernel": "k_ekf_gemm", "tflops": (gm[2] / (gm[0] * 1e-3) / 1e12) if gm[0] > 0 else None, "peak": FP64_PEAK_TFLOPS}
-        if mfma["tflops"] is not None:
-            mfma["frac"] = mfma["tflops"] / FP64_PEAK_TFLOPS
-            mfma["note"] = "tflops / frac are over SURVEY 8(d)'s ALGORITHMIC flops (dense-d formulas); executed_* are what the matrix cores did"
-        # executed flops: SQ_INSTS_VALU_MFMA_MOPS_F64 of the committed counter pass, per launch and mode, weighted by the modes'
-        # dispatch counts, scaled from that pass's streams per launch to this run's; over the launch time measured in THIS run
-        try:
-            mm = json.load(open(PMC_MFMA_FILE))
-            spl = mm.get("streams_per_launch", 96)
-            modes = {k: v for k, v in mm["kernels"].items() if k.startswith("k_ekf_gemm")}
-            nd = sum(v["dispatches"] for v in modes.values())
-            if nd and gm[1] > 0 and args.config == mm.get("config", "c2"):
-                gflop = sum(v["fp64_mfma_gflop_per_dispatch"] * v["dispatches"] for v in modes.values()) / nd * per_group / spl
-                t_launch = gm[0] * 1e-3 / gm[1]
-                mfma["executed_gflop_per_launch"] = gflop
-                mfma["executed_tflops"] = gflop * 1e9 / t_launch / 1e12
-                mfma["executed_frac"] = mfma["executed_tflops"] / FP64_PEAK_TFLOPS
-                mfma["executed_alone"] = {k: {"tflops": v["tflops"], "mfma_busy_pct_simd": v["mfma_busy_pct_simd"]} for k, v in modes.items()}
-                mfma["source"] = os.path.relpath(PMC_MFMA_FILE, ROOT)
-        except Exception:
-            pass
+        figures = kernel_figures(timing, args, per_group) if args.full else {}
         seq_note = ("%d distinct looping sequences per GPU, one per stream of a group" % args.unique
                     + ("" if not max_offset else "; the %d groups replay them %d frames apart (never the same stereo pair at the same time)"
                        % (n_groups, args.stagger))
@@ -731,7 +806,7 @@ def main(argv=None):
             "config": {"workload": "%s [%s]: %dx%d stereo, %d cam clones, grid %s (%d features/frame realised), 200 Hz IMU; "
                                    "KLT + EKF update on-GPU; %d independent streams per GPU batched per launch (%d host groups x %d threads%s); %s; "
                                    "pose_out.txt is not written and the reference's ever-growing path / point lists (Q20) are kept only for the %d streams whose trajectories "
-                                   "are compared with the CPU oracle"
+                                   "are dumped (stream 0) or compared with the CPU oracle (--full)"
                                    % (CONFIGS[args.config]["name"], args.config, args.width, args.height, args.clones, args.grid, n_feat, n_streams,
                                       n_groups, args.host_threads, ", FE|EKF pipelined" if pipe else "", seq_note, n_pose_streams),
                        "streams_per_gpu": n_streams, "features_per_frame": n_feat, "cam_clones": n_clones,
@@ -746,13 +821,13 @@ def main(argv=None):
                                      if (pipe and n_groups > 1) else "fixed: every batch of streams on its own group's queues"),
                        "host_throttled_ms_in_timed_region": None if thr0 is None or thr1 is None else round((thr1 - thr0) / 1e3, 1)},
             "id_mismatch": id_mismatch,
-            "value_gram_cholesky": hh["value_gram_cholesky"] if hh else None, "gram_window": hh,
-            "roofline": roof, "mfma": mfma, "kernels": kernels,
             "host_bookkeeping_us_per_stream_frame": {k: round(v * 1e6 / (n_streams * args.steps), 2) for k, v in hostprof.items()},
             "host_phases_ms_per_step": host_phases,
             "abi_host_ms_per_step": {k: round(v * 1e3 / args.steps / n_groups, 3) for k, v in abi_host.items()},
         }
-        if not args.no_cpu and world == 1 and args.cpu_frames > 0:
+        if args.full:
+            out.update({"value_gram_cholesky": hh["value_gram_cholesky"] if hh else None, "gram_window": hh}, **figures)
+        if args.full and not args.no_cpu and world == 1 and args.cpu_frames > 0:
             for s in syns:
                 s._cache.clear()
             del syns

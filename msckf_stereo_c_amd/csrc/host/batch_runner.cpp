@@ -676,7 +676,9 @@ int MultiRunner::run_balanced(int first, int warmup, int steps, int max_extra, d
                         Batch &X = B[g];
                         if (X.fe_done) continue;
                         const bool own = X.fe_next < X.from + X.cnt;
-                        if (!own && (shared.phase.load() == 2 || X.fe_next >= X.from + X.cnt + max_extra)) { X.fe_done = true; cv.notify_all(); continue; }
+                        // not while a worker is still stepping it: the filter workers leave once every batch is done, and the frame
+                        // in flight would be handed off after them, never filtered (front-end one frame ahead of frames_done)
+                        if (!own && !X.fe_busy && (shared.phase.load() == 2 || X.fe_next >= X.from + X.cnt + max_extra)) { X.fe_done = true; cv.notify_all(); continue; }
                         all_done = false;
                         if (X.fe_busy || groups_[g]->handoff.size() >= 2) continue;
                         if (b < 0 || X.fe_next - X.from < B[b].fe_next - B[b].from) b = g;
