@@ -5,14 +5,16 @@ import os
 
 import numpy as np
 
-from .ctypes_types import CORNER, POINT2F, Calib, EkfCfg, FeCfg
+from .ctypes_types import CORNER, IMU_STEP, POINT2F, Calib, EkfCfg, FeCfg, ImuStep
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 
 class MskfError(RuntimeError):
-    pass
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code        # the mskf_status, when the error came from the library
 
 
 class TrackArgs(C.Structure):
@@ -99,11 +101,20 @@ def lib():
 
 def _chk(rc):
     if rc != 0:
-        raise MskfError("mskf status %d: %s" % (rc, lib().mskf_last_error().decode()))
+        raise MskfError("mskf status %d: %s" % (rc, lib().mskf_last_error().decode()), rc)
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _imu_steps(steps):
+    """mskf_imu_step records as a contiguous IMU_STEP array (None / empty: no steps)."""
+    if steps is None:
+        return np.zeros(0, IMU_STEP)
+    a = np.ascontiguousarray(steps)
+    assert a.dtype == IMU_STEP and a.ndim == 1, a.dtype
+    return a
 
 
 class Context:
@@ -132,6 +143,61 @@ class Context:
         self.L.mskf_ekf_update_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(EkfUpdateArgs)]
         _chk(self.L.mskf_ekf_update_batch(self.h, n, hs, args))
         return [b[2]() for b in built]
+
+    def ekf_predict_batch(self, streams, steps, J):
+        """One mskf_ekf_predict_batch: streams[i] propagates over steps[i] (IMU_STEP records, None = none), then augments
+        with J[i] (6 x 21, None = no augmentation)."""
+        n = len(streams)
+        st = [_imu_steps(x) for x in steps]
+        Js = [None if j is None else np.ascontiguousarray(j, dtype=np.float64).reshape(6, 21) for j in J]
+        hs = (C.c_void_p * n)(*[s.h for s in streams])
+        ns = (C.c_int32 * n)(*[len(x) for x in st])
+        sp = (C.c_void_p * n)(*[x.ctypes.data if len(x) else None for x in st])
+        jp = (C.c_void_p * n)(*[None if j is None else j.ctypes.data for j in Js])
+        self.L.mskf_ekf_predict_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        _chk(self.L.mskf_ekf_predict_batch(self.h, n, hs, ns, sp, jp))
+
+    def ekf_remove_clones_batch(self, streams, pairs):
+        """One mskf_ekf_remove_clones_batch: pairs[i] = (a, b) clone indices of streams[i] in the current order, -1 = none."""
+        n = len(streams)
+        idx = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(n, 2))
+        hs = (C.c_void_p * n)(*[s.h for s in streams])
+        self.L.mskf_ekf_remove_clones_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+        _chk(self.L.mskf_ekf_remove_clones_batch(self.h, n, hs, _p(idx)))
+
+    def ekf_pos_var_batch(self, streams):
+        """P(12,12), P(13,13), P(14,14) of every stream, (n, 3)."""
+        out = self.ekf_pos_var_batch_begin(streams)
+        self.ekf_pos_var_batch_end()
+        return out
+
+    def ekf_pos_var_batch_begin(self, streams):
+        """Enqueue the read-out; the returned (n, 3) array is filled by ekf_pos_var_batch_end."""
+        n = len(streams)
+        out = np.full((n, 3), np.nan)
+        hs = (C.c_void_p * n)(*[s.h for s in streams])
+        self.L.mskf_ekf_get_pos_var_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+        _chk(self.L.mskf_ekf_get_pos_var_batch_begin(self.h, n, hs, _p(out)))
+        self._pv_pending = (out, hs)          # both must stay alive until _end
+        return out
+
+    def ekf_pos_var_batch_end(self):
+        self.L.mskf_ekf_get_pos_var_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_ekf_get_pos_var_batch_end(self.h))
+        self._pv_pending = None
+
+    def hip_stream(self):
+        return self.L.mskf_ctx_hip_stream(self.h)
+
+    def launch_copy(self, dst, src, nbytes):
+        """k_mskf_copy of up to 6 segments (device or pinned host addresses, 16-byte aligned) in one launch on this context's
+        HIP stream (fe_launch_copy: the staging copies of the hot path).  Asynchronous: sync() before reading."""
+        n = len(dst)
+        assert len(src) == n == len(nbytes)
+        self.L.fe_launch_copy.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p]
+        self.L.fe_launch_copy.restype = None
+        self.L.fe_launch_copy((C.c_void_p * n)(*dst), (C.c_void_p * n)(*src), (C.c_size_t * n)(*nbytes), n, self.hip_stream())
 
     def __del__(self):
         try:
@@ -244,6 +310,18 @@ class Stream:
     def ekf_remove_clone(self, idx):
         _chk(self.L.mskf_ekf_remove_clone(self.h, idx))
 
+    def ekf_propagate_imu(self, steps):
+        """mskf_ekf_propagate_imu over IMU_STEP records (Phi and Q are formed on the device)."""
+        st = _imu_steps(steps)
+        self.L.mskf_ekf_propagate_imu.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _chk(self.L.mskf_ekf_propagate_imu(self.h, len(st), st.ctypes.data if len(st) else None))
+
+    def ekf_pos_var(self):
+        out = np.full(3, np.nan)
+        self.L.mskf_ekf_get_pos_var.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(self.L.mskf_ekf_get_pos_var(self.h, _p(out)))
+        return out
+
     @staticmethod
     def _update_args(gravity, clones, positions, obs_start, obs_clone, obs_z, dof_offset, apply_row_cap, needs_init=None, init_ranges=None):
         """(mskf_ekf_update_args, buffers it points into, result builder) for one stream."""
@@ -272,6 +350,7 @@ class Stream:
         gamma = np.zeros(max(n_feat, 1))
         rows = np.zeros(1, np.int32)
         diag = np.zeros(2, np.int32)
+        pos_var = np.full(3, np.nan)
         a = EkfUpdateArgs()
         a.n_clones, a.n_feat, a.n_obs = n_clones, n_feat, len(obs_clone)
         a.dof_offset, a.apply_row_cap = dof_offset, int(apply_row_cap)
@@ -279,11 +358,13 @@ class Stream:
         a.clones, a.features, a.obs_clone, a.obs_z = clones.ctypes.data, feats.ctypes.data, obs_clone.ctypes.data, obs_z.ctypes.data
         a.delta_x, a.feat_status, a.gamma, a.rows_out = dx.ctypes.data, status.ctypes.data, gamma.ctypes.data, rows.ctypes.data
         a.diag_out = diag.ctypes.data
-        keep = (clones, feats, obs_clone, obs_z, dx, status, gamma, rows, diag)
+        a.pos_var_out = pos_var.ctypes.data
+        keep = (clones, feats, obs_clone, obs_z, dx, status, gamma, rows, diag, pos_var)
 
         def result():
             return dict(delta_x=dx, status=status[:n_feat], gamma=gamma[:n_feat], rows=int(rows[0]),
-                        positions=feats["position"].copy(), used_qr=int(diag[0]), tiny_pivots=int(diag[1]))
+                        positions=feats["position"].copy(), used_qr=int(diag[0]), tiny_pivots=int(diag[1]),
+                        pos_var=pos_var.copy())
         return a, keep, result
 
     def ekf_update(self, gravity, clones, positions, obs_start, obs_clone, obs_z, dof_offset, apply_row_cap,

@@ -47,6 +47,16 @@ class ImuSample(C.Structure):
                 ("linear_acceleration", C.c_double * 3)]
 
 
+class ImuStep(C.Structure):
+    """mskf_imu_step (include/mskf_hip.h): what the covariance part of processModel needs for one IMU sample."""
+    _fields_ = [("dt", C.c_double), ("gyro", C.c_double * 3), ("acc", C.c_double * 3), ("R_t", C.c_double * 9),
+                ("Phi00", C.c_double * 9), ("u", C.c_double * 3), ("s", C.c_double * 3), ("w1", C.c_double * 3),
+                ("w2", C.c_double * 3)]
+
+
+assert C.sizeof(ImuStep) == 37 * 8
+
+
 class TrackingInfo(C.Structure):
     _fields_ = [("time_stamp", C.c_double), ("before_tracking", C.c_int32), ("after_tracking", C.c_int32),
                 ("after_matching", C.c_int32), ("after_ransac", C.c_int32)]
@@ -57,6 +67,8 @@ POINT2F = np.dtype([("x", "<f4"), ("y", "<f4")])
 CORNER = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<i4"), ("cell", "<i4")])
 FEATURE_MEAS = np.dtype([("id", "<u4"), ("_pad", "<u4"), ("u0", "<f8"), ("v0", "<f8"), ("u1", "<f8"), ("v1", "<f8")])
 POSE = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4)])
+IMU_STEP = np.dtype([(name, "<f8", C.sizeof(ty) // 8) if C.sizeof(ty) > 8 else (name, "<f8") for name, ty in ImuStep._fields_])
+assert IMU_STEP.itemsize == C.sizeof(ImuStep)
 
 COMPAT_REFERENCE = 15     # Q1 | Q2 | Q4 | Q5 (include/mskf_types.h)
 
