@@ -65,7 +65,8 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
  * is kept for ABI stability and stays empty since the per-point geometry moved into that launch; pyramid: output pixels;
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
- * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured. */
+ * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
+ * stability and counts no launch: the augmentation runs inside k_ekf_propagate (MSKF_K_EKF_PROPAGATE), also for mskf_ekf_augment. */
 enum {
     MSKF_K_PYR = 0, MSKF_K_DETECT, MSKF_K_LK, MSKF_K_EKF_PROPAGATE, MSKF_K_EKF_AUGMENT, MSKF_K_EKF_FEATURES,
     MSKF_K_EKF_TSQR /* k_ekf_tsqr; rounds 1-3: the stacking-decision kernel, which no longer exists */, MSKF_K_EKF_GEMM, MSKF_K_EKF_CHOL, MSKF_K_EKF_TRSM, MSKF_K_EKF_SMALL, MSKF_K_EKF_REMOVE, MSKF_K_PT_GEOM, MSKF_K_FE_BOOK, MSKF_K_COUNT
@@ -152,7 +153,14 @@ int mskf_fe_track_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const
 /* The same in two halves, so that a host thread can prepare another batch (on another context, possibly sharing this
  * one's HIP stream: mskf_ctx_create_shared) while the device works: _begin validates, stages and enqueues everything and
  * returns; _end waits and copies the results into the args passed to _begin (they and their arrays must still be valid).
- * One pending batch per context. */
+ * One pending batch per context.  The same holds for every _begin / _end pair of this header:
+ *   - while a batch is pending, calls that need the staging buffers it owns fail with MSKF_ERR_INVALID, and mskf_last_error
+ *     names the pending batch: a track or device-frame batch blocks the front-end calls (push, track, frame), an update
+ *     batch blocks the next update, a position-variance read-out blocks every prediction, augmentation and clone removal;
+ *   - a failed _end (the wait timed out or the stream reported an error) leaves the batch pending: its kernels may still
+ *     be running.  _end may be called again; mskf_ctx_destroy drains the stream as always;
+ *   - a failed _begin leaves nothing pending and nothing running: if it had enqueued work, it synchronises the context's
+ *     stream before it returns the error. */
 int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_fe_track_args *args);
 int mskf_fe_track_batch_end(mskf_ctx *ctx);
 
@@ -265,7 +273,8 @@ typedef struct mskf_imu_step {
 int mskf_ekf_reset(mskf_stream *s, const double *P0 /* 21x21 row-major */);
 int mskf_ekf_propagate_imu(mskf_stream *s, int n_steps, const mskf_imu_step *steps);
 /* One fused launch for many streams: IMU propagation over n_steps[i] samples followed (J[i] != NULL) by the
- * state augmentation.  Equivalent to mskf_ekf_propagate_imu + mskf_ekf_augment per stream. */
+ * state augmentation.  mskf_ekf_propagate_imu, mskf_ekf_propagate and mskf_ekf_augment are batches of one of it, so
+ * mskf_ekf_propagate_imu followed by mskf_ekf_augment gives the same bits. */
 int mskf_ekf_predict_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *n_steps,
                            const mskf_imu_step *const *steps, const double *const *J);
 /* position variances P(12,12), P(13,13), P(14,14) for onlineReset (msckf_vio.cpp:1194-1196). Synchronises. */

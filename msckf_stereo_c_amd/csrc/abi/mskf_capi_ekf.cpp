@@ -8,7 +8,6 @@
 
 extern "C" {
 void ekf_launch_propagate(const EkfStreamDev *d, int n, hipStream_t st);
-void ekf_launch_augment(const EkfStreamDev *d, int n, hipStream_t st);
 void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st);
 void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave, const int *work_small, int n_small, const int *work_big, int n_big,
                          int max_rows, int max_rows_small, int big_clones, hipStream_t st);
@@ -37,31 +36,12 @@ int dev_alloc(double **p, size_t n, hipStream_t st) {
     MSKF_HIPCHK(hipMemsetAsync(*p, 0, n * sizeof(double), st));
     return MSKF_OK;
 }
-
-// a pinned host arena with a device twin and an event guarding reuse of the host side
-int arena_ensure(char **h, char **d, size_t *cap, size_t need) {
-    if (need <= *cap) return MSKF_OK;
-    // (single-stream entry points only — mskf_ekf_propagate / _augment —, not on the batched path: see PinnedDev::ensure for why
-    // a running pipeline must not free)
-    if (*h) (void)hipHostFree(*h);
-    if (*d) (void)hipFree(*d);
-    *h = *d = nullptr; *cap = 0;
-    const size_t c = align_up(need + need / 2, 4096);
-    MSKF_HIPCHK(hipHostMalloc((void **)h, c, hipHostMallocDefault));
-    MSKF_HIPCHK(hipMalloc((void **)d, c));
-    *cap = c;
-    return MSKF_OK;
-}
 }  // namespace
 
 struct EkfExtra {  // lives behind EkfStreamState via the stream (kept out of the device header)
     EkfStreamDev desc_static;         // constant part of the stream's descriptors (base_desc)
     bool desc_valid = false;
     double *P_alt = nullptr;          // ping-pong target of clone removal
-    char *h_small = nullptr, *d_small = nullptr;   // Phi/Q sequence, J
-    size_t small_cap = 0;
-    hipEvent_t small_done = nullptr;
-    bool small_pending = false;
     std::vector<double *> retired_hs; // stacked-Jacobian blocks from hipMalloc that were outgrown: freed with the stream (hipFree inside a run waits for the whole device)
 };
 static EkfExtra *extra_of(mskf_stream *s) { return (EkfExtra *)s->ekf_extra; }
@@ -114,7 +94,6 @@ int mskf_ekf_stream_init(mskf_stream *s) {
     tab[0] = 0.0;
     for (int i = 1; i < 100; ++i) tab[i] = s->ekf.chi2_mode == 1 ? mskf_chi2_ppf95[i - 1] : mskf_chi2_ppf05[i - 1];  // msckf_vio.cpp:181-185
     MSKF_HIPCHK(hipMemcpy(E.chi2, tab, sizeof(tab), hipMemcpyHostToDevice));
-    MSKF_HIPCHK(hipEventCreateWithFlags(&X->small_done, hipEventDisableTiming));
     return MSKF_OK;
 }
 
@@ -122,15 +101,8 @@ void mskf_ekf_stream_free(mskf_stream *s) {
     EkfStreamState &E = s->ekf_state;
     if (E.pool) (void)hipFree(E.pool);          // P, T, S, W, P_alt, act, gate_S, chi2
     if (E.Hs) { if (E.hs_async) (void)hipFreeAsync(E.Hs, s->ctx_ekf->stream); else (void)hipFree(E.Hs); }      // Hs + rowmask
-    if (E.h_arena) (void)hipHostFree(E.h_arena);
-    if (E.d_arena) (void)hipFree(E.d_arena);
-    if (E.h_out) (void)hipHostFree(E.h_out);
-    if (E.d_out) (void)hipFree(E.d_out);
     if (EkfExtra *X = extra_of(s)) {
         for (double *p : X->retired_hs) (void)hipFree(p);
-        if (X->h_small) (void)hipHostFree(X->h_small);
-        if (X->d_small) (void)hipFree(X->d_small);
-        if (X->small_done) (void)hipEventDestroy(X->small_done);
         delete X;
         s->ekf_extra = nullptr;
     }
@@ -164,16 +136,6 @@ static void base_desc(const mskf_stream *s, EkfStreamDev &D) {
     D = X->desc_static;
     D.P = E.P; D.d = E.d;
     D.Hs = E.Hs; D.rowmask = (unsigned long long *)E.rs;
-}
-
-static int small_begin(mskf_stream *s, EkfExtra *X, size_t bytes) {
-    if (X->small_pending) { MSKF_HIPCHK(hipEventSynchronize(X->small_done)); X->small_pending = false; }
-    if (bytes > X->small_cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(s->ctx_ekf->stream));
-        int rc = arena_ensure(&X->h_small, &X->d_small, &X->small_cap, bytes);
-        if (rc != MSKF_OK) return rc;
-    }
-    return MSKF_OK;
 }
 
 extern "C" int mskf_ekf_reset(mskf_stream *s, const double *P0) {
@@ -227,114 +189,96 @@ extern "C" int mskf_ekf_get_cov(mskf_stream *s, double *P, int capacity) {
     return MSKF_OK;
 }
 
-extern "C" int mskf_ekf_propagate(mskf_stream *s, int n_steps, const double *Phi, const double *Q) {
-    if (!s || n_steps < 0 || (n_steps && (!Phi || !Q))) return MSKF_ERR_INVALID;
-    if (n_steps == 0) return MSKF_OK;
-    EkfExtra *X = extra_of(s);
-    mskf_ctx *ctx = s->ctx_ekf;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    const size_t nn = EKF_IMU_DIM * EKF_IMU_DIM;
-    const size_t bytes = sizeof(double) * 2 * nn * (size_t)n_steps + sizeof(EkfStreamDev);
-    int rc = small_begin(s, X, bytes);
+// The one prediction routine.  Per stream n_steps[i] IMU steps (Phi_k, Q_k formed inside k_ekf_propagate) or, with Phi / Q
+// given, n_steps[i] pairs (Phi_k, Q_k) formed by the caller; then the state augmentation with J[i] where it is not NULL.
+// One staging copy through pred_arena and one launch for the whole batch; the single-stream calls are batches of one.
+static int predict(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *n_steps, const mskf_imu_step *const *steps,
+                   const double *const *Phi, const double *const *Q, const double *const *J) {
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);
     if (rc != MSKF_OK) return rc;
-    EkfStreamDev *D = (EkfStreamDev *)X->h_small;
-    double *pq = (double *)(X->h_small + sizeof(EkfStreamDev));
-    for (int k = 0; k < n_steps; ++k) {
-        std::memcpy(pq + (size_t)k * 2 * nn, Phi + (size_t)k * nn, sizeof(double) * nn);
-        std::memcpy(pq + (size_t)k * 2 * nn + nn, Q + (size_t)k * nn, sizeof(double) * nn);
+    const size_t nn = EKF_IMU_DIM * EKF_IMU_DIM, j_bytes = align_up(sizeof(double) * 6 * EKF_IMU_DIM, 64);
+    auto seq_bytes = [&](int i) { return align_up((Phi ? sizeof(double) * 2 * nn : sizeof(mskf_imu_step)) * (size_t)n_steps[i], 64); };
+    size_t bytes = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        if (!s || s->ctx_ekf != ctx || n_steps[i] < 0 || (n_steps[i] && (Phi ? !Phi[i] || !Q[i] : !steps[i]))) return MSKF_ERR_INVALID;
+        if (J[i] && s->ekf_state.d + 6 > EKF_IMU_DIM + 6 * s->ekf_state.max_clones) { mskf_set_error("clone capacity exceeded"); return MSKF_ERR_CAPACITY; }
+        bytes += seq_bytes(i) + (J[i] ? j_bytes : 0);
+        any |= n_steps[i] > 0 || J[i];
     }
-    base_desc(s, *D);
-    D->PhiQ = (const double *)(X->d_small + sizeof(EkfStreamDev));
-    D->n_steps = n_steps;
-    MSKF_HIPCHK(hipMemcpyAsync(X->d_small, X->h_small, bytes, hipMemcpyHostToDevice, ctx->stream));
-    MSKF_HIPCHK(hipEventRecord(X->small_done, ctx->stream));
-    X->small_pending = true;
-    ekf_launch_propagate((const EkfStreamDev *)X->d_small, 1, ctx->stream);
-    MSKF_HIPCHK(hipGetLastError());
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ekf_propagate_imu(mskf_stream *s, int n_steps, const mskf_imu_step *steps) {
-    if (!s || n_steps < 0 || (n_steps && !steps)) return MSKF_ERR_INVALID;
-    if (n_steps == 0) return MSKF_OK;
-    EkfExtra *X = extra_of(s);
-    mskf_ctx *ctx = s->ctx_ekf;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(EkfStreamDev) + sizeof(mskf_imu_step) * (size_t)n_steps;
-    int rc = small_begin(s, X, bytes);
-    if (rc != MSKF_OK) return rc;
-    EkfStreamDev *D = (EkfStreamDev *)X->h_small;
-    std::memcpy(X->h_small + sizeof(EkfStreamDev), steps, sizeof(mskf_imu_step) * (size_t)n_steps);
-    base_desc(s, *D);
-    D->imu_steps = (const mskf_imu_step *)(X->d_small + sizeof(EkfStreamDev));
-    D->n_steps = n_steps;
-    MSKF_HIPCHK(hipMemcpyAsync(X->d_small, X->h_small, bytes, hipMemcpyHostToDevice, ctx->stream));
-    MSKF_HIPCHK(hipEventRecord(X->small_done, ctx->stream));
-    X->small_pending = true;
-    {
-        const int ts = mskf_t_begin(ctx, MSKF_K_EKF_PROPAGATE);
-        ekf_launch_propagate((const EkfStreamDev *)X->d_small, 1, ctx->stream);
-        mskf_t_end(ctx, ts, 1);
-    }
-    MSKF_HIPCHK(hipGetLastError());
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ekf_predict_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *n_steps,
-                                      const mskf_imu_step *const *steps, const double *const *J) {
-    if (!ctx || n <= 0 || !streams || !n_steps || !steps || !J) return MSKF_ERR_INVALID;
-    // (the position-variance read-out works out of the same pinned arena, its kernel reads its descriptors there: not before its _end)
-    if (ctx->pend_pv.active) { mskf_set_error("a position-variance read-out of this context is still pending"); return MSKF_ERR_INVALID; }
+    if (!any) return MSKF_OK;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    size_t bytes = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
-    for (int i = 0; i < n; ++i) {
-        if (!streams[i] || streams[i]->ctx_ekf != ctx || n_steps[i] < 0 || (n_steps[i] && !steps[i])) return MSKF_ERR_INVALID;
-        bytes += align_up(sizeof(mskf_imu_step) * (size_t)n_steps[i], 64) + align_up(sizeof(double) * 6 * EKF_IMU_DIM, 64);
-    }
-    if (!ctx->pred_done) MSKF_HIPCHK(hipEventCreateWithFlags(&ctx->pred_done, hipEventDisableTiming));
-    if (ctx->pred_pending) { MSKF_HIPCHK(hipEventSynchronize(ctx->pred_done)); ctx->pred_pending = false; }
-    if (bytes > ctx->pred_arena.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        int rc = ctx->pred_arena.ensure(bytes);
-        if (rc != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->pred_arena.fence_wait()) != MSKF_OK || (rc = ctx->pred_arena.ensure(bytes)) != MSKF_OK) return rc;
     char *h = ctx->pred_arena.h, *dv = ctx->pred_arena.d;
     EkfStreamDev *D = (EkfStreamDev *)h;
     size_t off = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
-    bool any = false;
     for (int i = 0; i < n; ++i) {
-        mskf_stream *s = streams[i];
-        EkfStreamState &E = s->ekf_state;
-        base_desc(s, D[i]);
+        base_desc(streams[i], D[i]);
         D[i].n_steps = n_steps[i];
-        if (n_steps[i] > 0) {
-            D[i].PhiQ = nullptr;                           // Phi_k, Q_k are built inside k_ekf_propagate from the IMU steps
+        if (n_steps[i] > 0 && Phi) {
+            double *pq = (double *)(h + off);
+            for (int k = 0; k < n_steps[i]; ++k) {
+                std::memcpy(pq + (size_t)k * 2 * nn, Phi[i] + (size_t)k * nn, sizeof(double) * nn);
+                std::memcpy(pq + (size_t)k * 2 * nn + nn, Q[i] + (size_t)k * nn, sizeof(double) * nn);
+            }
+            D[i].PhiQ = (const double *)(dv + off);
+        } else if (n_steps[i] > 0) {
             std::memcpy(h + off, steps[i], sizeof(mskf_imu_step) * (size_t)n_steps[i]);
             D[i].imu_steps = (const mskf_imu_step *)(dv + off);
-            off += align_up(sizeof(mskf_imu_step) * (size_t)n_steps[i], 64);
-            any = true;
         }
+        off += seq_bytes(i);
         if (J[i]) {
-            if (E.d + 6 > EKF_IMU_DIM + 6 * E.max_clones) { mskf_set_error("clone capacity exceeded"); return MSKF_ERR_CAPACITY; }
             std::memcpy(h + off, J[i], sizeof(double) * 6 * EKF_IMU_DIM);
             D[i].J = (const double *)(dv + off);
-            off += align_up(sizeof(double) * 6 * EKF_IMU_DIM, 64);
-            any = true;
+            off += j_bytes;
         }
     }
-    if (!any) return MSKF_OK;
-    { const MskfCopy cp = {dv, h, off}; const int crc = mskf_copy_async(ctx, &cp, 1); if (crc != MSKF_OK) return crc; }
-    MSKF_HIPCHK(hipEventRecord(ctx->pred_done, st));
-    ctx->pred_pending = true;
+    DrainOnError drain{st, true};
+    { const MskfCopy cp = {dv, h, off}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
+    if ((rc = ctx->pred_arena.fence_record(st)) != MSKF_OK) return rc;
     {
         const int ts = mskf_t_begin(ctx, MSKF_K_EKF_PROPAGATE);
         ekf_launch_propagate((const EkfStreamDev *)dv, n, st);
         mskf_t_end(ctx, ts, n);
     }
     MSKF_HIPCHK(hipGetLastError());
+    drain.armed = false;
     for (int i = 0; i < n; ++i) if (J[i]) streams[i]->ekf_state.d += 6;
     return MSKF_OK;
+}
+
+extern "C" int mskf_ekf_predict_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *n_steps,
+                                      const mskf_imu_step *const *steps, const double *const *J) {
+    if (!ctx || n <= 0 || !streams || !n_steps || !steps || !J) return MSKF_ERR_INVALID;
+    return predict(ctx, n, streams, n_steps, steps, nullptr, nullptr, J);
+}
+
+extern "C" int mskf_ekf_propagate(mskf_stream *s, int n_steps, const double *Phi, const double *Q) {
+    if (!s) return MSKF_ERR_INVALID;
+    mskf_stream *ss[1] = {s};
+    const int32_t ns[1] = {n_steps};
+    const double *phi[1] = {Phi}, *q[1] = {Q}, *j[1] = {nullptr};
+    return predict(s->ctx_ekf, 1, ss, ns, nullptr, phi, q, j);
+}
+
+extern "C" int mskf_ekf_propagate_imu(mskf_stream *s, int n_steps, const mskf_imu_step *steps) {
+    if (!s) return MSKF_ERR_INVALID;
+    mskf_stream *ss[1] = {s};
+    const int32_t ns[1] = {n_steps};
+    const mskf_imu_step *st[1] = {steps};
+    const double *j[1] = {nullptr};
+    return predict(s->ctx_ekf, 1, ss, ns, st, nullptr, nullptr, j);
+}
+
+extern "C" int mskf_ekf_augment(mskf_stream *s, const double *J) {
+    if (!s || !J) return MSKF_ERR_INVALID;
+    mskf_stream *ss[1] = {s};
+    const int32_t ns[1] = {0};
+    const mskf_imu_step *st[1] = {nullptr};
+    const double *j[1] = {J};
+    return predict(s->ctx_ekf, 1, ss, ns, st, nullptr, nullptr, j);
 }
 
 extern "C" int mskf_ekf_get_pos_var_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out) {
@@ -344,27 +288,23 @@ extern "C" int mskf_ekf_get_pos_var_batch(mskf_ctx *ctx, int n, mskf_stream *con
 
 extern "C" int mskf_ekf_get_pos_var_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out) {
     if (!ctx || n <= 0 || !streams || !out) return MSKF_ERR_INVALID;
-    if (ctx->pend_pv.active) return MSKF_ERR_INVALID;
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);
+    if (rc != MSKF_OK) return rc;
+    for (int i = 0; i < n; ++i) if (!streams[i] || streams[i]->ctx_ekf != ctx) return MSKF_ERR_INVALID;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t desc_bytes = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
     const size_t bytes = desc_bytes + sizeof(double) * 3 * (size_t)n;
-    if (!ctx->pred_done) MSKF_HIPCHK(hipEventCreateWithFlags(&ctx->pred_done, hipEventDisableTiming));
-    if (ctx->pred_pending) { MSKF_HIPCHK(hipEventSynchronize(ctx->pred_done)); ctx->pred_pending = false; }
-    if (bytes > ctx->pred_arena.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        int rc = ctx->pred_arena.ensure(bytes);
-        if (rc != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->pred_arena.fence_wait()) != MSKF_OK || (rc = ctx->pred_arena.ensure(bytes)) != MSKF_OK) return rc;
     EkfStreamDev *D = (EkfStreamDev *)ctx->pred_arena.h;
-    for (int i = 0; i < n; ++i) {
-        if (!streams[i] || streams[i]->ctx_ekf != ctx) return MSKF_ERR_INVALID;
-        base_desc(streams[i], D[i]);
-    }
+    for (int i = 0; i < n; ++i) base_desc(streams[i], D[i]);
     // (no staging copies: the kernel reads its descriptors from the pinned arena and writes the 3 n doubles straight into it)
+    DrainOnError drain{st, true};
     ekf_launch_posvar((const EkfStreamDev *)ctx->pred_arena.h, n, (double *)(ctx->pred_arena.h + desc_bytes), st);
-    { const int wrc = mskf_wait_event(ctx, &ctx->pend_pv.done, true); if (wrc != MSKF_OK) return wrc; }
-    ctx->pend_pv.active = true; ctx->pend_pv.n = n; ctx->pend_pv.out = out; ctx->pend_pv.desc_bytes = desc_bytes;
+    mskf_ctx::PendingPosVar &V = ctx->pend_pv;
+    V.n = n; V.out = out; V.desc_bytes = desc_bytes;
+    if ((rc = mskf_batch_arm(ctx, V)) != MSKF_OK) return rc;
+    drain.armed = false;
     return MSKF_OK;
 }
 
@@ -372,8 +312,8 @@ extern "C" int mskf_ekf_get_pos_var_batch_end(mskf_ctx *ctx) {
     if (!ctx) return MSKF_ERR_INVALID;
     if (!ctx->pend_pv.active) return MSKF_OK;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
-    ctx->pend_pv.active = false;
-    { const int wrc = mskf_wait_event(ctx, &ctx->pend_pv.done, false); if (wrc != MSKF_OK) return wrc; }
+    const int rc = mskf_batch_finish(ctx, ctx->pend_pv);
+    if (rc != MSKF_OK) return rc;
     mskf_t_collect(ctx);
     std::memcpy(ctx->pend_pv.out, ctx->pred_arena.h + ctx->pend_pv.desc_bytes, sizeof(double) * 3 * (size_t)ctx->pend_pv.n);
     return MSKF_OK;
@@ -385,48 +325,14 @@ extern "C" int mskf_ekf_get_pos_var(mskf_stream *s, double out[3]) {
     return mskf_ekf_get_pos_var_batch(s->ctx_ekf, 1, ss, out);
 }
 
-extern "C" int mskf_ekf_augment(mskf_stream *s, const double *J) {
-    if (!s || !J) return MSKF_ERR_INVALID;
-    EkfStreamState &E = s->ekf_state;
-    if (E.d + 6 > EKF_IMU_DIM + 6 * E.max_clones) { mskf_set_error("clone capacity exceeded"); return MSKF_ERR_CAPACITY; }
-    EkfExtra *X = extra_of(s);
-    mskf_ctx *ctx = s->ctx_ekf;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    // the augment descriptor lives after a possible propagate descriptor: use a second region of the small arena
-    const size_t off = 0;
-    const size_t bytes = sizeof(EkfStreamDev) + sizeof(double) * 6 * EKF_IMU_DIM;
-    int rc = small_begin(s, X, bytes);
-    if (rc != MSKF_OK) return rc;
-    EkfStreamDev *D = (EkfStreamDev *)(X->h_small + off);
-    base_desc(s, *D);
-    std::memcpy(X->h_small + off + sizeof(EkfStreamDev), J, sizeof(double) * 6 * EKF_IMU_DIM);
-    D->J = (const double *)(X->d_small + off + sizeof(EkfStreamDev));
-    MSKF_HIPCHK(hipMemcpyAsync(X->d_small + off, X->h_small + off, bytes, hipMemcpyHostToDevice, ctx->stream));
-    MSKF_HIPCHK(hipEventRecord(X->small_done, ctx->stream));
-    X->small_pending = true;
-    {
-        const int ts = mskf_t_begin(ctx, MSKF_K_EKF_AUGMENT);
-        ekf_launch_augment((const EkfStreamDev *)(X->d_small + off), 1, ctx->stream);
-        mskf_t_end(ctx, ts, 1);
-    }
-    MSKF_HIPCHK(hipGetLastError());
-    E.d += 6;
-    return MSKF_OK;
-}
-
 extern "C" int mskf_ekf_remove_clones_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *idx) {
     if (!ctx || n <= 0 || !streams || !idx) return MSKF_ERR_INVALID;
-    if (ctx->pend_pv.active) { mskf_set_error("a position-variance read-out of this context is still pending"); return MSKF_ERR_INVALID; }
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);
+    if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t bytes = sizeof(EkfStreamDev) * (size_t)n;
-    if (!ctx->pred_done) MSKF_HIPCHK(hipEventCreateWithFlags(&ctx->pred_done, hipEventDisableTiming));
-    if (ctx->pred_pending) { MSKF_HIPCHK(hipEventSynchronize(ctx->pred_done)); ctx->pred_pending = false; }
-    if (bytes > ctx->pred_arena.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        int rc = ctx->pred_arena.ensure(bytes);
-        if (rc != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->pred_arena.fence_wait()) != MSKF_OK || (rc = ctx->pred_arena.ensure(bytes)) != MSKF_OK) return rc;
     EkfStreamDev *D = (EkfStreamDev *)ctx->pred_arena.h;
     bool any = false;
     for (int i = 0; i < n; ++i) {
@@ -444,15 +350,16 @@ extern "C" int mskf_ekf_remove_clones_batch(mskf_ctx *ctx, int n, mskf_stream *c
         any |= a >= 0;
     }
     if (!any) return MSKF_OK;
-    { const MskfCopy cp = {ctx->pred_arena.d, ctx->pred_arena.h, bytes}; const int crc = mskf_copy_async(ctx, &cp, 1); if (crc != MSKF_OK) return crc; }
-    MSKF_HIPCHK(hipEventRecord(ctx->pred_done, st));
-    ctx->pred_pending = true;
+    DrainOnError drain{st, true};
+    { const MskfCopy cp = {ctx->pred_arena.d, ctx->pred_arena.h, bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
+    if ((rc = ctx->pred_arena.fence_record(st)) != MSKF_OK) return rc;
     {
         const int ts = mskf_t_begin(ctx, MSKF_K_EKF_REMOVE);
         ekf_launch_remove_clone((const EkfStreamDev *)ctx->pred_arena.d, n, st);
         mskf_t_end(ctx, ts, n);
     }
     MSKF_HIPCHK(hipGetLastError());
+    drain.armed = false;
     for (int i = 0; i < n; ++i) {
         const EkfStreamDev &Di = D[i];
         if (Di.remove_index < 0) continue;
@@ -479,11 +386,13 @@ extern "C" int mskf_ekf_update_batch(mskf_ctx *ctx, int n, mskf_stream *const *s
 
 extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_update_args *args) {
     if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
-    if (ctx->pend_upd.active) { mskf_set_error("an update batch of this context is still pending (call mskf_ekf_update_batch_end)"); return MSKF_ERR_INVALID; }
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);
+    if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     const auto t_h0 = std::chrono::steady_clock::now();
     hipStream_t st = ctx->stream;
-    int rc = ctx->ekf_desc.ensure(n);
+    DrainOnError drain{st};
+    rc = ctx->ekf_desc.ensure(n);
     if (rc != MSKF_OK) return rc;
     int max_feat = 0, max_m = 0, max_d = 0, max_frows = 0, max_tri = 0, max_clones_cfg = 0;
     // Which kernels handle a stream is decided per STREAM, from that stream's features alone (EkfStreamDev::route): the same
@@ -579,6 +488,7 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
             const int cap = std::min(kMaxRows, std::max(2048, m_total + m_total / 2));
             const size_t bytes = ((size_t)cap * E.ld + (size_t)cap) * sizeof(double);
             double *grown = nullptr;
+            drain.armed = true;
             MSKF_HIPCHK(hipMallocAsync((void **)&grown, bytes, st));
             if (hipMemsetAsync(grown, 0, bytes, st) != hipSuccess) { (void)hipFreeAsync(grown, st); mskf_set_error("hipMemsetAsync of the grown stacked-Jacobian buffer failed"); return MSKF_ERR_HIP; }
             if (E.Hs) { if (E.hs_async) (void)hipFreeAsync(E.Hs, st); else extra_of(s)->retired_hs.push_back(E.Hs); }      // (rs lives behind Hs in the same allocation)
@@ -615,11 +525,7 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
     for (int c = 0; c < 3; ++c) for (int i = 0; i < n; ++i) n_work[c] += std::min(cnt_cls[(size_t)c * n + i], EKF_SLOTS);
     const size_t work_off = in_bytes;
     in_bytes = align_up(in_bytes + sizeof(int) * (size_t)(n_work[0] + n_work[1] + n_work[2]), 64);
-    if (in_bytes > ctx->upd_in.cap || out_bytes > ctx->upd_out.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        if ((rc = ctx->upd_in.ensure(in_bytes)) != MSKF_OK) return rc;
-        if ((rc = ctx->upd_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->upd_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->upd_out.ensure(out_bytes)) != MSKF_OK) return rc;
     char *hin = ctx->upd_in.h, *din = ctx->upd_in.d, *hout = ctx->upd_out.h, *dout = ctx->upd_out.d;
     {
         int *w = (int *)(hin + work_off);
@@ -674,6 +580,7 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
     }
     if (max_feat > 0) {
         {
+            drain.armed = true;
             const MskfCopy cp[2] = {{din, hin, in_bytes}, {ctx->ekf_desc.d, ctx->ekf_desc.h, sizeof(EkfStreamDev) * (size_t)n}};
             if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
         }
@@ -738,16 +645,18 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
         (void)max_m;
         MSKF_HIPCHK(hipGetLastError());
         { const MskfCopy cp = {hout, dout, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
-        if ((rc = mskf_wait_event(ctx, &ctx->pend_upd.done, true)) != MSKF_OK) return rc;
     }
     {
         mskf_ctx::PendingUpdate &U = ctx->pend_upd;
-        U.active = true; U.launched = max_feat > 0; U.n = n; U.streams = streams; U.args = args;
+        U.launched = max_feat > 0; U.n = n; U.streams = streams; U.args = args;
         U.lay.resize((size_t)5 * n);
         for (int i = 0; i < n; ++i) {
             U.lay[5 * i] = lay[i].o_dx; U.lay[5 * i + 1] = lay[i].o_gamma; U.lay[5 * i + 2] = lay[i].o_rows;
             U.lay[5 * i + 3] = lay[i].o_status; U.lay[5 * i + 4] = lay[i].o_pos;
         }
+        if (!U.launched) U.active = true;            // nothing launched, no mark: _end only fills the outputs
+        else if ((rc = mskf_batch_arm(ctx, U)) != MSKF_OK) return rc;
+        drain.armed = false;
     }
     if (ctx->t_gate) ctx->host_s[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
@@ -760,10 +669,10 @@ extern "C" int mskf_ekf_update_batch_end(mskf_ctx *ctx) {
     mskf_ctx::PendingUpdate &U = ctx->pend_upd;
     if (!U.active) return MSKF_OK;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
-    U.active = false;
-    if (U.launched) {
-        int rc;
-        if ((rc = mskf_wait_event(ctx, &U.done, false)) != MSKF_OK) return rc;
+    if (!U.launched) U.active = false;
+    else {
+        const int rc = mskf_batch_finish(ctx, U);
+        if (rc != MSKF_OK) return rc;
         mskf_t_collect(ctx);
     }
     const auto t_h1 = std::chrono::steady_clock::now();

@@ -64,11 +64,10 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     for (int i = 0; i < 3; ++i) c->desc[i].release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
     c->jobs.release();
-    c->book_desc.release(); c->book_out.release();
+    c->book_desc.release(); c->book_out.release(); c->grid_in.release();
     if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
     c->ekf_desc.release();
     c->pred_arena.release();
-    if (c->pred_done) (void)hipEventDestroy(c->pred_done);
     if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
     if (c->flag_h) (void)hipHostFree((void *)c->flag_h);
     if (c->cell_ev) (void)hipEventDestroy(c->cell_ev);
@@ -84,11 +83,6 @@ extern "C" size_t fe_book_lds_budget(void);
 
 extern "C" void fe_launch_copy(void *const *dst, const void *const *src, const size_t *bytes, int n_segs, hipStream_t st);
 int mskf_copy_async(mskf_ctx *c, const MskfCopy *segs, int n) {
-    static const bool sdma = [] { const char *e = std::getenv("MSKF_SDMA_COPIES"); return e && e[0] == '1'; }();
-    if (sdma) {
-        for (int i = 0; i < n; ++i) if (segs[i].bytes) MSKF_HIPCHK(hipMemcpyAsync(segs[i].dst, segs[i].src, segs[i].bytes, hipMemcpyDefault, c->stream));
-        return MSKF_OK;
-    }
     for (int i0 = 0; i0 < n; i0 += MSKF_COPY_SEGS) {
         void *dst[MSKF_COPY_SEGS]; const void *src[MSKF_COPY_SEGS]; size_t bytes[MSKF_COPY_SEGS];
         int m = 0;
@@ -174,6 +168,37 @@ int mskf_wait_event(mskf_ctx *c, hipEvent_t *ev_slot, bool record) {
     }
     return MSKF_OK;
 }
+
+int mskf_batch_arm(mskf_ctx *c, PendingBatch &b) {
+    const int rc = mskf_wait_event(c, &b.done, true);
+    if (rc == MSKF_OK) b.active = true;
+    return rc;
+}
+int mskf_batch_finish(mskf_ctx *c, PendingBatch &b) {
+    const int rc = mskf_wait_event(c, &b.done, false);
+    if (rc == MSKF_OK) b.active = false;
+    return rc;
+}
+
+int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which) {
+    const char *owner = nullptr;
+    switch (which) {
+        case MSKF_ARENAS_FE:
+            if (c->pend_trk.active) owner = "a track batch of this context is still pending (call mskf_fe_track_batch_end)";
+            else if (c->pend_frame.active) owner = "a device frame of this context is still pending (call mskf_fe_frame_batch_end)";
+            break;
+        case MSKF_ARENAS_UPDATE:
+            if (c->pend_upd.active) owner = "an update batch of this context is still pending (call mskf_ekf_update_batch_end)";
+            break;
+        case MSKF_ARENAS_PRED:
+            if (c->pend_pv.active) owner = "a position-variance read-out of this context is still pending (call mskf_ekf_get_pos_var_batch_end)";
+            break;
+    }
+    if (!owner) return MSKF_OK;
+    mskf_set_error(owner);
+    return MSKF_ERR_INVALID;
+}
+
 int mskf_wait(mskf_ctx *c) {
     int rc = mskf_wait_event(c, &c->wait_ev, true);
     if (rc != MSKF_OK) return rc;
@@ -474,10 +499,11 @@ extern "C" int mskf_fe_push_stereo_batch(mskf_ctx *ctx, int n, mskf_stream *cons
 static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, bool copy_cells) {
     if (!ctx || n <= 0 || !streams || !cam0 || !cam1) return MSKF_ERR_INVALID;
     // the pinned staging of a pending batch (descriptors, pyramid jobs, the cell arena) may still be in flight
-    if (ctx->pend_frame.active || ctx->pend_trk.active) { mskf_set_error("a batch of this context is still pending"); return MSKF_ERR_INVALID; }
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
+    if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    int rc = ctx->jobs.ensure((size_t)n * 2);
+    rc = ctx->jobs.ensure((size_t)n * 2);
     if (rc != MSKF_OK) return rc;
     rc = ctx->desc[0].ensure(n);
     if (rc != MSKF_OK) return rc;
@@ -485,7 +511,7 @@ static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const u
     size_t cell_bytes = 0;
     {
         for (int i = 0; i < n; ++i) { if (!streams[i] || streams[i]->ctx != ctx) return MSKF_ERR_INVALID; cell_bytes += sizeof(unsigned long long) * (size_t)streams[i]->fe.det_rows * streams[i]->fe.det_cols; }
-        if (cell_bytes > ctx->cell_arena.cap) { MSKF_HIPCHK(hipStreamSynchronize(st)); rc = ctx->cell_arena.ensure(cell_bytes); if (rc != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
+        if (cell_bytes > ctx->cell_arena.cap) { rc = ctx->cell_arena.ensure(cell_bytes); if (rc != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
         ++ctx->push_gen;
         size_t off = 0;
         for (int i = 0; i < n; ++i) { streams[i]->cell_off = off; streams[i]->push_gen = ctx->push_gen; off += sizeof(unsigned long long) * (size_t)streams[i]->fe.det_rows * streams[i]->fe.det_cols; }
@@ -657,12 +683,12 @@ extern "C" int mskf_fe_track_batch(mskf_ctx *ctx, int n, mskf_stream *const *str
 
 extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_fe_track_args *args) {
     if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
-    if (ctx->pend_trk.active) { mskf_set_error("a track batch of this context is still pending (call mskf_fe_track_batch_end)"); return MSKF_ERR_INVALID; }
-    if (ctx->pend_frame.active) { mskf_set_error("a device frame of this context is still pending (call mskf_fe_frame_batch_end)"); return MSKF_ERR_INVALID; }
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
+    if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     const auto t_h0 = std::chrono::steady_clock::now();
     hipStream_t st = ctx->stream;
-    int rc = ctx->desc[1].ensure(n);
+    rc = ctx->desc[1].ensure(n);
     if (rc != MSKF_OK) return rc;
     int max_pts = 0;
     size_t in_bytes = 0, out_bytes = 0;
@@ -683,11 +709,7 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         max_pts = std::max(max_pts, a.n);
     }
     if (max_pts <= 0) return MSKF_OK;      // nothing to track: no batch pending, _end is a no-op
-    if (in_bytes > ctx->trk_in.cap || out_bytes > ctx->trk_out.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        if ((rc = ctx->trk_in.ensure(in_bytes)) != MSKF_OK) return rc;
-        if ((rc = ctx->trk_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->trk_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->trk_out.ensure(out_bytes)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -703,7 +725,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         d.out0 = (mskf_point2f *)o; d.out1 = d.out0 + np; d.und0 = d.out1 + np; d.und1 = d.und0 + np;
         d.status = (uint8_t *)(d.und1 + np);
     }
+    DrainOnError drain{st};
     {
+        drain.armed = true;
         const MskfCopy cp[2] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
         if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
     }
@@ -713,9 +737,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     mskf_t_end(ctx, ts, 0);
     { const MskfCopy cp = {ctx->trk_out.h, ctx->trk_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
     MSKF_HIPCHK(hipGetLastError());
-    if ((rc = mskf_wait_event(ctx, &ctx->pend_trk.done, true)) != MSKF_OK) return rc;
-    ctx->pend_trk.active = true; ctx->pend_trk.n = n; ctx->pend_trk.args = args;
-    ctx->pend_trk.ts = ts;
+    ctx->pend_trk.n = n; ctx->pend_trk.args = args; ctx->pend_trk.ts = ts;
+    if ((rc = mskf_batch_arm(ctx, ctx->pend_trk)) != MSKF_OK) return rc;
+    drain.armed = false;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
 }
@@ -726,9 +750,8 @@ extern "C" int mskf_fe_track_batch_end(mskf_ctx *ctx) {
     if (!ctx) return MSKF_ERR_INVALID;
     if (!ctx->pend_trk.active) return MSKF_OK;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    ctx->pend_trk.active = false;      // also when the wait fails (timeout, stream error): the context must stay usable for a retry or a teardown
-    if ((rc = mskf_wait_event(ctx, &ctx->pend_trk.done, false)) != MSKF_OK) return rc;
+    const int rc = mskf_batch_finish(ctx, ctx->pend_trk);
+    if (rc != MSKF_OK) return rc;
     const int n = ctx->pend_trk.n;
     const mskf_fe_track_args *args = ctx->pend_trk.args;
     const std::vector<size_t> &out_off = ctx->pend_trk.out_off;
@@ -781,25 +804,36 @@ extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const
     mskf_stream::Book &K = s->book;
     if (!K.cap) { mskf_set_error("this stream keeps its books on the host (grid_min / grid_max above the device limit)"); return MSKF_ERR_UNSUPPORTED; }
     if (n > K.cap) return MSKF_ERR_CAPACITY;
-    MSKF_HIPCHK(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    MSKF_HIPCHK(hipStreamSynchronize(st));
+    mskf_ctx *ctx = s->ctx;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MSKF_HIPCHK(hipStreamSynchronize(st));      // (also: the previous set_grid's copy has read grid_in)
+    // the seven arrays through the context's pinned grid_in, one staging copy
     const FeGridArr &G = K.grid[K.parity];
+    const size_t n8 = (8 * (size_t)n + 63) & ~(size_t)63, n4 = (4 * (size_t)n + 63) & ~(size_t)63;
+    const size_t o_st = 5 * n8 + n4;
+    const int rc = ctx->grid_in.ensure(o_st + sizeof(FeBookState));
+    if (rc != MSKF_OK) return rc;
+    char *hs = ctx->grid_in.h;
     if (n) {
-        MSKF_HIPCHK(hipMemcpyAsync(G.id, id, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        MSKF_HIPCHK(hipMemcpyAsync(G.lifetime, lifetime, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-        MSKF_HIPCHK(hipMemcpyAsync(G.cam0, cam0, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        MSKF_HIPCHK(hipMemcpyAsync(G.cam1, cam1, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        MSKF_HIPCHK(hipMemcpyAsync(G.und0, und0, 8 * (size_t)n, hipMemcpyHostToDevice, st));
-        MSKF_HIPCHK(hipMemcpyAsync(G.und1, und1, 8 * (size_t)n, hipMemcpyHostToDevice, st));
+        std::memcpy(hs, id, 8 * (size_t)n);
+        std::memcpy(hs + n8, lifetime, 4 * (size_t)n);
+        std::memcpy(hs + n8 + n4, cam0, 8 * (size_t)n);
+        std::memcpy(hs + 2 * n8 + n4, cam1, 8 * (size_t)n);
+        std::memcpy(hs + 3 * n8 + n4, und0, 8 * (size_t)n);
+        std::memcpy(hs + 4 * n8 + n4, und1, 8 * (size_t)n);
     }
-    FeBookState h;
+    FeBookState &h = *(FeBookState *)(hs + o_st);
     std::memset(&h, 0, sizeof(h));
     h.next_id = next_feature_id; h.n_prev = n; h.n_curr = n;
     h.ransac_draws = ransac_draws;
     if (tracking_counters) { h.after_tracking = tracking_counters[0]; h.after_matching = tracking_counters[1]; h.after_ransac = tracking_counters[2]; }
-    MSKF_HIPCHK(hipMemcpyAsync(K.st, &h, sizeof(h), hipMemcpyHostToDevice, st));
+    const MskfCopy cp[7] = {{G.id, hs, 8 * (size_t)n}, {G.lifetime, hs + n8, 4 * (size_t)n}, {G.cam0, hs + n8 + n4, 8 * (size_t)n},
+                            {G.cam1, hs + 2 * n8 + n4, 8 * (size_t)n}, {G.und0, hs + 3 * n8 + n4, 8 * (size_t)n},
+                            {G.und1, hs + 4 * n8 + n4, 8 * (size_t)n}, {K.st, hs + o_st, sizeof(FeBookState)}};
+    const int crc = mskf_copy_async(ctx, cp, 7);
     MSKF_HIPCHK(hipStreamSynchronize(st));
+    if (crc != MSKF_OK) return crc;
     K.n_prev = n; K.n_cand_last = -1; K.grid_set = true;
     return MSKF_OK;
 }
@@ -807,7 +841,8 @@ extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const
 extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1,
                                          int on_device, mskf_fe_frame_args *args) {
     if (!ctx || n <= 0 || !streams || !cam0 || !cam1 || !args) return MSKF_ERR_INVALID;
-    if (ctx->pend_frame.active || ctx->pend_trk.active) { mskf_set_error("a batch of this context is still pending"); return MSKF_ERR_INVALID; }
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
+    if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     for (int i = 0; i < n; ++i) {
@@ -819,7 +854,8 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         if (a.capacity < s->book.cap || !a.id || !a.lifetime || !a.cam0 || !a.cam1 || !a.und0 || !a.und1) return MSKF_ERR_INVALID;
     }
     const auto t_h0 = std::chrono::steady_clock::now();
-    int rc = push_batch(ctx, n, streams, cam0, cam1, on_device, false);
+    DrainOnError drain{st, true};        // (push_batch enqueues the images, the pyramids and the detector)
+    rc = push_batch(ctx, n, streams, cam0, cam1, on_device, false);
     if (rc != MSKF_OK) return rc;
     if ((rc = ctx->desc[1].ensure(n)) != MSKF_OK || (rc = ctx->desc[2].ensure(n)) != MSKF_OK || (rc = ctx->book_desc.ensure(n)) != MSKF_OK) return rc;
     std::vector<size_t> &out_off = ctx->pend_frame.out_off;
@@ -837,10 +873,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         const int est = K.n_cand_last < 0 ? K.cand_cap / 2 : std::min(K.cand_cap, K.n_cand_last + K.n_cand_last / 2 + 32);
         max_cand_est = std::max(max_cand_est, est);
     }
-    if (out_bytes > ctx->book_out.cap) {
-        MSKF_HIPCHK(hipStreamSynchronize(st));
-        if ((rc = ctx->book_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    }
+    if ((rc = ctx->book_out.ensure(out_bytes)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         mskf_stream::Book &K = s->book;
@@ -909,7 +942,10 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     mskf_t_end(ctx, tb, n);
     { const MskfCopy cp = {ctx->book_out.h, ctx->book_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
     MSKF_HIPCHK(hipGetLastError());
-    if ((rc = mskf_wait_event(ctx, &ctx->pend_frame.done, true)) != MSKF_OK) return rc;
+    ctx->pend_frame.n = n; ctx->pend_frame.streams = streams; ctx->pend_frame.args = args;
+    ctx->pend_frame.ts1 = ts1; ctx->pend_frame.ts2 = ts2;
+    if ((rc = mskf_batch_arm(ctx, ctx->pend_frame)) != MSKF_OK) return rc;
+    drain.armed = false;
     // state rotation (:192-200): the grid just built is the next frame's previous grid, curr cam0 becomes prev cam0
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
@@ -917,8 +953,6 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         std::swap(s->i_prev0, s->i_curr0);
         s->has_curr = false;
     }
-    ctx->pend_frame.active = true; ctx->pend_frame.n = n; ctx->pend_frame.streams = streams; ctx->pend_frame.args = args;
-    ctx->pend_frame.ts1 = ts1; ctx->pend_frame.ts2 = ts2;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
 }
@@ -928,9 +962,8 @@ extern "C" int mskf_fe_frame_batch_end(mskf_ctx *ctx) {
     mskf_ctx::PendingFrame &F = ctx->pend_frame;
     if (!F.active) return MSKF_OK;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
-    F.active = false;
-    int rc;
-    if ((rc = mskf_wait_event(ctx, &F.done, false)) != MSKF_OK) return rc;
+    const int rc = mskf_batch_finish(ctx, F);
+    if (rc != MSKF_OK) return rc;
     const auto t_h1 = std::chrono::steady_clock::now();
     long long tracks1 = 0, tracks2 = 0;
     bool overflow = false;

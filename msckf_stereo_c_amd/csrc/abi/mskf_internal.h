@@ -38,9 +38,16 @@ struct PinnedDev {  // a pinned host array with a device twin
     T *h = nullptr, *d = nullptr;
     size_t cap = 0;
     std::vector<std::pair<T *, T *>> retired;      // outgrown buffers, freed with the owner
+    // Optional reuse fence, for an arena whose host side no pending batch protects (pred_arena): recorded behind the copy
+    // that reads h, synchronised by the next writer before it writes h.
+    hipEvent_t fence = nullptr;
+    bool fence_pending = false;
     // Growth NEVER frees: hipFree / hipHostFree wait for every stream of the device, and a context that outgrew a staging
     // buffer in the middle of a run stood still until all the other groups' queues were idle (0.3 s in the round-3 bench).
     // The outgrown pair is retired and freed by release(); with doubling that is at most as much again as the final size.
+    // Growth therefore needs no stream synchronisation either: work in flight keeps reading and writing the retired pair,
+    // and nothing in flight knows the new one.  (What keeps the host from overwriting h under an in-flight reader is the
+    // fence or the pending batch that owns the arena, not growth.)
     int ensure(size_t n) {
         if (n <= cap) return MSKF_OK;
         if (h || d) retired.push_back({h, d});
@@ -51,13 +58,58 @@ struct PinnedDev {  // a pinned host array with a device twin
         cap = c;
         return MSKF_OK;
     }
+    int fence_wait() {            // before writing h
+        if (!fence_pending) return MSKF_OK;
+        MSKF_HIPCHK(hipEventSynchronize(fence));
+        fence_pending = false;
+        return MSKF_OK;
+    }
+    int fence_record(hipStream_t st) {   // behind the copy that reads h
+        if (!fence) MSKF_HIPCHK(hipEventCreateWithFlags(&fence, hipEventDisableTiming));
+        MSKF_HIPCHK(hipEventRecord(fence, st));
+        fence_pending = true;
+        return MSKF_OK;
+    }
     void release() {
         if (h) (void)hipHostFree(h);
         if (d) (void)hipFree(d);
         for (auto &r : retired) { if (r.first) (void)hipHostFree(r.first); if (r.second) (void)hipFree(r.second); }
         retired.clear();
         h = d = nullptr; cap = 0;
+        if (fence) (void)hipEventDestroy(fence);
+        fence = nullptr; fence_pending = false;
     }
+};
+
+// A batch between its _begin and its _end (one of each kind per context).  Each kind keeps its own fields around it.
+//   mskf_batch_arm:    record the completion mark behind everything the _begin enqueued, then set `active`.
+//   mskf_batch_finish: wait for the mark; `active` is cleared only once the wait succeeded.  A failed _end (timeout, stream
+//                      error) leaves the batch pending, since its kernels may still be using the arenas it owns: _end may
+//                      be called again, a _begin that needs those arenas is refused, mskf_ctx_destroy drains the stream.
+//                      Timing is collected by the caller (the LK units are known only from the unpacked results).
+// A _begin that fails after it has enqueued anything (copy, memset, stream-ordered allocation, launch) synchronises the
+// context's stream before it returns the error (DrainOnError): no staged work outlives it, and nothing is left pending.
+struct PendingBatch {
+    bool active = false;
+    hipEvent_t done = nullptr;        // completion-mark slot (mskf_wait_event)
+};
+int mskf_batch_arm(mskf_ctx *c, PendingBatch &b);
+int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
+
+// Which pending batch owns which arenas of the context:
+//   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
+//   a pending update owns ekf_desc, upd_in and upd_out;
+//   a pending position-variance read-out owns pred_arena (its kernel reads descriptors from and writes results into the host side).
+// Every _begin and every batch call that writes an arena refuses while the owner is pending: MSKF_ERR_INVALID, and the
+// error message names the pending batch.
+enum MskfArenas { MSKF_ARENAS_FE, MSKF_ARENAS_UPDATE, MSKF_ARENAS_PRED };
+int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which);
+
+// Set `armed` once a _begin has enqueued work; a return while it is still set synchronises the context's stream.
+struct DrainOnError {
+    hipStream_t st;
+    bool armed = false;
+    ~DrainOnError() { if (armed) (void)hipStreamSynchronize(st); }     // (its result is ignored: the original error is returned)
 };
 
 struct TimingSlot { hipEvent_t a, b; int kind; long long units; };
@@ -78,10 +130,10 @@ struct mskf_ctx {
     PinnedDev<FeStreamDev> desc[3];   // 0: push/detect, 1: track (first track call of a device frame), 2: second track call of a device frame
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid
-    struct PendingFrame {
-        bool active = false; int n = 0; mskf_stream *const *streams = nullptr; struct mskf_fe_frame_args *args = nullptr;
+    PinnedDev<char> grid_in;          // staging of mskf_fe_set_grid (synchronous: no batch owns it)
+    struct PendingFrame : PendingBatch {
+        int n = 0; mskf_stream *const *streams = nullptr; struct mskf_fe_frame_args *args = nullptr;
         std::vector<size_t> out_off; int ts1 = -1, ts2 = -1;
-        hipEvent_t done = nullptr;
     } pend_frame;
     hipEvent_t wait_ev = nullptr;     // mark of mskf_wait
     bool wait_block = false;
@@ -96,23 +148,19 @@ struct mskf_ctx {
     PinnedDev<Pyr3Job> jobs;
     PinnedDev<EkfStreamDev> ekf_desc;
     PinnedDev<char> upd_in, upd_out;     // inputs / results of every stream of an update batch (one copy each way)
-    PinnedDev<char> pred_arena;          // descriptors + IMU steps + J of mskf_ekf_predict_batch
-    hipEvent_t pred_done = nullptr;
-    bool pred_pending = false;
+    PinnedDev<char> pred_arena;          // descriptors + Phi/Q or IMU steps + J of a prediction, clone removal, position-variance read-out (fenced)
     std::vector<mskf_stream *> streams;
-    // a batch between its *_begin and *_end call (one of each kind per context)
-    struct PendingTrack {
-        bool active = false; int n = 0; const mskf_fe_track_args *args = nullptr;
+    // batches between their *_begin and *_end call (PendingBatch)
+    struct PendingTrack : PendingBatch {
+        int n = 0; const mskf_fe_track_args *args = nullptr;
         std::vector<size_t> out_off; int ts = -1;
-        hipEvent_t done = nullptr;
     } pend_trk;
-    struct PendingUpdate {
-        bool active = false, launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
+    struct PendingUpdate : PendingBatch {
+        bool launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
         std::vector<size_t> lay;   // per stream: o_dx, o_gamma, o_rows, o_status, o_pos
         std::vector<int> cnt_cls;              // scratch: features per size class of the feature kernel and stream, [3][n]
-        hipEvent_t done = nullptr;
     } pend_upd;
-    struct PendingPosVar { bool active = false; int n = 0; double *out = nullptr; size_t desc_bytes = 0; hipEvent_t done = nullptr; } pend_pv;
+    struct PendingPosVar : PendingBatch { int n = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_pv;
 };
 // Completion marks.  mskf_wait_event(c, slot, true) marks the point the context's stream has reached, (.., false) waits
 // for that mark.  Spinning mode (default): the mark is a sequence number written into pinned host memory by a stream
@@ -120,8 +168,10 @@ struct mskf_ctx {
 // spinning in several threads at once slows every other thread's launches down, measured -25 %).  MSKF_WAIT=block: a
 // blocking-sync HIP event, the thread is parked.  `slot` identifies the mark (one per kind of pending batch).
 // Staging copies between the library's own pinned host arenas and device memory, enqueued on the context's stream as ONE kernel
-// launch for up to MSKF_COPY_SEGS segments (fe_kernels.hip: why not hipMemcpyAsync); MSKF_SDMA_COPIES=1 goes back to
-// hipMemcpyAsync (one call per segment).  Both ends must be addressable from a kernel: device memory or hipHostMalloc'ed memory.
+// launch for up to MSKF_COPY_SEGS segments (fe_kernels.hip: why not hipMemcpyAsync).  Both ends must be addressable from a
+// kernel: device memory or hipHostMalloc'ed memory.  Every copy from or into an arena of the library goes this way;
+// hipMemcpy* in the C ABI copies only memory the caller owns (image pushes, mskf_ekf_reset / set_cov / get_cov,
+// mskf_ekf_debug_read, mskf_fe_get_level) and the chi-square table of mskf_ekf_stream_init.
 struct MskfCopy { void *dst; const void *src; size_t bytes; };
 int mskf_copy_async(mskf_ctx *c, const MskfCopy *segs, int n);
 int mskf_wait_event(mskf_ctx *c, hipEvent_t *ev_slot, bool record);

@@ -85,9 +85,4 @@ struct EkfStreamState {       // host-side bookkeeping of the device buffers of 
     double *P = nullptr, *Hs = nullptr, *rs = nullptr, *T = nullptr, *S = nullptr, *W = nullptr, *gate_S = nullptr;
     int *act = nullptr;       // ld ints: active column list of the current update
     double *chi2 = nullptr;
-    // per-update staging: one pinned+device arena, laid out by the host
-    char *h_arena = nullptr, *d_arena = nullptr;
-    size_t arena_bytes = 0;
-    char *h_out = nullptr, *d_out = nullptr;   // results: delta_x, status, gamma, rows, positions
-    size_t out_bytes = 0;
 };

@@ -1,7 +1,7 @@
 // ekf_kernels.hip — hand-written gfx950 kernels of the MSCKF measurement update.
 //
-//  k_ekf_propagate      : covariance part of processModel        (msckf_vio.cpp:458-469)
-//  k_ekf_augment        : covariance part of stateAugmentation   (:564-582)
+//  k_ekf_propagate      : covariance part of processModel        (msckf_vio.cpp:458-469), fused with the one of
+//                         stateAugmentation (:564-582)
 //  k_ekf_remove_clone   : clone row/column deletion              (:1161-1181)
 //  k_ekf_feature_blocks : Feature::initializePosition (feature.hpp:289-450), measurementJacobian
 //                         (:610-677), featureJacobian null-space projection (:679-775), gatingTest (:909-935)
@@ -117,7 +117,7 @@ __device__ __forceinline__ void build_phi_q(const mskf_imu_step &st, const doubl
 // frame's launch chain, 360 us in the busy device for 10 us of work), P_II <- sym(Phi P_II Phi^T + Q) (in LDS); the clone cross terms are propagated once with the
 // composed transition  P_IC <- (Phi_n ... Phi_1) P_IC  (one pass over P instead of one per IMU sample),
 // P_CI <- P_IC^T.  With S.J set the state augmentation (rows/cols [d, d+6) = J [P_II P_IC], corner
-// sym(J P_II J^T)) is fused into the same pass.
+// sym(J P_II J^T)) is fused into the same pass; with n_steps = 0 it is the augmentation alone (mskf_ekf_augment).
 __global__ __launch_bounds__(WG) void k_ekf_propagate(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_steps <= 0 && !S.J) return;
@@ -195,37 +195,6 @@ __global__ __launch_bounds__(WG) void k_ekf_propagate(const EkfStreamDev *stream
             for (int k = 0; k < N; ++k) { s += sC[r * N + k] * sJ[c * N + k]; st += sC[c * N + k] * sJ[r * N + k]; }
             P[(size_t)(d + r) * ld + (d + c)] = (s + st) / 2.0;
         }
-    }
-}
-
-// ------------------------------------------------------------------------------------ augment
-// rows/cols [d, d+6): [J P11, J P12], corner sym(J P11 J^T)
-__global__ __launch_bounds__(WG) void k_ekf_augment(const EkfStreamDev *streams) {
-    const EkfStreamDev &S = streams[blockIdx.y];
-    if (!S.J) return;
-    double *P = S.P;
-    const int d = S.d, ld = S.ld, N = EKF_IMU_DIM;  // d = dimension BEFORE augmentation
-    __shared__ double sJ[6 * N], sC[6 * N];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 6 * N; i += WG) sJ[i] = S.J[i];
-    __syncthreads();
-    for (int c = tid; c < d; c += WG) {
-        double col[N];
-        for (int k = 0; k < N; ++k) col[k] = P[(size_t)k * ld + c];
-        for (int r = 0; r < 6; ++r) {
-            double s = 0;
-            for (int k = 0; k < N; ++k) s += sJ[r * N + k] * col[k];
-            P[(size_t)(d + r) * ld + c] = s;
-            P[(size_t)c * ld + (d + r)] = s;
-            if (c < N) sC[r * N + c] = s;
-        }
-    }
-    __syncthreads();
-    if (tid < 36) {
-        const int r = tid / 6, c = tid % 6;
-        double s = 0, st = 0;
-        for (int k = 0; k < N; ++k) { s += sC[r * N + k] * sJ[c * N + k]; st += sC[c * N + k] * sJ[r * N + k]; }
-        P[(size_t)(d + r) * ld + (d + c)] = (s + st) / 2.0;
     }
 }
 
@@ -1090,7 +1059,6 @@ __global__ __launch_bounds__(64) void k_ekf_pair_blocks(const EkfStreamDev *stre
 // ------------------------------------------------------------------------------------ launchers
 extern "C" {
 void ekf_launch_propagate(const EkfStreamDev *d, int n, hipStream_t st) { hipLaunchKernelGGL(k_ekf_propagate, dim3(1, n), dim3(WG), 0, st, d); }
-void ekf_launch_augment(const EkfStreamDev *d, int n, hipStream_t st) { hipLaunchKernelGGL(k_ekf_augment, dim3(1, n), dim3(WG), 0, st, d); }
 void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_ekf_remove_clone, dim3(32, n), dim3(WG), 0, st, d);
 }

@@ -158,7 +158,9 @@ def test_predict_batch(gpu_ctx, oracle):
     """mskf_ekf_predict_batch over six streams of different sizes (augmentation only, propagation only, both, neither):
     each stream matches the reference at the bars of the realistic-P test, the same stream alone in a batch of one bit for
     bit, and mskf_ekf_propagate_imu followed by mskf_ekf_augment bit for bit (the header calls them equivalent; they form
-    the same sums in the same order).  Observed on MI355X: P_II <= 9.3e-16, P_IC <= 2.5e-16, new clone rows <= 3.6e-16."""
+    the same sums in the same order).  Observed on MI355X: P_II <= 9.3e-16, P_IC <= 2.5e-16, new clone rows <= 3.6e-16.
+    Then the three single-stream calls on a fresh context, each staging more bytes than every call before it there (the
+    context's staging arena grows between them), against the reference at the same bars."""
     inputs = _batch_inputs()
 
     def fresh():
@@ -197,6 +199,26 @@ def test_predict_batch(gpu_ctx, oracle):
             continue
         err = _check_predicted(P, P0, steps, J, "stream %d" % i)
         print("stream %d d %d steps %d J %s: %s" % (i, P0.shape[0], len(steps), J is not None, {k: "%.1e" % v for k, v in err.items()}))
+    ctx = capi.Context(0)
+    try:
+        rng = np.random.default_rng(78)
+        s = _stream(ctx, oracle, 40)
+        P0 = R.spd(N + 6 * 30, rng)
+        s.ekf_set_cov(P0)
+        J = R.augment_jacobian(rng)
+        steps = R.imu_steps(40, 0.005, gyro=GYRO["fast"], q0=ATT["general"], seed=78, jitter=0.05)
+        s.ekf_augment(J)                                                   # descriptor + J: 640 bytes
+        P1 = s.ekf_get_cov()
+        _check_predicted(P1, P0, [], J, "fresh context, augment")
+        s.ekf_propagate_imu(steps)                                         # + 40 IMU steps: 12 KiB
+        P2 = s.ekf_get_cov()
+        _check_predicted(P2, P1, steps, None, "fresh context, propagate_imu")
+        _, Phis, Qs = R.propagate(P2, steps[:4], _qc())
+        s.ekf_propagate(np.array(Phis, dtype=np.float64), np.array(Qs, dtype=np.float64))     # + 4 (Phi, Q) pairs: 28 KiB
+        _check_predicted(s.ekf_get_cov(), P2, steps[:4], None, "fresh context, propagate")
+        s.close()
+    finally:
+        ctx.close()
 
 
 def test_predict_batch_capacity_changes_nothing(gpu_ctx, oracle):
@@ -416,13 +438,15 @@ def test_pos_var_out_of_batches(gpu_ctx, oracle):
 
 def test_pending_pos_var_read_out_blocks_predict_and_removal(gpu_ctx, oracle):
     """While a mskf_ekf_get_pos_var_batch_begin is pending (its kernel reads descriptors from the arena they would reuse),
-    mskf_ekf_predict_batch and mskf_ekf_remove_clones_batch refuse and change nothing; after _end both work again."""
+    mskf_ekf_predict_batch, mskf_ekf_remove_clones_batch and the single-stream mskf_ekf_propagate, mskf_ekf_propagate_imu and
+    mskf_ekf_augment refuse and change nothing; after _end all of them work again."""
     rng = np.random.default_rng(41)
     s = _stream(gpu_ctx, oracle, 8)
     P0 = R.spd(N + 6 * 4, rng)
     s.ekf_set_cov(P0)
     steps = R.imu_steps(3, 0.005, gyro=GYRO["fast"], q0=ATT["general"])
     J = R.augment_jacobian(rng)
+    Phis, Qs = (np.array(x, dtype=np.float64) for x in R.propagate(P0, steps, _qc())[1:])
     out = gpu_ctx.ekf_pos_var_batch_begin([s])
     try:
         with pytest.raises(capi.MskfError) as e:
@@ -430,6 +454,15 @@ def test_pending_pos_var_read_out_blocks_predict_and_removal(gpu_ctx, oracle):
         assert e.value.code == ERR_INVALID
         with pytest.raises(capi.MskfError) as e:
             gpu_ctx.ekf_remove_clones_batch([s], [(0, 1)])
+        assert e.value.code == ERR_INVALID
+        with pytest.raises(capi.MskfError) as e:
+            s.ekf_propagate(Phis, Qs)
+        assert e.value.code == ERR_INVALID
+        with pytest.raises(capi.MskfError) as e:
+            s.ekf_propagate_imu(steps)
+        assert e.value.code == ERR_INVALID
+        with pytest.raises(capi.MskfError) as e:
+            s.ekf_augment(J)
         assert e.value.code == ERR_INVALID
     finally:
         gpu_ctx.ekf_pos_var_batch_end()
@@ -439,6 +472,15 @@ def test_pending_pos_var_read_out_blocks_predict_and_removal(gpu_ctx, oracle):
     _check_predicted(s.ekf_get_cov(), P0, steps, J)
     gpu_ctx.ekf_remove_clones_batch([s], [(0, 1)])
     assert s.ekf_dim() == P0.shape[0] + 6 - 12
+    P1 = s.ekf_get_cov()
+    s.ekf_propagate(Phis, Qs)
+    P2 = s.ekf_get_cov()
+    _check_predicted(P2, P1, steps, None)
+    s.ekf_propagate_imu(steps)
+    P3 = s.ekf_get_cov()
+    _check_predicted(P3, P2, steps, None)
+    s.ekf_augment(J)
+    _check_predicted(s.ekf_get_cov(), P3, [], J)
     s.close()
 
 

@@ -32,8 +32,6 @@ if [ "$WHAT" = lines ]; then
   echo "2 ranks done"
   timeout -k 10 300 python bench.py --full --no-cpu --steps 20 --warmup 5 --host-images > "$OUT/bench_host_images.json" 2>> "$OUT/log.txt" || exit 4
   timeout -k 10 300 python bench.py --full --config c5 --streams 8 --groups 1 --no-cpu --steps 20 --warmup 5 > "$OUT/bench_c5_8streams.json" 2>> "$OUT/log.txt" || exit 6
-  # the staging copies through hipMemcpyAsync (SDMA) as until the middle of round 4: may stall for a minute, never fails the collection
-  MSKF_SDMA_COPIES=1 MSKF_WAIT_TIMEOUT_S=100 timeout -k 10 150 python bench.py --full --no-cpu --steps 20 --warmup 5 > "$OUT/bench_sdma_copies.json" 2>> "$OUT/log.txt" || echo "sdma-copies run did not finish"
   echo "all lines done"
 else
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python bench.py --full --no-cpu --steps 20 --warmup 5 --gram-steps 0 > "$OUT/bench_under_rocprof.json" 2>> "$OUT/log.txt" || exit 2
