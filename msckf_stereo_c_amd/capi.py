@@ -118,10 +118,15 @@ def _imu_steps(steps):
 
 
 class Context:
-    def __init__(self, device=0):
+    def __init__(self, device=0, shared_with=None):
+        """shared_with: a parent Context whose HIP stream this one enqueues on (mskf_ctx_create_shared; close it first)."""
         self.L = lib()
         self.h = C.c_void_p()
-        _chk(self.L.mskf_ctx_create(device, C.byref(self.h)))
+        if shared_with is None:
+            _chk(self.L.mskf_ctx_create(device, C.byref(self.h)))
+        else:
+            self.L.mskf_ctx_create_shared.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+            _chk(self.L.mskf_ctx_create_shared(shared_with.h, C.byref(self.h)))
         self.streams = []
 
     def close(self):

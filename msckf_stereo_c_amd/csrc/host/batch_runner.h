@@ -1,9 +1,10 @@
 // batch_runner.h — steps many independent VIO streams (cg::System objects) in lockstep so that every
 // device phase of a frame is ONE batched C-ABI call (mskf_fe_push_stereo_batch, mskf_fe_track_batch,
 // mskf_ekf_update_batch, ...).  Streams are independent units: no data crosses streams.
-// A BatchGroup owns one mskf_ctx (one HIP stream); a MultiRunner runs several groups on their own host
-// threads so the host bookkeeping of one group overlaps the kernels of another.
+// A BatchGroup owns two mskf_ctx (front-end and filter, one HIP stream each); a MultiRunner runs several groups, in lockstep
+// on their own host threads or as one pipelined run, so the host bookkeeping of one group overlaps the kernels of another.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
@@ -28,29 +29,24 @@ struct StreamSequence {   // a looping pre-rendered stereo sequence + IMU sample
     int imu_cursor_ekf = 0;   // next sample for the filter stage of the pipeline
 };
 
-// A measurement window inside one continuous pipelined run of all groups (bench.py).  The groups' hardware queues are not
-// served evenly (some groups are a quarter of the run ahead of others), so the window is defined on the WORK, not on any one
-// group's frames: it opens when the groups together have completed n_groups x W frames (front-end and filter) and closes
-// when they have completed n_groups x (W + K) — exactly K steps' worth of stream-frames are finished inside it, with every
-// group busy from before it opens until after it closes (a group runs at least W + K frames and then keeps stepping until
-// the window is closed; frames started before it closes are finished but not counted).  Each stage opens its accounting
-// gates (kernel timing of its context, host bookkeeping slots, phase times) at its first frame boundary inside the window
-// and closes them at the first one after it.
+// The measurement window of one continuous pipelined run of all batches (MultiRunner::run_balanced).  The device's hardware
+// queues are not served evenly, so the window is defined on the WORK, not on any one batch's frames: it opens when the batches
+// together have completed n_groups x W frames (front-end and filter) and closes when they have completed n_groups x (W + K) —
+// exactly K steps' worth of stream-frames are finished inside it.  Every batch runs at least W + K frames and keeps stepping
+// (at most max_extra frames more) until the window is closed; frames started before it closes are finished but not counted.
+// Each worker opens its accounting gates (kernel timing of its context, host bookkeeping slots, phase times) at its first
+// frame boundary inside the window and closes them at the first one after it.
 struct TimedShared {
     std::atomic<long> completed{0};
     long target_open = 0, target_close = 0;
     std::atomic<int> phase{0};               // 0 warm-up, 1 window open, 2 closed
     double t_open = 0, t_close = 0;          // steady_clock seconds
 };
-struct TimedWindow {
-    TimedShared *shared = nullptr;
-    int mark_end = 0;                        // absolute frame index: the sentinel snapshot is taken after frame mark_end - 1 of this group
-    int max_extra = 0;
-    // results
-    double t_fe_begin = 0, t_fe_end = 0, t_ekf_begin = 0, t_ekf_end = 0;   // when the stages opened / closed their gates
-    int fe_frames = 0, ekf_frames = 0;       // frames each stage started between its open and close
-    int frames_done = 0;                     // frames the group processed in this run
-    int frames_at_close = 0;                 // ... of which completed (both stages) when the shared window closed (balanced runner)
+struct TimedWindow {                         // index g: worker g (open / close times, frames started) and batch g (frames completed)
+    double t_fe_begin = 0, t_fe_end = 0, t_ekf_begin = 0, t_ekf_end = 0;   // when the workers opened / closed their gates
+    int fe_frames = 0, ekf_frames = 0;       // frames each worker started between its open and close
+    int frames_done = 0;                     // frames the batch completed in this run
+    int frames_at_close = 0;                 // ... of which completed (both stages) when the shared window closed
 };
 
 struct FrameBatch {           // what the front-end stage hands to the filter stage: one frame of every stream
@@ -83,8 +79,8 @@ class ForkJoin {
 class BatchGroup {
   public:
     // host_threads / ekf_host_threads: threads that share the per-stream host phases of the front-end / filter stage (0 = as
-    // host_threads); halves = 2: two staggered half-batches per stage on contexts sharing the stage's HIP stream
-    BatchGroup(int device, int n, const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ekf_cfg &ekf, int host_threads = 1, int ekf_host_threads = 0, int halves = 1);
+    // host_threads)
+    BatchGroup(int device, int n, const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ekf_cfg &ekf, int host_threads = 1, int ekf_host_threads = 0);
     ~BatchGroup();
     bool ok() const { return ok_; }
     int size() const { return (int)systems_.size(); }
@@ -94,10 +90,7 @@ class BatchGroup {
     int step(const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, const double *t, bool is_draw);
     // frames [first, first+n) of the attached sequences, IMU fed in the reference harness order (Q10)
     int run(int first, int n);
-    // same frames as a two-stage pipeline: a front-end thread (context ctx()) and a filter thread (context
-    // ekf_ctx()); the front-end never reads filter state, so the results are identical to run()
-    int run_pipelined(int first, int n, TimedWindow *win = nullptr);
-    // ---- the two stages of a frame as separate calls on BORROWED contexts, for the balanced runner (MultiRunner::run_balanced):
+    // ---- the two stages of a frame as separate calls, for the pipelined runner (MultiRunner::run_balanced):
     // a batch (this object's streams and host state) is handed to whichever worker (a context + a host thread) is free.
     // fe_stage: IMU feed + front-end of frame k + the hand-off snapshot; ekf_stage: IMU feed + filter of a snapshot.  `acc`
     // receives the phase times (the worker's accounting, PH_*).  A stage of a batch is run by one worker at a time.
@@ -109,11 +102,9 @@ class BatchGroup {
     void snapshot_ekf_mark();
     std::deque<std::unique_ptr<FrameBatch>> handoff;          // balanced runner: frames through the front-end, waiting for the filter
     std::vector<std::unique_ptr<FrameBatch>> handoff_pool;
-    // device contexts: the streams of a group are driven as up to two half-batches, each with its own staging
-    // context; the halves of a stage share one HIP stream (mskf_ctx_create_shared), so a group still uses two queues
-    int n_halves() const { return (int)half_.size(); }
-    mskf_ctx *ctx(int h = 0) const { return half_[h].ctx; }
-    mskf_ctx *ekf_ctx(int h = 0) const { return half_[h].ctx_ekf; }
+    // the contexts the front-end / filter stage currently runs on (the group's own ones outside a pipelined run)
+    mskf_ctx *ctx() const { return ctx_; }
+    mskf_ctx *ekf_ctx() const { return ekf_ctx_; }
     std::vector<StreamSequence> seq;
     const std::string &error() const { return error_; }
     // phases of the front-end thread: PH_IMU .. PH_FE_QWAIT (without PH_EKF_*); of the filter thread: PH_EKF_QWAIT, PH_IMU_EKF, PH_EKF_A .. PH_POSVAR
@@ -121,8 +112,8 @@ class BatchGroup {
            PH_HANDOFF, PH_FE_QWAIT, PH_EKF_QWAIT, PH_IMU_EKF, PH_COUNT };
     double phase_s[PH_COUNT] = {0};   // wall seconds per phase of step() (host bookkeeping vs device calls)
     double window_phase_s[PH_COUNT] = {0};   // the same inside the last TimedWindow (each stage between its own marks)
-    // what local stream 0 had computed when the stages closed the window (the sentinel of bench.py): front-end state after
-    // frame mark_end - 1, filter state after the same frame
+    // what local stream 0 had computed at the end of its batch's own frames of a pipelined run (the sentinel of bench.py):
+    // front-end state after the last of them, filter state after the same frame
     struct MarkDump { std::vector<unsigned long long> ids; std::vector<int> life; std::vector<Point2f> c0, c1; double imu[28] = {0}; bool fe_valid = false, ekf_valid = false; } mark_dump;
     void set_gates(bool on);          // accounting gates of both contexts (call while no stage is running)
 
@@ -130,22 +121,8 @@ class BatchGroup {
     int step_fe(const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, const double *t, bool is_draw);
     int step_ekf(const FrameBatch *fb);
     int feed_imu(int k, bool to_fe, bool to_ekf);
-    // A half-batch: streams [i0, i0 + n).  While the device works on one half the host thread prepares or digests the
-    // other (the *_begin / *_end entry points of the C-ABI), so host bookkeeping and device time overlap inside a thread.
-    struct Half {
-        mskf_ctx *ctx = nullptr, *ctx_ekf = nullptr;
-        int i0 = 0, n = 0;
-        std::vector<mskf_stream *> sub_s;              // streams with a non-empty update, and their args (valid until *_end)
-        std::vector<mskf_ekf_update_args> sub_a;
-        std::vector<int> sub_i;
-        std::vector<int32_t> ns, rm;
-        std::vector<const mskf_imu_step *> sp;
-        std::vector<const double *> jp;
-        std::vector<double> pv;
-        bool any = false, upd_pending = false, pv_pending = false;
-    };
-    std::vector<Half> half_;
-    mskf_ctx *home_fe_ = nullptr, *home_ekf_ = nullptr;       // the contexts this group created (half_[0] may point at borrowed ones)
+    mskf_ctx *ctx_ = nullptr, *ekf_ctx_ = nullptr;             // current contexts of the two stages (borrowed in a pipelined run)
+    mskf_ctx *home_fe_ = nullptr, *home_ekf_ = nullptr;       // the contexts this group created
     double *acc_fe_ = nullptr, *acc_ekf_ = nullptr;           // where step_fe / step_ekf account their phases (default: phase_s)
     mskf_point *ekf_tail_ = nullptr;                          // the filter stage's last enqueued work (clone removal is not waited for)
     mskf_ctx *ekf_tail_ctx_ = nullptr;
@@ -156,16 +133,22 @@ class BatchGroup {
     std::vector<mskf_fe_track_args> a1_, a2_;
     std::vector<mskf_fe_frame_args> fa_;
     std::vector<mskf_ekf_update_args> u_;
+    std::vector<mskf_stream *> upd_s_;                        // streams with a non-empty update, and their args (valid until *_end)
+    std::vector<mskf_ekf_update_args> upd_a_;
+    std::vector<int32_t> pred_ns_, rm_;                       // prediction steps and clone removals per stream
+    std::vector<const mskf_imu_step *> pred_sp_;
+    std::vector<const double *> pred_jp_;
+    std::vector<double> pv_;                                  // position variances fetched on their own (3 per stream)
     std::vector<const uint8_t *> p0_, p1_;
     std::vector<double> t_;
     std::unique_ptr<ForkJoin> pool_, pool_ekf_;
-    void par(int n, const std::function<void(int)> &fn) { if (pool_) pool_->run(n, fn); else for (int i = 0; i < n; ++i) fn(i); }
+    static void par(ForkJoin *pool, int n, const std::function<void(int)> &fn) { if (pool) pool->run(n, fn); else for (int i = 0; i < n; ++i) fn(i); }
 };
 
 class MultiRunner {
   public:
     MultiRunner(int device, int n_groups, int per_group, const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ekf_cfg &ekf,
-                int host_threads = 1, int ekf_host_threads = 0, int halves = 1);
+                int host_threads = 1, int ekf_host_threads = 0);
     ~MultiRunner();
     bool ok() const;
     int n_streams() const { return n_groups_ * per_group_; }
@@ -176,13 +159,16 @@ class MultiRunner {
     StreamSequence &sequence(int stream) { int l; BatchGroup &g = group_of(stream, l); return g.seq[l]; }
     void imu(int stream, const mskf_imu_sample &s) { int l; BatchGroup &g = group_of(stream, l); g.imu(l, s); }
     int step(const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, const double *t);
+    // frames [first, first + n) of every group.  pipelined: one run_balanced; otherwise lockstep (BatchGroup::run), the groups
+    // on their own threads (threaded) or one after another
     int run(int first, int n, bool threaded, bool pipelined = false);
     // ONE pipelined run of every group (no fill / drain at the warm-up / timed boundary): *elapsed_s = the time in which the
     // groups together completed frames n_groups x warmup + 1 ... n_groups x (warmup + steps) of the run (TimedShared).
-    int run_timed(int first, int warmup, int steps, int max_extra, double *elapsed_s);
-    // The same measurement with the batches NOT tied to queues: every group contributes a front-end worker and a filter worker
-    // (its two contexts and two threads), and a worker takes, frame by frame, the batch that is furthest behind and ready for its
-    // stage.  The hardware queues of a device are not served evenly, and which ones fall behind changes from run to run (measured:
+    int run_timed(int first, int warmup, int steps, int max_extra, double *elapsed_s) { return run_balanced(first, warmup, steps, max_extra, elapsed_s); }
+    // The scheduler of every pipelined run: the front-end of a batch runs on one worker and its filter on another, with at most
+    // two frames of the batch waiting between them.  The batches are NOT tied to queues: every group contributes a front-end worker and a filter
+    // worker (its two contexts and two threads), and a worker takes, frame by frame, the batch that is furthest behind and ready
+    // for its stage.  The hardware queues of a device are not served evenly, and which ones fall behind changes from run to run (measured:
     // 78 k to 99 k stereo frames/s for the same code with fixed batch-to-queue binding, some groups at 10 ms per frame and others
     // at 26); a slow queue then simply takes fewer batches, all streams advance at the same pace, and the device stays loaded.
     // Results are identical (a stream's arithmetic does not depend on the queue it runs on).
@@ -203,6 +189,8 @@ class MultiRunner {
     std::vector<std::unique_ptr<BatchGroup>> groups_;
     int fe_workers_ = 0, ekf_workers_ = 0;
     std::vector<int> off_, next_;   // per group: frame offset, next frame not yet processed
+    // the frame a run from `first` starts group g at: where it stands, or earlier while it catches up through its offset
+    int start_of(int g, int first) const { return (off_[g] > 0 || next_[g] > 0) ? std::min(next_[g], first + off_[g]) : first; }
     std::vector<TimedWindow> win_;
 };
 

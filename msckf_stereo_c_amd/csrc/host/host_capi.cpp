@@ -9,8 +9,8 @@ using namespace cg;
 extern "C" {
 
 void *mskfh_runner_create(int device, int n_groups, int per_group, const mskf_calib *calib, const mskf_fe_cfg *fe, const mskf_ekf_cfg *ekf,
-                          int host_threads, int ekf_host_threads, int halves) {
-    MultiRunner *r = new MultiRunner(device, n_groups, per_group, *calib, *fe, *ekf, host_threads, ekf_host_threads, halves);
+                          int host_threads, int ekf_host_threads) {
+    MultiRunner *r = new MultiRunner(device, n_groups, per_group, *calib, *fe, *ekf, host_threads, ekf_host_threads);
     if (!r->ok()) {
         std::fprintf(stderr, "mskfh_runner_create: %s\n", r->error().c_str());
         delete r;
@@ -49,7 +49,8 @@ void mskfh_runner_set_sequence(void *h, int stream, const uint8_t *cam0_base, co
     q.n_static = n_static; q.n_loop = n_loop; q.t0_ns = t0_ns; q.frame_dt_ns = frame_dt_ns; q.imu = imu; q.n_imu = n_imu;
     q.imu_cursor = 0;
 }
-// threaded: one host thread per group; pipelined: front-end and filter of each group run as a two-stage pipeline
+// pipelined: front-end and filter of each group run as a two-stage pipeline (MultiRunner::run_balanced); threaded: the groups
+// of a lockstep run on one host thread each
 int mskfh_runner_run(void *h, int first, int n, int threaded, int pipelined) { return ((MultiRunner *)h)->run(first, n, threaded != 0, pipelined != 0); }
 // `warmup` + `steps` frames of every group in one pipelined run; *elapsed_s covers exactly the `steps` frames (MultiRunner::run_timed)
 int mskfh_runner_run_timed(void *h, int first, int warmup, int steps, int max_extra, double *elapsed_s) {
@@ -58,7 +59,7 @@ int mskfh_runner_run_timed(void *h, int first, int warmup, int steps, int max_ex
 int mskfh_runner_frames_done(void *h, int g) { return ((MultiRunner *)h)->frames_done(g); }
 // group g's stages in the last timed window: [0] front-end open, [1] front-end close, [2] filter open, [3] filter close (steady
 // clock, s), [4] frames the front-end started inside, [5] frames the filter started inside, [6] frames of the run the batch had
-// completed when the shared window closed (balanced runner; 0 otherwise)
+// completed when the shared window closed
 void mskfh_runner_window(void *h, int g, double out[7]) {
     const TimedWindow &w = ((MultiRunner *)h)->window(g);
     out[0] = w.t_fe_begin; out[1] = w.t_fe_end; out[2] = w.t_ekf_begin; out[3] = w.t_ekf_end; out[4] = w.fe_frames; out[5] = w.ekf_frames;
@@ -105,21 +106,17 @@ void mskfh_runner_keep_trajectory(void *h, int keep) {
 
 void mskfh_runner_set_timing(void *h, int enable) {
     MultiRunner *r = (MultiRunner *)h;
-    for (int g = 0; g < r->n_groups(); ++g)
-        for (int h = 0; h < r->group(g).n_halves(); ++h) { mskf_ctx_set_timing(r->group(g).ctx(h), enable); mskf_ctx_set_timing(r->group(g).ekf_ctx(h), enable); }
+    for (int g = 0; g < r->n_groups(); ++g) { mskf_ctx_set_timing(r->group(g).ctx(), enable); mskf_ctx_set_timing(r->group(g).ekf_ctx(), enable); }
 }
 // sums over groups; arrays of MSKF_K_COUNT
 void mskfh_runner_get_timing(void *h, double *ms, long long *launches, long long *units, int reset) {
     MultiRunner *r = (MultiRunner *)h;
     for (int k = 0; k < MSKF_K_COUNT; ++k) { ms[k] = 0; launches[k] = 0; units[k] = 0; }
     for (int g = 0; g < r->n_groups(); ++g)
-        for (int h = 0; h < r->group(g).n_halves(); ++h) {
-            mskf_ctx *cs[2] = {r->group(g).ctx(h), r->group(g).ekf_ctx(h)};
-            for (mskf_ctx *c : cs) {
-                double m[MSKF_K_COUNT]; long long l[MSKF_K_COUNT], u[MSKF_K_COUNT];
-                if (mskf_ctx_get_timing(c, m, l, u, reset) != MSKF_OK) continue;
-                for (int k = 0; k < MSKF_K_COUNT; ++k) { ms[k] += m[k]; launches[k] += l[k]; units[k] += u[k]; }
-            }
+        for (mskf_ctx *c : {r->group(g).ctx(), r->group(g).ekf_ctx()}) {
+            double m[MSKF_K_COUNT]; long long l[MSKF_K_COUNT], u[MSKF_K_COUNT];
+            if (mskf_ctx_get_timing(c, m, l, u, reset) != MSKF_OK) continue;
+            for (int k = 0; k < MSKF_K_COUNT; ++k) { ms[k] += m[k]; launches[k] += l[k]; units[k] += u[k]; }
         }
 }
 
@@ -129,10 +126,7 @@ void mskfh_runner_get_abi_host_time(void *h, double *out, int reset) {
     MultiRunner *r = (MultiRunner *)h;
     for (int k = 0; k < 4; ++k) out[k] = 0;
     for (int g = 0; g < r->n_groups(); ++g)
-        for (int h = 0; h < r->group(g).n_halves(); ++h) {
-            mskf_ctx *cs[2] = {r->group(g).ctx(h), r->group(g).ekf_ctx(h)};
-            for (mskf_ctx *c : cs) { double t[4]; if (mskf_ctx_get_host_time(c, t, reset) == MSKF_OK) for (int k = 0; k < 4; ++k) out[k] += t[k]; }
-        }
+        for (mskf_ctx *c : {r->group(g).ctx(), r->group(g).ekf_ctx()}) { double t[4]; if (mskf_ctx_get_host_time(c, t, reset) == MSKF_OK) for (int k = 0; k < 4; ++k) out[k] += t[k]; }
 }
 
 // wall seconds per step() phase summed over groups (BatchGroup::PH_*), optionally reset

@@ -24,7 +24,7 @@ def lib():
             raise MskfError("libmskf_host.so is not built (run python -m msckf_stereo_c_amd.build); there is no CPU fallback")
         L = C.CDLL(p)
         L.mskfh_runner_create.restype = C.c_void_p
-        L.mskfh_runner_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(Calib), C.POINTER(FeCfg), C.POINTER(EkfCfg), C.c_int, C.c_int, C.c_int]
+        L.mskfh_runner_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(Calib), C.POINTER(FeCfg), C.POINTER(EkfCfg), C.c_int, C.c_int]
         L.mskfh_runner_set_workers.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mskfh_runner_set_compression.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_runner_destroy.argtypes = [C.c_void_p]
@@ -87,14 +87,14 @@ def set_fe_books_on_host(on):
 class Runner:
     """n_groups x per_group independent VIO streams on one GPU."""
 
-    def __init__(self, calib, fe_cfg, ekf_cfg, n_groups=1, per_group=1, device=0, host_threads=1, ekf_host_threads=0, halves=1):
+    def __init__(self, calib, fe_cfg, ekf_cfg, n_groups=1, per_group=1, device=0, host_threads=1, ekf_host_threads=0):
         """host_threads / ekf_host_threads: threads sharing the per-stream host phases of a group's front-end / filter stage
-        (0 = as host_threads); halves = 2: two staggered half-batches per stage (BatchGroup)."""
+        (0 = as host_threads)."""
         self.L = lib()
         self.calib, self.fe_cfg, self.ekf_cfg = calib, fe_cfg, ekf_cfg
         self.n = n_groups * per_group
         self.n_groups, self.per_group = n_groups, per_group
-        self.h = self.L.mskfh_runner_create(device, n_groups, per_group, C.byref(calib), C.byref(fe_cfg), C.byref(ekf_cfg), host_threads, ekf_host_threads, halves)
+        self.h = self.L.mskfh_runner_create(device, n_groups, per_group, C.byref(calib), C.byref(fe_cfg), C.byref(ekf_cfg), host_threads, ekf_host_threads)
         if not self.h:
             raise MskfError("could not create the runner (no GPU / HIP library?): see stderr")
         self._keep = []
@@ -143,7 +143,9 @@ class Runner:
 
     def run(self, first, n, threaded=True, pipelined=False):
         """Frames [first, first+n) of the attached sequences.  pipelined: front-end and filter of every group run
-        as a two-stage pipeline on two HIP streams (identical results: the front-end never reads filter state)."""
+        as a two-stage pipeline on two HIP streams (identical results: the front-end never reads filter state), all groups in
+        one run of MultiRunner::run_balanced.  threaded applies to lockstep runs only: the groups on their own host threads
+        (True) or one after another."""
         self._chk(self.L.mskfh_runner_run(self.h, first, n, int(threaded), int(pipelined)))
 
     def run_timed(self, first, warmup, steps, max_extra=8):

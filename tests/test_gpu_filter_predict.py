@@ -484,6 +484,69 @@ def test_pending_pos_var_read_out_blocks_predict_and_removal(gpu_ctx, oracle):
     s.close()
 
 
+def _work_beside_a_pending_read_out(parent, child, oracle):
+    """A position-variance read-out pending on `parent` (which then refuses predictions) while `child` runs a prediction batch
+    and an update batch to completion, each on a stream of its own.  Returns (read-out, P after prediction, P after update,
+    update rows) and the inputs."""
+    rng = np.random.default_rng(47)
+    calib = oracle.euroc_calib(376, 240)
+    pr = ekf_problems.make_problem(calib, seed=6, n_clones=10, n_feat=12)
+    P0, P1 = R.spd(N + 6 * 4, rng), R.spd(N + 6 * 5, rng)
+    J = R.augment_jacobian(rng)
+    steps = R.imu_steps(6, 0.005, gyro=GYRO["fast"], q0=ATT["general"], seed=47, jitter=0.05)
+    p, a, b = _stream(parent, oracle, 8), _stream(child, oracle, 8), _stream(child, oracle, 12)
+    p.ekf_set_cov(P0)
+    a.ekf_set_cov(P1)
+    b.ekf_set_cov(pr["P"])
+    full = dict(gravity=pr["gravity"], clones=pr["clones"], positions=pr["positions"], obs_start=pr["obs_start"], obs_clone=pr["obs_clone"],
+                obs_z=pr["obs_z"], dof_offset=-1, apply_row_cap=True)
+    out = parent.ekf_pos_var_batch_begin([p])
+    try:
+        with pytest.raises(capi.MskfError) as e:
+            parent.ekf_predict_batch([p], [steps], [J])
+        assert e.value.code == ERR_INVALID
+        child.ekf_predict_batch([a], [steps], [J])
+        res = child.ekf_update_batch([b], [full])
+    finally:
+        parent.ekf_pos_var_batch_end()
+    got = (out[0].copy(), a.ekf_get_cov(), b.ekf_get_cov(), res[0]["rows"])
+    for s in (p, a, b):
+        s.close()
+    return got, (P0, P1, pr["P"], steps, J)
+
+
+def test_shared_context_beside_a_pending_batch_of_its_parent(gpu_ctx, oracle):
+    """mskf_ctx_create_shared: a second context with staging arenas of its own that enqueues on its parent's HIP stream.  It
+    reports the parent's stream; while a read-out is pending on the parent, a prediction batch and an update batch run to
+    completion on the shared context (their arenas are not the pending batch's); the covariances are bit-identical to the
+    same work on two independent contexts; and destroying the shared context first leaves the parent usable."""
+    shared = capi.Context(shared_with=gpu_ctx)
+    try:
+        assert shared.hip_stream() == gpu_ctx.hip_stream()
+        (pv, Pa, Pb, rows), (P0, P1, Pu, steps, J) = _work_beside_a_pending_read_out(gpu_ctx, shared, oracle)
+    finally:
+        shared.close()
+    c1, c2 = capi.Context(0), capi.Context(0)
+    try:
+        assert c1.hip_stream() != c2.hip_stream()
+        (pv_i, Pa_i, Pb_i, rows_i), _ = _work_beside_a_pending_read_out(c1, c2, oracle)
+    finally:
+        c2.close()
+        c1.close()
+    assert np.array_equal(pv, _pv(P0)) and np.array_equal(pv_i, pv)
+    _check_predicted(Pa, P1, steps, J)
+    assert rows > 0 and not np.array_equal(Pb, Pu)
+    assert np.array_equal(Pa, Pa_i) and np.array_equal(Pb, Pb_i) and rows == rows_i
+    # the parent, its shared context destroyed
+    s = _stream(gpu_ctx, oracle, 8)
+    s.ekf_set_cov(P0)
+    gpu_ctx.ekf_predict_batch([s], [steps], [J])
+    P2 = s.ekf_get_cov()
+    _check_predicted(P2, P0, steps, J)
+    assert np.array_equal(gpu_ctx.ekf_pos_var_batch([s])[0], _pv(P2))
+    s.close()
+
+
 # ------------------------------------------------------------------------------------------------ f. staging copies
 class _Hip:
     """hipMalloc / hipHostMalloc / hipMemcpy of the HIP runtime the library itself is linked against."""

@@ -149,7 +149,8 @@ def _attach_sequences(oracle, run, syns, n_frames, keep):
 
 
 def test_pipelined_run_is_identical_to_lockstep(oracle):
-    """BatchGroup::run_pipelined (front-end thread | filter thread, two HIP streams) == lockstep run == oracle."""
+    """One batch through MultiRunner::run_balanced (a front-end worker | a filter worker, two HIP streams) == lockstep run
+    (BatchGroup::run) == oracle."""
     w, h, n_frames = 376, 240, 70
     fe, ekf = default_fe_cfg(), default_ekf_cfg(max_cam_state_size=10)
     syns = [oracle.Synth(seed=0x5EED0020 + i, width=w, height=h) for i in range(2)]
@@ -175,34 +176,6 @@ def test_pipelined_run_is_identical_to_lockstep(oracle):
         assert np.array_equal(osys.dump()[0], b.dump(i)[0])
         op = osys.poses()
         assert np.abs(op["p"] - pb["p"]).max() < POS_TOL
-    for r in runs:
-        r.close()
-
-
-def test_half_batches_on_a_shared_stream_are_identical(oracle):
-    """halves=2: a group drives two staggered half-batches per stage, each on its own context sharing the stage's
-    HIP stream (mskf_ctx_create_shared), through the *_batch_begin / *_batch_end halves of the C-ABI.  Everything must be
-    bit-identical to the one-batch run, the filter included: which kernels handle a stream's update is decided per
-    STREAM (EkfStreamDev::route), never from the rest of the batch, so a stream's arithmetic does not depend on which
-    streams share its launches.  (Round 2 chose the route per batch and this test had to be relaxed to 1e-9.)"""
-    w, h, n_frames = 376, 240, 60
-    fe, ekf = default_fe_cfg(), default_ekf_cfg(max_cam_state_size=10)
-    syns = [oracle.Synth(seed=0x5EED0060 + i, width=w, height=h) for i in range(4)]
-    keep, runs = [], []
-    for halves in (1, 2):
-        run = R.Runner(syns[0].calib, fe, ekf, 1, 4, host_threads=1, halves=halves)
-        _attach_sequences(oracle, run, syns, n_frames, keep)
-        run.run(0, n_frames, threaded=True, pipelined=True)
-        runs.append(run)
-    a, b = runs
-    for i in range(4):
-        for x, y in zip(a.dump(i)[:4], b.dump(i)[:4]):
-            assert np.array_equal(x, y)
-        pa, pb = a.poses(i), b.poses(i)
-        assert len(pa) == len(pb) > 15
-        assert np.array_equal(pa["p"], pb["p"]) and np.array_equal(pa["q"], pb["q"])
-        assert np.array_equal(a.cov(i), b.cov(i))
-        assert a.num_updates(i) == b.num_updates(i) > 0
     for r in runs:
         r.close()
 
@@ -568,19 +541,21 @@ def test_nap_wait_mode_in_a_child_process():
 
 
 _TIMED_RUN = {}
+TIMED_BATCHES = [3, 1]      # three staggered batches (c2 / c3 / c5 shape), and one batch with no extra frames (bench.py's c4)
 
 
-def _timed_run(oracle):
-    """ONE run of MultiRunner::run_timed (three staggered batches), shared by the two tests below: what was computed, and
-    how the window was accounted."""
-    if _TIMED_RUN:
-        return _TIMED_RUN
-    w, h, prime, warm, steps, delta, extra = 376, 240, 26, 3, 9, 5, 12
+def _timed_run(oracle, nb):
+    """ONE run of MultiRunner::run_timed over nb batches, shared by the two tests below: what was computed, and how the window
+    was accounted.  One batch gets max_extra = 0, as bench.py gives it."""
+    if nb in _TIMED_RUN:
+        return _TIMED_RUN[nb]
+    w, h, prime, warm, steps, delta = 376, 240, 26, 3, 9, 5
+    extra = 12 if nb > 1 else 0
     fe, ekf = default_fe_cfg(), default_ekf_cfg(max_cam_state_size=10)
     syn = oracle.Synth(seed=0x5EED0061, width=w, height=h)
     keep = []
-    run = R.Runner(syn.calib, fe, ekf, 3, 1, host_threads=1)
-    _attach_sequences(oracle, run, [syn, syn, syn], prime + warm + steps + 2 * delta + extra + 2, keep)
+    run = R.Runner(syn.calib, fe, ekf, nb, 1, host_threads=1)
+    _attach_sequences(oracle, run, [syn] * nb, prime + warm + steps + (nb - 1) * delta + extra + 2, keep)
     run.set_stagger(delta)
     run.run(0, prime, threaded=True, pipelined=True)
     run.set_timing(1)
@@ -588,26 +563,27 @@ def _timed_run(oracle):
     elapsed = run.run_timed(prime, warm, steps, max_extra=extra)
     timing = run.get_timing(reset=True)
     run.set_timing(False)
-    _TIMED_RUN.update(dict(shape=(prime, warm, steps, delta, extra), fe=fe, ekf=ekf, syn=syn, elapsed=elapsed, timing=timing,
-                           phases=run.get_window_phases(), windows=[run.window(g) for g in range(3)],
-                           done=[run.frames_done(g) - run.group_offset(g) for g in range(3)],
-                           marks=[run.mark_dump(g) for g in range(3)], dumps=[run.dump(g) for g in range(3)],
-                           poses=[run.poses(g) for g in range(3)]))
+    _TIMED_RUN[nb] = dict(shape=(prime, warm, steps, delta, extra), fe=fe, ekf=ekf, syn=syn, elapsed=elapsed, timing=timing,
+                          phases=run.get_window_phases(), windows=[run.window(g) for g in range(nb)],
+                          done=[run.frames_done(g) - run.group_offset(g) for g in range(nb)],
+                          marks=[run.mark_dump(g) for g in range(nb)], dumps=[run.dump(g) for g in range(nb)],
+                          poses=[run.poses(g) for g in range(nb)])
     run.close()
-    return _TIMED_RUN
+    return _TIMED_RUN[nb]
 
 
-def test_timed_window_results(oracle):
+@pytest.mark.parametrize("nb", TIMED_BATCHES)
+def test_timed_window_results(oracle, nb):
     """MultiRunner::run_timed (bench.py): warm-up + timed steps in ONE pipelined run.  The window is defined on the work
     (it opens when the batches together have completed n_groups x warm-up frames and closes at n_groups x (warm-up + steps)),
     every batch runs at least warm-up + steps frames and keeps stepping until the window is closed.  The sentinel snapshot
     taken after frame warm-up + steps of a batch equals the oracle at exactly that frame whatever the batch did afterwards,
     the live state has moved on by the drain frames, and the trajectory over all frames stays within tolerance."""
-    T = _timed_run(oracle)
+    T = _timed_run(oracle, nb)
     prime, warm, steps, delta, extra = T["shape"]
     syn, fe, ekf = T["syn"], T["fe"], T["ekf"]
     assert T["elapsed"] > 0
-    for g in range(3):
+    for g in range(nb):
         done = T["done"][g]
         assert prime + warm + steps <= done <= prime + warm + steps + extra
         # the batch's sentinel after frame prime + warm + steps (+ offset) = the oracle after exactly that many frames
@@ -625,22 +601,23 @@ def test_timed_window_results(oracle):
         assert len(op) == len(gp) and np.abs(op["p"] - gp["p"]).max() < POS_TOL
 
 
-def test_timed_window_accounting(oracle):
+@pytest.mark.parametrize("nb", TIMED_BATCHES)
+def test_timed_window_accounting(oracle, nb):
     """The accounting of the same run, asserted structurally (nothing here depends on how fast the box is): the window
     holds exactly steps x batches completed frames; every stage opened its gates before it closed them; every phase item
     is non-negative and a thread's items do not add up to more than its own window; kernels are timed only inside the
     window (the pyramid launches equal the front-end frames started in it)."""
-    T = _timed_run(oracle)
+    T = _timed_run(oracle, nb)
     prime, warm, steps, delta, extra = T["shape"]
     wins, ph = T["windows"], T["phases"]
     # completed frames of the run when the window closed: warm-up + timed steps of every batch, wherever each batch stood
-    assert sum(int(wd["frames_at_close"]) for wd in wins) == 3 * (warm + steps)
+    assert sum(int(wd["frames_at_close"]) for wd in wins) == nb * (warm + steps)
     for g, wd in enumerate(wins):
         assert 0 < wd["fe_open"] < wd["fe_close"] and 0 < wd["ekf_open"] < wd["ekf_close"]
         assert 0 <= wd["frames_at_close"] <= T["done"][g] - prime
         assert wd["fe_frames"] >= 1 and wd["ekf_frames"] >= 1
     fe_frames = sum(int(wd["fe_frames"]) for wd in wins)
-    assert fe_frames <= 3 * (steps + extra + 2)
+    assert fe_frames <= nb * (steps + extra + 2)
     assert all(v >= 0.0 for v in ph.values())
     fe_sum = sum(ph[k] for k in R.Runner.FE_THREAD_PHASES)
     fe_win = sum(wd["fe_close"] - wd["fe_open"] for wd in wins)
