@@ -128,6 +128,7 @@ class Context:
             self.L.mskf_ctx_create_shared.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
             _chk(self.L.mskf_ctx_create_shared(shared_with.h, C.byref(self.h)))
         self.streams = []
+        self._trk_pending = None
 
     def close(self):
         if self.h:
@@ -148,6 +149,33 @@ class Context:
         self.L.mskf_ekf_update_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(EkfUpdateArgs)]
         _chk(self.L.mskf_ekf_update_batch(self.h, n, hs, args))
         return [b[2]() for b in built]
+
+    def _track_batch_args(self, streams, problems):
+        n = len(streams)
+        built = [Stream._track_args(**pr) for pr in problems]
+        args = (TrackArgs * n)(*[b[0] for b in built])
+        hs = (C.c_void_p * n)(*[s.h for s in streams])
+        return n, built, args, hs
+
+    def track_batch(self, streams, problems):
+        """One mskf_fe_track_batch over several streams of this context; problems[i] = kwargs of Stream.track."""
+        n, built, args, hs = self._track_batch_args(streams, problems)
+        self.L.mskf_fe_track_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(TrackArgs)]
+        _chk(self.L.mskf_fe_track_batch(self.h, n, hs, args))
+        return [b[2] for b in built]
+
+    def track_batch_begin(self, streams, problems):
+        """mskf_fe_track_batch_begin: enqueue the batch; the returned result dicts are filled by track_batch_end."""
+        n, built, args, hs = self._track_batch_args(streams, problems)
+        self.L.mskf_fe_track_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(TrackArgs)]
+        _chk(self.L.mskf_fe_track_batch_begin(self.h, n, hs, args))
+        self._trk_pending = (built, args, hs)          # must stay alive until _end
+        return [b[2] for b in built]
+
+    def track_batch_end(self):
+        self.L.mskf_fe_track_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_fe_track_batch_end(self.h))
+        self._trk_pending = None
 
     def ekf_predict_batch(self, streams, steps, J):
         """One mskf_ekf_predict_batch: streams[i] propagates over steps[i] (IMU_STEP records, None = none), then augments
@@ -258,7 +286,9 @@ class Stream:
         _chk(self.L.mskf_fe_get_cell_candidates(self.h, int(min_score), _p(out), n, C.byref(got)))
         return out[:got.value]
 
-    def track(self, pts, do_temporal, Hpred=None):
+    @staticmethod
+    def _track_args(pts, do_temporal, Hpred=None):
+        """(mskf_fe_track_args, buffers it points into, result dict the call fills) for one stream."""
         pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
         n = len(pts)
         out0, out1, und0, und1 = (np.zeros((n, 2), np.float32) for _ in range(4))
@@ -269,8 +299,12 @@ class Stream:
         H = np.eye(3) if Hpred is None else np.ascontiguousarray(Hpred, dtype=np.float64)
         a.Hpred[:] = list(H.reshape(-1))
         a.out0, a.out1, a.und0, a.und1, a.status = (x.ctypes.data for x in (out0, out1, und0, und1, status))
+        return a, pts, dict(out0=out0, out1=out1, und0=und0, und1=und1, status=status)
+
+    def track(self, pts, do_temporal, Hpred=None):
+        a, _keep, result = self._track_args(pts, do_temporal, Hpred)
         _chk(self.L.mskf_fe_track(self.h, C.byref(a)))
-        return dict(out0=out0, out1=out1, und0=und0, und1=und1, status=status)
+        return result
 
     def swap(self):
         _chk(self.L.mskf_fe_swap(self.h))

@@ -503,6 +503,15 @@ static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const u
     if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    // A push returns once its work is enqueued (the mark behind it is waited for by whoever reads the cell maxima), and its
+    // copy kernel reads the pinned job / descriptor arrays when it runs: a second push straight after the first (push, swap,
+    // push) must not overwrite them before that.  Without this wait the first push could build the pyramid the SECOND one
+    // described and leave its own image with the levels 1 .. 3 of whatever the buffer held before.
+    // This guards the push -> push hand-over of the public (copy_cells) path only: every such push records cell_ev behind its
+    // last command.  A device-frame push (copy_cells = false) records nothing; its staging is protected by the pending frame
+    // batch (mskf_refuse_if_owned above, and _end drains the stream), and after one the wait below is on an older mark that
+    // is already satisfied.
+    if (ctx->cell_mark_recorded && (rc = mskf_wait_event(ctx, &ctx->cell_ev, false)) != MSKF_OK) return rc;
     rc = ctx->jobs.ensure((size_t)n * 2);
     if (rc != MSKF_OK) return rc;
     rc = ctx->desc[0].ensure(n);
@@ -579,6 +588,7 @@ static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const u
     if (copy_cells) {
         { const MskfCopy cp = {ctx->cell_arena.h, ctx->cell_arena.d, cell_bytes}; const int crc = mskf_copy_async(ctx, &cp, 1); if (crc != MSKF_OK) return crc; }
         { const int erc = mskf_wait_event(ctx, &ctx->cell_ev, true); if (erc != MSKF_OK) return erc; }
+        ctx->cell_mark_recorded = true;
     }
     MSKF_HIPCHK(hipGetLastError());
     return MSKF_OK;

@@ -144,6 +144,7 @@ struct mskf_ctx {
     PinnedDev<char> trk_in, trk_out;  // input points / results of every stream of a track batch (one copy each way)
     unsigned long long push_gen = 0;
     hipEvent_t cell_ev = nullptr;     // recorded behind the D2H copy of the per-cell maxima of the last push
+    bool cell_mark_recorded = false;  // a push has recorded cell_ev: the next push waits for it before it reuses the staging
     bool cell_keys_dirty = true;      // the key array holds bytes no generation tag explains (fresh allocation): clear before use
     PinnedDev<Pyr3Job> jobs;
     PinnedDev<EkfStreamDev> ekf_desc;

@@ -2,9 +2,9 @@
 //
 //  k_pyr_down3    : cg::pyr_down x 3        (reference call sites image_processor.cpp:239,242): levels 1 .. 3 of an image in one launch
 //  k_detect_cells : cg::CornerDetector      (:132,259,657) — per-cell integer Shi-Tomasi maximum (32x32 px tiles)
-//  k_lk_points4   : cg::optical_flow_multi_level (:410 temporal, :569 stereo) with the prediction (:321-350);
-//  k_pt_geom      : the image-bounds gates (:416-424, :575-583), the stereo initial guess (:542-548),
-//                   undistortion and the epipolar gate (:587-617), one thread per point.
+//  k_track4       : cg::optical_flow_multi_level (:410 temporal, :569 stereo) with the prediction (:321-350), the
+//                   image-bounds gates (:416-424, :575-583), the stereo initial guess (:542-548), undistortion and
+//                   the epipolar gate (:587-617): one launch per track call, four points per wavefront.
 //
 // Arithmetic contract: every decision-bearing quantity is integer or a fixed
 // sequence of IEEE-754 double operations; this file must be compiled with -ffp-contract=off.
@@ -655,7 +655,7 @@ __device__ __forceinline__ double lk_scaled_f64(long long b) {
 }
 
 // ------------------------------------------------------------------------------------------ LK, four points per wavefront
-// k_lk_points4: pyramidal LK (OpenCV calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW semantics, fixed point: every
+// l4_track (the LK half of k_track4): pyramidal LK (OpenCV calcOpticalFlowPyrLK with OPTFLOW_USE_INITIAL_FLOW semantics, fixed point: every
 // decision-bearing quantity is an integer or a fixed sequence of double operations) with a 16-lane row of the
 // wavefront per point: lane r of a row owns image row r of the 16 x 16 search footprint, i.e. ALL 15 pixels of window
 // row r.  What that buys over one wavefront per point (round 1: 2840 VALU instructions per point, now 1950):
@@ -993,7 +993,8 @@ __device__ __forceinline__ void l4_track(const PyrDev &A, const PyrDev &B, bool 
 //   -> image-bounds gate (:416-424) -> stereo initial guess undistort(cam0, R01) . distort(cam1) (:542-548)
 //   -> stereo LK curr cam0 -> curr cam1 (:569) -> image-bounds gate (:575-583), undistorted points (:601-604, also what
 //   publish() sends, :1154-1155) and the epipolar gate (:605-617).
-// Round 2 ran this chain as five launches (k_lk_points4 x 2 + k_pt_geom x 3, one thread per point for the geometry) with
+// Round 2 ran this chain as five launches (two LK launches and three geometry launches, kernels that no longer exist, one thread
+// per point for the geometry) with
 // out0 / out1 / status making a round trip through global memory between each; the per-point double-precision geometry is
 // a few hundred instructions, issued here once per wavefront for its four points (the sixteen lanes of a row compute the
 // same values).  The two tracks run through ONE copy of the LK code (a two-trip loop), so the kernel is no larger.

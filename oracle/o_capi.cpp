@@ -52,6 +52,20 @@ void orc_lk_track(const uint8_t *imgA, const uint8_t *imgB, int w, int h, int n,
     for (int i = 0; i < n; ++i) { ptsB[i] = b[i]; status[i] = st[i]; }
 }
 
+// The same tracks point by point with a trace record each (o_image.h LkTrace: 63 int64 per point)
+void orc_lk_track_trace(const uint8_t *imgA, const uint8_t *imgB, int w, int h, int n, const mskf_point2f *ptsA,
+                        mskf_point2f *ptsB, uint8_t *status, int64_t *trace) {
+    static_assert(sizeof(LkTrace) == 63 * sizeof(int64_t), "oracle_py.LK_TRACE mirrors this layout");
+    std::vector<Img> pa, pb;
+    build_pyramid(wrap(imgA, w, h), pa);
+    build_pyramid(wrap(imgB, w, h), pb);
+    for (int i = 0; i < n; ++i) {
+        LkTrace tr;
+        lk_track_point_trace(pa, pb, ptsA[i].x, ptsA[i].y, ptsB[i].x, ptsB[i].y, status[i], &tr);
+        std::memcpy(trace + (size_t)i * 63, &tr, sizeof(tr));
+    }
+}
+
 // all det_rows*det_cols per-cell maxima (score 0 = none)
 void orc_cell_maxima(const uint8_t *img, int w, int h, int det_rows, int det_cols, mskf_corner *out) {
     CornerDetector d(det_rows, det_cols, 0);

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cfloat>
 #include <cstring>
+#include <cstdlib>
 
 namespace orc {
 
@@ -76,8 +77,33 @@ static inline int sample5(const Img &im, int x, int y, int w00, int w01, int w10
 // work counters for sizing the GPU kernel: [0] points, [1] levels solved, [2] iterations
 long long g_lk_stats[3] = {0, 0, 0};
 
+// |sum over one window row| and |sum over up to four adjacent window rows| (every start row, so the aligned groups the
+// device sums in 32 bits, rows 12..14 included, are among them) of one accumulator's 15 row sums
+static void trace_partials(const int64_t row[15], int64_t &lane, int64_t &quad, int64_t &total) {
+    int64_t t = 0;
+    for (int j = 0; j < 15; ++j) t += row[j];
+    if (t < 0) t = -t;
+    if (t > total) total = t;
+    for (int j = 0; j < 15; ++j) {
+        const int64_t a = row[j] < 0 ? -row[j] : row[j];
+        if (a > lane) lane = a;
+        int64_t q = 0;
+        for (int k = j; k < 15 && k < j + 4; ++k) q += row[k];
+        if (q < 0) q = -q;
+        if (q > quad) quad = q;
+    }
+}
+
 void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
                     float ax, float ay, float &bx, float &by, uint8_t &status) {
+    lk_track_point_trace(pyrA, pyrB, ax, ay, bx, by, status, nullptr);
+}
+
+// The same track; with tr != nullptr it also reports what the point went through (o_image.h LkTrace).  The trace only
+// observes: no value that decides the result depends on it.
+void lk_track_point_trace(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
+                          float ax, float ay, float &bx, float &by, uint8_t &status, LkTrace *tr) {
+    if (tr) *tr = LkTrace();
     const double FLT_SCALE = 1.0 / (1 << 20);
     const double MIN_EIG = 1e-4;
     const double EPS2 = 0.01 * 0.01;
@@ -94,12 +120,23 @@ void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
         else { ncx = ncx * 2.0f; ncy = ncy * 2.0f; }
 
         const int ipx = (int)floorf(pwx), ipy = (int)floorf(pwy);
+        LkTraceLevel *tl = tr ? &tr->lvl[l] : nullptr;
+        if (tl) { tl->ipx = ipx; tl->ipy = ipy; }
         if (ipx < -LK_WIN || ipx >= A.w || ipy < -LK_WIN || ipy >= A.h) {
             if (l == 0) status = 0;
             continue;
         }
         int w00, w01, w10, w11;
         bilinear_weights(pwx - (float)ipx, pwy - (float)ipy, w00, w01, w10, w11);
+        if (tl) {
+            tl->entered = 1;
+            if (w11 == -1) {
+                tr->w11_neg |= 1;
+                for (int j = -1; j <= 15; ++j)
+                    for (int i = -1; i <= 15; ++i)
+                        if (A.at(ipx + i + 1, ipy + j + 1) == 255) tr->w11_neg |= 2;
+            }
+        }
 
         // 17x17 interpolated template, index [j+1][i+1] for i,j in [-1,15]
         int P[17][17];
@@ -108,6 +145,7 @@ void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
                 P[j + 1][i + 1] = sample5(A, ipx + i, ipy + j, w00, w01, w10, w11);
         int Ix[15][15], Iy[15][15];
         int64_t A11 = 0, A12 = 0, A22 = 0;
+        int64_t r11[15] = {0}, r12[15] = {0}, r22[15] = {0};
         for (int j = 0; j < 15; ++j)
             for (int i = 0; i < 15; ++i) {
                 const int (*p)[17] = P;
@@ -119,7 +157,17 @@ void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
                 const int gx = (sx + 16) >> 5, gy = (sy + 16) >> 5;
                 Ix[j][i] = gx; Iy[j][i] = gy;
                 A11 += (int64_t)gx * gx; A12 += (int64_t)gx * gy; A22 += (int64_t)gy * gy;
+                if (tr) {
+                    r11[j] += (int64_t)gx * gx; r12[j] += (int64_t)gx * gy; r22[j] += (int64_t)gy * gy;
+                    if (std::abs(gx) > tr->max_Ix) tr->max_Ix = std::abs(gx);
+                    if (std::abs(gy) > tr->max_Iy) tr->max_Iy = std::abs(gy);
+                }
             }
+        if (tr) {
+            trace_partials(r11, tr->lane[0], tr->quad[0], tr->total[0]);
+            trace_partials(r12, tr->lane[1], tr->quad[1], tr->total[1]);
+            trace_partials(r22, tr->lane[2], tr->quad[2], tr->total[2]);
+        }
         const double a11 = (double)A11 * FLT_SCALE, a12 = (double)A12 * FLT_SCALE, a22 = (double)A22 * FLT_SCALE;
         double D = a11 * a22 - a12 * a12;
         const double dd = a11 - a22;
@@ -130,6 +178,7 @@ void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
         }
         D = 1.0 / D;
         ++g_lk_stats[1];
+        if (tl) tl->solved = 1;
 
         float wx = ncx - (float)LK_HALF_WIN, wy = ncy - (float)LK_HALF_WIN;
         float pdx = 0.f, pdy = 0.f;
@@ -141,13 +190,36 @@ void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
             }
             bilinear_weights(wx - (float)inx, wy - (float)iny, w00, w01, w10, w11);
             ++g_lk_stats[2];
+            if (tl) {
+                if (tl->iters == 0) { tl->inx0 = tl->inx_min = tl->inx_max = inx; tl->iny0 = tl->iny_min = tl->iny_max = iny; }
+                if (inx < tl->inx_min) tl->inx_min = inx;
+                if (inx > tl->inx_max) tl->inx_max = inx;
+                if (iny < tl->iny_min) tl->iny_min = iny;
+                if (iny > tl->iny_max) tl->iny_max = iny;
+                ++tl->iters;
+                if (w11 == -1) {
+                    tr->w11_neg |= 1;
+                    for (int j = 0; j < 15; ++j)
+                        for (int i = 0; i < 15; ++i)
+                            if (B.at(inx + i + 1, iny + j + 1) == 255) tr->w11_neg |= 2;
+                }
+            }
             int64_t b1 = 0, b2 = 0;
+            int64_t rb1[15] = {0}, rb2[15] = {0};
             for (int j = 0; j < 15; ++j)
                 for (int i = 0; i < 15; ++i) {
                     const int diff = sample5(B, inx + i, iny + j, w00, w01, w10, w11) - P[j + 1][i + 1];
                     b1 += (int64_t)diff * Ix[j][i];
                     b2 += (int64_t)diff * Iy[j][i];
+                    if (tr) {
+                        rb1[j] += (int64_t)diff * Ix[j][i]; rb2[j] += (int64_t)diff * Iy[j][i];
+                        if (std::abs(diff) > tr->max_diff) tr->max_diff = std::abs(diff);
+                    }
                 }
+            if (tr) {
+                trace_partials(rb1, tr->lane[3], tr->quad[3], tr->total[3]);
+                trace_partials(rb2, tr->lane[4], tr->quad[4], tr->total[4]);
+            }
             const double db1 = (double)b1 * FLT_SCALE, db2 = (double)b2 * FLT_SCALE;
             const float dx = (float)((a12 * db2 - a22 * db1) * D);
             const float dy = (float)((a12 * db1 - a11 * db2) * D);

@@ -41,6 +41,27 @@ void lk_track(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
 void lk_track_point(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
                     float ax, float ay, float &bx, float &by, uint8_t &status);
 
+// What one lk_track_point call went through, for tests that must state from the oracle alone which edges of the device
+// kernel their inputs reach (all fields int64 so that the record is a plain array for the Python side).
+struct LkTraceLevel {
+    int64_t entered = 0;         // the template window passed the level's in-image gate
+    int64_t solved = 0;          // ... and its 2x2 system passed the eigenvalue / determinant gate
+    int64_t ipx = 0, ipy = 0;    // integer template corner (set for every level, entered or not)
+    int64_t inx0 = 0, iny0 = 0;  // integer search corner of the first iteration that ran
+    int64_t inx_min = 0, inx_max = 0, iny_min = 0, iny_max = 0;   // over the iterations that ran
+    int64_t iters = 0;           // iterations that ran (their search window was inside the gate)
+};
+struct LkTrace {
+    LkTraceLevel lvl[LK_LEVELS];
+    int64_t max_Ix = 0, max_Iy = 0, max_diff = 0;   // largest magnitudes over all levels and iterations
+    int64_t w11_neg = 0;         // bit 0: a fourth bilinear weight was -1; bit 1: ... and multiplied a 255 pixel
+    int64_t lane[5] = {0, 0, 0, 0, 0};   // largest |sum over one window row| of the A11, A12, A22, b1, b2 terms
+    int64_t quad[5] = {0, 0, 0, 0, 0};   // largest |sum over up to four adjacent window rows| of the same
+    int64_t total[5] = {0, 0, 0, 0, 0};  // largest |sum over the whole window| of the same (what the device sums in 64 bits)
+};
+void lk_track_point_trace(const std::vector<Img> &pyrA, const std::vector<Img> &pyrB,
+                          float ax, float ay, float &bx, float &by, uint8_t &status, LkTrace *tr);
+
 // K4: grid corner detector. One best integer Shi-Tomasi corner per det cell.
 struct CornerDetector {
     int rows = 30, cols = 47, thr = 10;

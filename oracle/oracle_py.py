@@ -64,6 +64,7 @@ def lib():
         L.orc_system_get_imu_state.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_pyr_down.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.orc_lk_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_lk_track_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_cell_maxima.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.orc_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_detect.restype = C.c_int
@@ -275,6 +276,25 @@ def lk_track(imgA, imgB, ptsA, ptsB_init):
     st = np.zeros(len(a), np.uint8)
     lib().orc_lk_track(_p(np.ascontiguousarray(imgA)), _p(np.ascontiguousarray(imgB)), w, h, len(a), _p(a), _p(b), _p(st))
     return b, st
+
+
+# orc::LkTrace (o_image.h): what each point went through, level by level (index = pyramid level)
+LK_TRACE_LEVEL = np.dtype([(k, "<i8") for k in ("entered", "solved", "ipx", "ipy", "inx0", "iny0", "inx_min", "inx_max",
+                                                "iny_min", "iny_max", "iters")])
+LK_TRACE = np.dtype([("lvl", LK_TRACE_LEVEL, 4), ("max_Ix", "<i8"), ("max_Iy", "<i8"), ("max_diff", "<i8"), ("w11_neg", "<i8"),
+                     ("lane", "<i8", 5), ("quad", "<i8", 5), ("total", "<i8", 5)])
+assert LK_TRACE.itemsize == 63 * 8
+
+
+def lk_track_trace(imgA, imgB, ptsA, ptsB_init):
+    """lk_track plus one LK_TRACE record per point; positions and status are those of lk_track."""
+    h, w = imgA.shape
+    a = np.ascontiguousarray(ptsA, dtype=np.float32).reshape(-1, 2)
+    b = np.ascontiguousarray(ptsB_init, dtype=np.float32).reshape(-1, 2).copy()
+    st = np.zeros(len(a), np.uint8)
+    tr = np.zeros(len(a), LK_TRACE)
+    lib().orc_lk_track_trace(_p(np.ascontiguousarray(imgA)), _p(np.ascontiguousarray(imgB)), w, h, len(a), _p(a), _p(b), _p(st), _p(tr))
+    return b, st, tr
 
 
 def cell_maxima(img, det_rows=30, det_cols=47):
