@@ -6,24 +6,7 @@
 #include "../../../include/mskf_chi2_table.h"
 #include "mskf_internal.h"
 
-extern "C" {
-void ekf_launch_propagate(const EkfStreamDev *d, int n, hipStream_t st);
-void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st);
-void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave, const int *work_small, int n_small, const int *work_big, int n_big,
-                         int max_rows, int max_rows_small, int big_clones, hipStream_t st);
-void ekf_launch_pair_features(const EkfStreamDev *d, int n, int max_feat, int max_tri, hipStream_t st);
-void ekf_launch_posvar(const EkfStreamDev *d, int n, double *out, hipStream_t st);
-void ekf_launch_posvar_upd(const EkfStreamDev *d, int n, hipStream_t st);
-void ekf_launch_gemm(const EkfStreamDev *d, int n, int mode, int max_mn, hipStream_t st);
-void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int max_d, hipStream_t st);
-void ekf_launch_tsqr(const EkfStreamDev *d, int n, int max_d, int do_cap, hipStream_t st);
-void ekf_launch_trsm(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
-void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
-int ekf_small_update_max_na(void);
-}
-
 namespace {
-constexpr int kMaxClonesDev = 64;   // MAX_CLONES_DEV in ekf_kernels.hip
 constexpr int kMaxRows = 65536;     // stacked-Jacobian row capacity per stream and update
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -49,8 +32,8 @@ static EkfExtra *extra_of(mskf_stream *s) { return (EkfExtra *)s->ekf_extra; }
 int mskf_ekf_stream_init(mskf_stream *s) {
     EkfStreamState &E = s->ekf_state;
     E.max_clones = s->ekf.max_cam_state_size;
-    if (E.max_clones < 4 || E.max_clones > kMaxClonesDev) {
-        mskf_set_error("max_cam_state_size must be in [4, 64]");
+    if (E.max_clones < 4 || E.max_clones > MAX_CLONES_DEV) {
+        mskf_set_error("max_cam_state_size must be in [4, " + std::to_string(MAX_CLONES_DEV) + "]");
         return MSKF_ERR_UNSUPPORTED;
     }
     if (s->ekf.compression_mode < 0 || s->ekf.compression_mode > 3) {
@@ -384,166 +367,166 @@ extern "C" int mskf_ekf_update_batch(mskf_ctx *ctx, int n, mskf_stream *const *s
     return rc != MSKF_OK ? rc : mskf_ekf_update_batch_end(ctx);
 }
 
-extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_update_args *args) {
-    if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
-    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);
-    if (rc != MSKF_OK) return rc;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    const auto t_h0 = std::chrono::steady_clock::now();
-    hipStream_t st = ctx->stream;
-    DrainOnError drain{st};
-    rc = ctx->ekf_desc.ensure(n);
-    if (rc != MSKF_OK) return rc;
-    int max_feat = 0, max_m = 0, max_d = 0, max_frows = 0, max_tri = 0, max_clones_cfg = 0;
-    // Which kernels handle a stream is decided per STREAM, from that stream's features alone (EkfStreamDev::route): the same
-    // stream takes the same route, and therefore runs the same arithmetic, whatever else is in the batch.
-    //   pairs : every feature has exactly two Jacobian observations, all of the same ordered clone pair (the pruning update)
-    //   wave  : every feature has <= 4 Jacobian observations and a triangulation over <= 32 clones: class [0] of the
-    //           feature kernel, one wavefront per feature; otherwise a feature is in class [1] (<= 16 observations) or [2]
-    //   small : the stream touches at most four clones (<= 24 active columns): whole update in k_ekf_small_update
-    int max_frows_cls[3] = {0, 0, 0};
-    std::vector<int> &cnt_cls = ctx->pend_upd.cnt_cls;          // [3][n]
-    cnt_cls.assign((size_t)3 * n, 0);
-    std::vector<int> route(n, 0), na_max(n, 0);
-    bool any_pairs = false, any_small = false, any_general = false;
-    bool any_householder = false, any_gram = false;      // among the general-route streams: compressed by k_ekf_tsqr / by the Gram factorisation
-    int max_feat_pairs = 0;
-    double fl_feat = 0, fl_qr = 0, fl_upd = 0;   // algorithmic FP64 flops of this launch
-    struct Lay { size_t clones, feats, obs_clone, obs_z, tri; int n_tri; size_t o_dx, o_gamma, o_rows, o_status, o_pos; int m_total; };
-    bool any_pv_nofeat = false;
-    std::vector<Lay> lay(n);
-    size_t in_bytes = 0, out_bytes = 0;
+// ---------------------------------------------------------------------------------------------- measurement update
+// mskf_ekf_update_batch_begin in four steps: plan_update looks at the whole batch and decides everything, touching nothing;
+// grow_stacks, pack_update and enqueue_update then carry the plan out.
+// What the batch as a whole needs (the per-stream part is EkfUpdatePlan, mskf_internal.h)
+struct UpdateBatchPlan {
+    bool any_pairs, any_small, any_general;
+    bool any_householder, any_gram;      // among the general-route streams: compressed by k_ekf_tsqr / by the Gram factorisation
+    bool any_pv_nofeat;                  // a stream without features wants its position variances
+    int max_feat, max_d, max_clones_cfg;
+    int max_frows, max_frows_small;      // block rows (4 n_obs) of the largest feature / of the largest one in the small class's list
+    int max_feat_pairs, max_tri;         // over the pair-route streams
+    int n_work[3];                       // entries of the three work lists of the feature kernel
+    size_t work_off, in_bytes, out_bytes;
+    double fl_feat, fl_qr, fl_upd;       // algorithmic FP64 flops of this launch
+};
+// flops of a stream's Kalman update per d^3: downdate 4, a factorisation 1/3, T, S and the solve 2 each
+constexpr double kUpdFlopsPerD3 = 4.0 + 1.0 / 3.0 + 2.0 + 2.0 + 2.0;
+
+// Which kernels handle a stream is decided per STREAM, from that stream's features alone (EkfStreamDev::route): the same
+// stream takes the same route, and therefore runs the same arithmetic, whatever else is in the batch.
+//   pairs : every feature has exactly two Jacobian observations, all of the same ordered clone pair (the pruning update)
+//   wave  : every feature has <= FEAT_WAVE_CLONES Jacobian observations and a triangulation over <= TRI_SMALL_CLONES clones:
+//           list [0] of the feature kernel, one wavefront per feature; otherwise a feature is in list [1]
+//           (<= FEAT_SMALL_CLONES observations and triangulation clones) or [2]
+//   small : the stream touches at most SU_MAX_NA / 6 clones: whole update in k_ekf_small_update
+static int plan_stream(const mskf_ctx *ctx, const mskf_stream *s, const mskf_ekf_update_args &a, EkfUpdatePlan &L, UpdateBatchPlan &B) {
+    if (!s || s->ctx_ekf != ctx) return MSKF_ERR_INVALID;
+    const EkfStreamState &E = s->ekf_state;
+    if (a.n_clones * 6 + EKF_IMU_DIM != E.d) { mskf_set_error("n_clones does not match the covariance dimension"); return MSKF_ERR_INVALID; }
+    if (a.n_feat < 0 || a.n_obs < 0) return MSKF_ERR_INVALID;
+    if (a.n_feat && (!a.clones || !a.features || !a.obs_clone || !a.obs_z || !a.delta_x || !a.feat_status || !a.rows_out)) return MSKF_ERR_INVALID;
+    L = EkfUpdatePlan{};
+    unsigned long long clone_mask = 0ULL;          // clones any Jacobian block of this stream touches: bounds the active columns
+    bool pairs = a.n_feat > 0, wave = a.n_feat > 0;
+    int pair_a = -1, pair_b = -1, frows_cls[3] = {0, 0, 0};
+    for (int j = 0; j < a.n_feat; ++j) {
+        const mskf_ekf_feature &f = a.features[j];
+        L.n_tri += f.needs_init ? 1 : 0;
+        if (f.n_obs < 2 || f.n_obs > E.max_clones || f.obs_start < 0 || f.obs_start + f.n_obs > a.n_obs) return MSKF_ERR_INVALID;
+        if (f.needs_init && (f.n_init < 1 || f.n_init > E.max_clones || f.init_start < 0 || f.init_start + f.n_init > a.n_obs)) return MSKF_ERR_INVALID;
+        if (f.n_obs != 2) pairs = false;
+        else if (pairs) {
+            // the pair kernel keeps the two clones' blocks in the order (lower, higher) and shares their covariance
+            // block among the features: both observations distinct, ascending, and the same pair for every feature
+            const int c0 = a.obs_clone[f.obs_start], c1 = a.obs_clone[f.obs_start + 1];
+            if (j == 0) { pair_a = c0; pair_b = c1; }
+            if (!(c0 < c1) || c0 != pair_a || c1 != pair_b) pairs = false;
+        }
+        if (f.n_obs > FEAT_WAVE_CLONES || (f.needs_init && f.n_init > TRI_SMALL_CLONES)) wave = false;
+        L.m_total += 4 * f.n_obs - 3;
+        B.max_frows = std::max(B.max_frows, 4 * f.n_obs);
+        const int cls = std::max(f.n_obs, f.needs_init ? f.n_init : 0) <= FEAT_SMALL_CLONES ? 1 : 2;
+        frows_cls[cls] = std::max(frows_cls[cls], 4 * f.n_obs);
+        ++L.cnt[cls];
+        for (int o = 0; o < f.n_obs; ++o) {
+            const int c = a.obs_clone[f.obs_start + o];
+            if (c < 0 || c >= a.n_clones) return MSKF_ERR_INVALID;
+            clone_mask |= 1ULL << c;
+        }
+        const double nj = 4.0 * f.n_obs - 3.0, M = f.n_obs, dd = E.d;
+        B.fl_feat += 2.0 * nj * (4.0 * M) * (6.0 * M) + 2.0 * nj * dd * dd + 2.0 * nj * nj * dd;
+    }
+    if (L.m_total > kMaxRows) { mskf_set_error("stacked Jacobian exceeds the row capacity"); return MSKF_ERR_CAPACITY; }
+    L.clones = B.in_bytes;
+    L.feats = align_up(L.clones + sizeof(mskf_clone_state) * (size_t)a.n_clones, 16);
+    L.obs_clone = align_up(L.feats + sizeof(EkfFeatDev) * (size_t)a.n_feat, 16);
+    L.obs_z = align_up(L.obs_clone + sizeof(int) * (size_t)a.n_obs, 16);
+    L.tri = align_up(L.obs_z + sizeof(double) * 4 * (size_t)a.n_obs, 16);
+    B.in_bytes = align_up(L.tri + sizeof(int) * (size_t)L.n_tri, 64);
+    L.o_dx = B.out_bytes;
+    L.o_gamma = align_up(L.o_dx + sizeof(double) * (size_t)E.ld, 16);
+    L.o_pos = align_up(L.o_gamma + sizeof(double) * (size_t)a.n_feat, 16);
+    L.o_rows = align_up(L.o_pos + sizeof(double) * 3 * (size_t)a.n_feat, 16);
+    L.o_status = L.o_rows + 32 + 32;           // rows_out (5 ints, padded to 32 bytes) + 3 position variances
+    B.out_bytes = align_up(L.o_status + (size_t)a.n_feat, 64);
+    B.any_pv_nofeat |= a.pos_var_out != nullptr && a.n_feat == 0;
+    // (the first block is sized for what a stream of this configuration can stack, mskf_ekf_stream_init: growth is rare)
+    if (L.m_total > E.max_rows) L.grow_rows = std::min(kMaxRows, std::max(2048, L.m_total + L.m_total / 2));
+    if (a.n_feat > 0) {
+        const double dd = E.d, mm = L.m_total;
+        if (L.m_total > E.d) B.fl_qr += 2.0 * mm * dd * dd - (2.0 / 3.0) * dd * dd * dd;
+        B.fl_upd += kUpdFlopsPerD3 * dd * dd * dd;
+        if (pairs) wave = false;
+        L.na_max = 6 * __builtin_popcountll(clone_mask);
+        const bool small = L.na_max <= SU_MAX_NA;
+        L.route = (pairs ? EKF_ROUTE_PAIRS : 0) | (wave ? EKF_ROUTE_WAVE : 0) | (small ? EKF_ROUTE_SMALL : 0);
+        B.any_pairs |= pairs; B.any_small |= small; B.any_general |= !small;
+        if (!small) { const bool hh = ekf_mode_householder(s->ekf.compression_mode); B.any_householder |= hh; B.any_gram |= !hh; }
+        if (pairs) { B.max_feat_pairs = std::max(B.max_feat_pairs, a.n_feat); B.max_tri = std::max(B.max_tri, L.n_tri); }
+        if (pairs || wave) {
+            // the whole stream is list [0] (wave) or handled by the pair kernels: none of its features in [1] / [2]
+            L.cnt[0] = pairs ? 0 : L.cnt[1] + L.cnt[2];
+            L.cnt[1] = L.cnt[2] = 0;
+        } else B.max_frows_small = std::max(B.max_frows_small, frows_cls[1]);
+    }
+    B.max_clones_cfg = std::max(B.max_clones_cfg, E.max_clones);
+    B.max_feat = std::max(B.max_feat, a.n_feat);
+    B.max_d = std::max(B.max_d, E.d);
+    return MSKF_OK;
+}
+
+// Validates every stream and feature of the batch and fills plan[0..n) and B.  No HIP call, and nothing but the plan is
+// written: a batch that is refused for its last stream has not touched the first.
+static int plan_update(const mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_ekf_update_args *args, EkfUpdatePlan *plan, UpdateBatchPlan &B) {
+    B = UpdateBatchPlan{};
     for (int i = 0; i < n; ++i) {
-        mskf_stream *s = streams[i];
-        mskf_ekf_update_args &a = args[i];
-        if (!s || s->ctx_ekf != ctx) return MSKF_ERR_INVALID;
-        EkfStreamState &E = s->ekf_state;
-        if (a.n_clones * 6 + EKF_IMU_DIM != E.d) { mskf_set_error("n_clones does not match the covariance dimension"); return MSKF_ERR_INVALID; }
-        if (a.n_feat < 0 || a.n_obs < 0) return MSKF_ERR_INVALID;
-        if (a.n_feat && (!a.clones || !a.features || !a.obs_clone || !a.obs_z || !a.delta_x || !a.feat_status || !a.rows_out)) return MSKF_ERR_INVALID;
-        Lay &L = lay[i];
-        int m_total = 0;
-        unsigned long long clone_mask = 0ULL;          // clones any Jacobian block of this stream touches: bounds the active columns
-        int n_tri = 0;
-        bool pairs = a.n_feat > 0, wave = a.n_feat > 0;
-        int pair_a = -1, pair_b = -1, s_frows_cls[3] = {0, 0, 0};
-        for (int j = 0; j < a.n_feat; ++j) {
-            const mskf_ekf_feature &f = a.features[j];
-            n_tri += f.needs_init ? 1 : 0;
-            if (f.n_obs < 2 || f.n_obs > E.max_clones || f.obs_start < 0 || f.obs_start + f.n_obs > a.n_obs) return MSKF_ERR_INVALID;
-            if (f.needs_init && (f.n_init < 1 || f.n_init > E.max_clones || f.init_start < 0 || f.init_start + f.n_init > a.n_obs)) return MSKF_ERR_INVALID;
-            if (f.n_obs != 2) pairs = false;
-            else if (pairs) {
-                // the pair kernel keeps the two clones' blocks in the order (lower, higher) and shares their covariance
-                // block among the features: both observations distinct, ascending, and the same pair for every feature
-                const int c0 = a.obs_clone[f.obs_start], c1 = a.obs_clone[f.obs_start + 1];
-                if (j == 0) { pair_a = c0; pair_b = c1; }
-                if (!(c0 < c1) || c0 != pair_a || c1 != pair_b) pairs = false;
-            }
-            if (4 * f.n_obs > 16 || (f.needs_init && f.n_init > 32)) wave = false;      // (TRI_SMALL_CLONES)
-            m_total += 4 * f.n_obs - 3;
-            max_frows = std::max(max_frows, 4 * f.n_obs);
-            {
-                const int cls_n = std::max(f.n_obs, f.needs_init ? f.n_init : 0), cls = cls_n <= 16 ? 1 : 2;
-                s_frows_cls[cls] = std::max(s_frows_cls[cls], 4 * f.n_obs);
-                ++cnt_cls[(size_t)cls * n + i];
-            }
-            for (int o = 0; o < f.n_obs; ++o) {
-                const int c = a.obs_clone[f.obs_start + o];
-                if (c < 0 || c >= a.n_clones) return MSKF_ERR_INVALID;
-                clone_mask |= 1ULL << c;
-            }
-            const double nj = 4.0 * f.n_obs - 3.0, M = f.n_obs, dd = E.d;
-            fl_feat += 2.0 * nj * (4.0 * M) * (6.0 * M) + 2.0 * nj * dd * dd + 2.0 * nj * nj * dd;
-        }
-        if (a.n_feat > 0) {
-            const double dd = E.d, mm = m_total;
-            if (m_total > E.d) fl_qr += 2.0 * mm * dd * dd - (2.0 / 3.0) * dd * dd * dd;
-            fl_upd += (4.0 + 1.0 / 3.0 + 2.0 + 2.0 + 2.0) * dd * dd * dd;
-        }
-        if (m_total > kMaxRows) { mskf_set_error("stacked Jacobian exceeds the row capacity"); return MSKF_ERR_CAPACITY; }
-        L.m_total = m_total;
-        L.clones = in_bytes;
-        L.feats = align_up(L.clones + sizeof(mskf_clone_state) * (size_t)a.n_clones, 16);
-        L.obs_clone = align_up(L.feats + sizeof(EkfFeatDev) * (size_t)a.n_feat, 16);
-        L.obs_z = align_up(L.obs_clone + sizeof(int) * (size_t)a.n_obs, 16);
-        L.tri = align_up(L.obs_z + sizeof(double) * 4 * (size_t)a.n_obs, 16);
-        in_bytes = align_up(L.tri + sizeof(int) * (size_t)n_tri, 64);
-        L.o_dx = out_bytes;
-        L.o_gamma = align_up(L.o_dx + sizeof(double) * (size_t)E.ld, 16);
-        L.o_pos = align_up(L.o_gamma + sizeof(double) * (size_t)a.n_feat, 16);
-        L.o_rows = align_up(L.o_pos + sizeof(double) * 3 * (size_t)a.n_feat, 16);
-        L.o_status = L.o_rows + 32 + 32;           // rows_out (5 ints, padded to 32 bytes) + 3 position variances
-        any_pv_nofeat |= a.pos_var_out != nullptr && a.n_feat == 0;
-        out_bytes = align_up(L.o_status + (size_t)a.n_feat, 64);
-        if (m_total > E.max_rows) {
-            // Growth of the stacked-Jacobian buffer, STREAM-ORDERED: hipFree / hipMalloc synchronise the whole device, and a
-            // group that grows a buffer in the middle of a run then waits until every other group's queue is idle (measured in
-            // the round-3 bench: the two groups that met their largest pruning update inside the timed window stood still for
-            // 0.3 s each).  The first allocation is sized for what a stream of this configuration can stack (stream init).
-            // The new block is allocated FIRST: if that fails the call fails with the stream's buffers as they were (a later,
-            // smaller update still finds a valid Hs of max_rows rows).  The old block goes back to the pool it came from: a
-            // stream-ordered free for a stream-ordered block, retirement until the stream is destroyed for the first one
-            // (hipMalloc'ed at stream creation; hipFreeAsync does not take such a pointer without a device-wide wait).
-            const int cap = std::min(kMaxRows, std::max(2048, m_total + m_total / 2));
-            const size_t bytes = ((size_t)cap * E.ld + (size_t)cap) * sizeof(double);
-            double *grown = nullptr;
-            drain.armed = true;
-            MSKF_HIPCHK(hipMallocAsync((void **)&grown, bytes, st));
-            if (hipMemsetAsync(grown, 0, bytes, st) != hipSuccess) { (void)hipFreeAsync(grown, st); mskf_set_error("hipMemsetAsync of the grown stacked-Jacobian buffer failed"); return MSKF_ERR_HIP; }
-            if (E.Hs) { if (E.hs_async) (void)hipFreeAsync(E.Hs, st); else extra_of(s)->retired_hs.push_back(E.Hs); }      // (rs lives behind Hs in the same allocation)
-            E.Hs = grown;
-            E.rs = E.Hs + (size_t)cap * E.ld;
-            E.max_rows = cap;
-            E.hs_async = true;
-        }
-        if (a.n_feat > 0) {
-            if (pairs) wave = false;
-            const bool small = 6 * __builtin_popcountll(clone_mask) <= ekf_small_update_max_na();
-            route[i] = (pairs ? 1 : 0) | (wave ? 2 : 0) | (small ? 4 : 0);
-            na_max[i] = 6 * __builtin_popcountll(clone_mask);
-            any_pairs |= pairs; any_small |= small; any_general |= !small;
-            if (!small) { const bool hh = s->ekf.compression_mode == 2 || s->ekf.compression_mode == 3; any_householder |= hh; any_gram |= !hh; }
-            if (pairs) { max_feat_pairs = std::max(max_feat_pairs, a.n_feat); max_tri = std::max(max_tri, n_tri); }
-            if (pairs || wave) {
-                // the whole stream is class [0] (wave) or handled by the pair kernels: none of its features in [1] / [2]
-                cnt_cls[i] = pairs ? 0 : cnt_cls[(size_t)n + i] + cnt_cls[(size_t)2 * n + i];
-                cnt_cls[(size_t)n + i] = 0; cnt_cls[(size_t)2 * n + i] = 0;
-            } else {
-                for (int c = 1; c < 3; ++c) max_frows_cls[c] = std::max(max_frows_cls[c], s_frows_cls[c]);
-            }
-        }
-        max_clones_cfg = std::max(max_clones_cfg, E.max_clones);
-        L.n_tri = n_tri;
-        max_feat = std::max(max_feat, a.n_feat);
-        max_m = std::max(max_m, m_total);
-        max_d = std::max(max_d, E.d);
+        const int rc = plan_stream(ctx, streams[i], args[i], plan[i], B);
+        if (rc != MSKF_OK) return rc;
     }
     // work lists: stream << 16 | slot << 8 | n_slots per feature group in flight
     if (n > 0xffff) { mskf_set_error("too many streams in one update batch"); return MSKF_ERR_CAPACITY; }
-    int n_work[3] = {0, 0, 0};
-    for (int c = 0; c < 3; ++c) for (int i = 0; i < n; ++i) n_work[c] += std::min(cnt_cls[(size_t)c * n + i], EKF_SLOTS);
-    const size_t work_off = in_bytes;
-    in_bytes = align_up(in_bytes + sizeof(int) * (size_t)(n_work[0] + n_work[1] + n_work[2]), 64);
-    if ((rc = ctx->upd_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->upd_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    char *hin = ctx->upd_in.h, *din = ctx->upd_in.d, *hout = ctx->upd_out.h, *dout = ctx->upd_out.d;
-    {
-        int *w = (int *)(hin + work_off);
-        for (int c = 0; c < 3; ++c)
-            for (int i = 0; i < n; ++i) {
-                const int ns = std::min(cnt_cls[(size_t)c * n + i], EKF_SLOTS);
-                for (int k = 0; k < ns; ++k) *w++ = (i << 16) | (k << 8) | ns;
-            }
-    }
+    for (int c = 0; c < 3; ++c) for (int i = 0; i < n; ++i) B.n_work[c] += std::min(plan[i].cnt[c], EKF_SLOTS);
+    B.work_off = B.in_bytes;
+    B.in_bytes = align_up(B.in_bytes + sizeof(int) * (size_t)(B.n_work[0] + B.n_work[1] + B.n_work[2]), 64);
+    return MSKF_OK;
+}
+
+// Growth of the stacked-Jacobian buffer of the streams the plan marked, STREAM-ORDERED: hipFree / hipMalloc synchronise the
+// whole device, and a group that grows a buffer in the middle of a run then waits until every other group's queue is idle
+// (measured in the round-3 bench: the two groups that met their largest pruning update inside the timed window stood still
+// for 0.3 s each).
+// The new block is allocated FIRST: if that fails the call fails with the stream's buffers as they were (a later, smaller
+// update still finds a valid Hs of max_rows rows).  The old block goes back to the pool it came from: a stream-ordered free
+// for a stream-ordered block, retirement until the stream is destroyed for the first one (hipMalloc'ed at stream creation;
+// hipFreeAsync does not take such a pointer without a device-wide wait).
+static int grow_stacks(int n, mskf_stream *const *streams, const EkfUpdatePlan *plan, hipStream_t st) {
     for (int i = 0; i < n; ++i) {
-        mskf_stream *s = streams[i];
-        mskf_ekf_update_args &a = args[i];
-        const Lay &L = lay[i];
+        EkfStreamState &E = streams[i]->ekf_state;
+        const int cap = plan[i].grow_rows;
+        if (cap <= E.max_rows) continue;
+        const size_t bytes = ((size_t)cap * E.ld + (size_t)cap) * sizeof(double);
+        double *grown = nullptr;
+        MSKF_HIPCHK(hipMallocAsync((void **)&grown, bytes, st));
+        if (hipMemsetAsync(grown, 0, bytes, st) != hipSuccess) { (void)hipFreeAsync(grown, st); mskf_set_error("hipMemsetAsync of the grown stacked-Jacobian buffer failed"); return MSKF_ERR_HIP; }
+        if (E.Hs) { if (E.hs_async) (void)hipFreeAsync(E.Hs, st); else extra_of(streams[i])->retired_hs.push_back(E.Hs); }      // (rs lives behind Hs in the same allocation)
+        E.Hs = grown;
+        E.rs = E.Hs + (size_t)cap * E.ld;
+        E.max_rows = cap;
+        E.hs_async = true;
+    }
+    return MSKF_OK;
+}
+
+// The batch's inputs into upd_in (per stream: clone states, features, observations, triangulation list; then the three
+// work lists) and its descriptors into ekf_desc, host side.
+static void pack_update(mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_ekf_update_args *args, const EkfUpdatePlan *plan, const UpdateBatchPlan &B) {
+    char *hin = ctx->upd_in.h, *din = ctx->upd_in.d, *dout = ctx->upd_out.d;
+    int *w = (int *)(hin + B.work_off);
+    for (int c = 0; c < 3; ++c)
+        for (int i = 0; i < n; ++i) {
+            const int ns = std::min(plan[i].cnt[c], EKF_SLOTS);
+            for (int k = 0; k < ns; ++k) *w++ = (i << 16) | (k << 8) | ns;
+        }
+    for (int i = 0; i < n; ++i) {
+        const mskf_ekf_update_args &a = args[i];
+        const EkfUpdatePlan &L = plan[i];
         if (a.n_clones) std::memcpy(hin + L.clones, a.clones, sizeof(mskf_clone_state) * (size_t)a.n_clones);
         EkfFeatDev *fd = (EkfFeatDev *)(hin + L.feats);
         int *tri = (int *)(hin + L.tri);
-        int n_tri_w = 0;
-        int row = 0;
+        int n_tri_w = 0, row = 0;
         for (int j = 0; j < a.n_feat; ++j) {
             const mskf_ekf_feature &f = a.features[j];
             fd[j].obs_start = f.obs_start; fd[j].n_obs = f.n_obs;
@@ -559,9 +542,9 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
             std::memcpy(hin + L.obs_z, a.obs_z, sizeof(double) * 4 * (size_t)a.n_obs);
         }
         EkfStreamDev &D = ctx->ekf_desc.h[i];
-        base_desc(s, D);
+        base_desc(streams[i], D);
         D.n_clones = a.n_clones; D.n_feat = a.n_feat; D.n_obs = a.n_obs;
-        D.route = route[i]; D.na_max = na_max[i];
+        D.route = L.route; D.na_max = L.na_max;
         D.dof_offset = a.dof_offset; D.apply_row_cap = a.apply_row_cap;
         D.m_total = L.m_total;
         for (int k = 0; k < 3; ++k) D.gravity[k] = a.gravity[k];
@@ -578,86 +561,76 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
         D.pos_var_out = a.pos_var_out ? (double *)(dout + L.o_rows + 32) : nullptr;
         D.feat_status = (uint8_t *)(dout + L.o_status);
     }
-    if (max_feat > 0) {
-        {
-            drain.armed = true;
-            const MskfCopy cp[2] = {{din, hin, in_bytes}, {ctx->ekf_desc.d, ctx->ekf_desc.h, sizeof(EkfStreamDev) * (size_t)n}};
-            if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
-        }
-        int ts = mskf_t_begin(ctx, MSKF_K_EKF_FEATURES);
-        if (any_pairs) ekf_launch_pair_features(ctx->ekf_desc.d, n, max_feat_pairs, max_tri, st);      // the pruning update
-        if (n_work[0] + n_work[1] + n_work[2] > 0) {
-            const int *w0 = (const int *)(din + work_off);
-            ekf_launch_features(ctx->ekf_desc.d, w0, n_work[0], w0 + n_work[0], n_work[1], w0 + n_work[0] + n_work[1], n_work[2], max_frows,
-                                max_frows_cls[1], max_clones_cfg, st);
-        }
-        mskf_t_end(ctx, ts, (long long)fl_feat);
-        // (which blocks are stacked - the 1500-row cap of :1002-1010 - is worked out by the first dense kernel of each route
-        //  itself: ekf_cap.h; rounds 1-3 ran it as a launch of its own here)
-        enum { GM_GRAM = 0, GM_T = 1, GM_S2 = 2, GM_PUPD = 3 };
-        const double d3 = fl_upd / (4.0 + 1.0 / 3.0 + 2.0 + 2.0 + 2.0);     // sum of d^3 over the launch
-        if (any_small) {
-            // streams that stack blocks of at most four clones (the pruning update: the two clones being removed):
-            // compression, gain and Y in one launch (k_ekf_small_update); the other streams leave it at once
-            ts = mskf_t_begin(ctx, MSKF_K_EKF_SMALL);
-            ekf_launch_small_update(ctx->ekf_desc.d, n, max_d, st);
-            mskf_t_end(ctx, ts, any_general ? 0 : (long long)(fl_qr + fl_upd));
-        }
-        if (any_general) {
-            // QR compression as Gram + semidefinite Cholesky (Householder TSQR inside the factorisation kernel for the
-            // streams that need it), then the Kalman update (ekf_linalg.hip); small-route streams leave these at once
-            if (any_gram) {
-                // (also the first dense kernel of the general route: its tiles work out the stacking decision for every stream)
-                ts = mskf_t_begin(ctx, MSKF_K_EKF_GEMM);
-                ekf_launch_gemm(ctx->ekf_desc.d, n, GM_GRAM, max_d + 1, st);
-                mskf_t_end(ctx, ts, (long long)fl_qr);
-            }
-            if (any_householder) {
-                // Householder TSQR of the streams in compression_mode 2 / 3 (a kernel without LDS of its own: ekf_linalg.hip); with no
-                // Gram launch before it, it is the first dense kernel and makes the stacking decision itself
-                ts = mskf_t_begin(ctx, MSKF_K_EKF_TSQR);
-                ekf_launch_tsqr(ctx->ekf_desc.d, n, max_d, any_gram ? 0 : 1, st);
-                mskf_t_end(ctx, ts, (long long)fl_qr);
-            }
-            if (any_gram) {
-                ts = mskf_t_begin(ctx, MSKF_K_EKF_CHOL);
-                ekf_launch_chol(ctx->ekf_desc.d, n, 0, max_d, st);
-                mskf_t_end(ctx, ts, (long long)(d3 / 3.0));
-            }
-            ts = mskf_t_begin(ctx, MSKF_K_EKF_GEMM);
-            ekf_launch_gemm(ctx->ekf_desc.d, n, GM_T, max_d, st);
-            mskf_t_end(ctx, ts, (long long)(2.0 * d3));
-            ts = mskf_t_begin(ctx, MSKF_K_EKF_GEMM);
-            ekf_launch_gemm(ctx->ekf_desc.d, n, GM_S2, max_d, st);
-            mskf_t_end(ctx, ts, (long long)(2.0 * d3));
-            ts = mskf_t_begin(ctx, MSKF_K_EKF_CHOL);
-            ekf_launch_chol(ctx->ekf_desc.d, n, 1, max_d, st);
-            mskf_t_end(ctx, ts, (long long)(d3 / 3.0));
-            ts = mskf_t_begin(ctx, MSKF_K_EKF_TRSM);
-            ekf_launch_trsm(ctx->ekf_desc.d, n, max_d, st);
-            mskf_t_end(ctx, ts, (long long)(2.0 * d3));
-        }
-        // P <- P - Y^T Y and delta_x = Y^T w for every stream, whichever route produced Y
-        ts = mskf_t_begin(ctx, MSKF_K_EKF_GEMM);
-        ekf_launch_gemm(ctx->ekf_desc.d, n, GM_PUPD, max_d, st);
-        mskf_t_end(ctx, ts, any_general ? (long long)(4.0 * d3) : 0);
-        if (any_pv_nofeat) ekf_launch_posvar_upd(ctx->ekf_desc.d, n, st);       // (streams with features get theirs from the downdate's epilogue)
-        (void)max_m;
-        MSKF_HIPCHK(hipGetLastError());
-        { const MskfCopy cp = {hout, dout, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
+}
+
+// One timed launch (mskf_t_begin / mskf_t_end around it)
+#define EKF_TIMED(kind, units, launch) do { const int ts_ = mskf_t_begin(ctx, kind); launch; mskf_t_end(ctx, ts_, (long long)(units)); } while (0)
+
+// Staging copy in, the launch chain, result copy out.  A launch set is enqueued when some stream of the batch needs it; the
+// streams of the other routes leave those kernels at once.
+static int enqueue_update(mskf_ctx *ctx, int n, const UpdateBatchPlan &B) {
+    hipStream_t st = ctx->stream;
+    const EkfStreamDev *D = ctx->ekf_desc.d;
+    const MskfCopy in[2] = {{ctx->upd_in.d, ctx->upd_in.h, B.in_bytes}, {ctx->ekf_desc.d, ctx->ekf_desc.h, sizeof(EkfStreamDev) * (size_t)n}};
+    const int rc = mskf_copy_async(ctx, in, 2);
+    if (rc != MSKF_OK) return rc;
+    const int ts = mskf_t_begin(ctx, MSKF_K_EKF_FEATURES);
+    if (B.any_pairs) ekf_launch_pair_features(D, n, B.max_feat_pairs, B.max_tri, st);      // the pruning update
+    if (B.n_work[0] + B.n_work[1] + B.n_work[2] > 0) {
+        const int *w0 = (const int *)(ctx->upd_in.d + B.work_off);
+        ekf_launch_features(D, w0, B.n_work[0], w0 + B.n_work[0], B.n_work[1], w0 + B.n_work[0] + B.n_work[1], B.n_work[2], B.max_frows,
+                            B.max_frows_small, B.max_clones_cfg, st);
     }
-    {
-        mskf_ctx::PendingUpdate &U = ctx->pend_upd;
-        U.launched = max_feat > 0; U.n = n; U.streams = streams; U.args = args;
-        U.lay.resize((size_t)5 * n);
-        for (int i = 0; i < n; ++i) {
-            U.lay[5 * i] = lay[i].o_dx; U.lay[5 * i + 1] = lay[i].o_gamma; U.lay[5 * i + 2] = lay[i].o_rows;
-            U.lay[5 * i + 3] = lay[i].o_status; U.lay[5 * i + 4] = lay[i].o_pos;
-        }
-        if (!U.launched) U.active = true;            // nothing launched, no mark: _end only fills the outputs
-        else if ((rc = mskf_batch_arm(ctx, U)) != MSKF_OK) return rc;
-        drain.armed = false;
+    mskf_t_end(ctx, ts, (long long)B.fl_feat);
+    // (which blocks are stacked - the 1500-row cap of :1002-1010 - is worked out by the first dense kernel of each route
+    //  itself: ekf_cap.h; rounds 1-3 ran it as a launch of its own here)
+    const double d3 = B.fl_upd / kUpdFlopsPerD3;     // sum of d^3 over the launch
+    const int max_d = B.max_d;
+    // streams that stack blocks of at most four clones (the pruning update: the two clones being removed):
+    // compression, gain and Y in one launch (k_ekf_small_update); the other streams leave it at once
+    if (B.any_small) EKF_TIMED(MSKF_K_EKF_SMALL, B.any_general ? 0 : B.fl_qr + B.fl_upd, ekf_launch_small_update(D, n, max_d, st));
+    if (B.any_general) {
+        // QR compression as Gram + semidefinite Cholesky (Householder TSQR inside the factorisation kernel for the
+        // streams that need it), then the Kalman update (ekf_linalg.hip); small-route streams leave these at once
+        // (GRAM is also the first dense kernel of the general route: its tiles work out the stacking decision for every stream)
+        if (B.any_gram) EKF_TIMED(MSKF_K_EKF_GEMM, B.fl_qr, ekf_launch_gemm(D, n, GM_GRAM, max_d + 1, st));
+        // Householder TSQR of the streams in compression_mode 2 / 3 (a kernel without LDS of its own: ekf_linalg.hip); with no
+        // Gram launch before it, it is the first dense kernel and makes the stacking decision itself
+        if (B.any_householder) EKF_TIMED(MSKF_K_EKF_TSQR, B.fl_qr, ekf_launch_tsqr(D, n, max_d, B.any_gram ? 0 : 1, st));
+        if (B.any_gram) EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 0, max_d, st));
+        EKF_TIMED(MSKF_K_EKF_GEMM, 2.0 * d3, ekf_launch_gemm(D, n, GM_T, max_d, st));
+        EKF_TIMED(MSKF_K_EKF_GEMM, 2.0 * d3, ekf_launch_gemm(D, n, GM_S2, max_d, st));
+        EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 1, max_d, st));
+        EKF_TIMED(MSKF_K_EKF_TRSM, 2.0 * d3, ekf_launch_trsm(D, n, max_d, st));
     }
+    // P <- P - Y^T Y and delta_x = Y^T w for every stream, whichever route produced Y
+    EKF_TIMED(MSKF_K_EKF_GEMM, B.any_general ? 4.0 * d3 : 0, ekf_launch_gemm(D, n, GM_PUPD, max_d, st));
+    if (B.any_pv_nofeat) ekf_launch_posvar_upd(D, n, st);       // (streams with features get theirs from the downdate's epilogue)
+    MSKF_HIPCHK(hipGetLastError());
+    const MskfCopy out = {ctx->upd_out.h, ctx->upd_out.d, B.out_bytes};
+    return mskf_copy_async(ctx, &out, 1);
+}
+#undef EKF_TIMED
+
+extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_update_args *args) {
+    if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);
+    if (rc != MSKF_OK) return rc;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    const auto t_h0 = std::chrono::steady_clock::now();
+    mskf_ctx::PendingUpdate &U = ctx->pend_upd;
+    U.plan.resize((size_t)n);
+    UpdateBatchPlan B;
+    if ((rc = plan_update(ctx, n, streams, args, U.plan.data(), B)) != MSKF_OK) return rc;
+    if ((rc = ctx->ekf_desc.ensure(n)) != MSKF_OK || (rc = ctx->upd_in.ensure(B.in_bytes)) != MSKF_OK || (rc = ctx->upd_out.ensure(B.out_bytes)) != MSKF_OK) return rc;
+    // the batch is accepted: from here on work is enqueued, and a failure drains the stream before it is reported
+    DrainOnError drain{ctx->stream, true};
+    if ((rc = grow_stacks(n, streams, U.plan.data(), ctx->stream)) != MSKF_OK) return rc;
+    pack_update(ctx, n, streams, args, U.plan.data(), B);
+    U.launched = B.max_feat > 0; U.n = n; U.streams = streams; U.args = args;
+    if (!U.launched) U.active = true;            // nothing launched, no mark: _end only fills the outputs
+    else if ((rc = enqueue_update(ctx, n, B)) != MSKF_OK || (rc = mskf_batch_arm(ctx, U)) != MSKF_OK) return rc;
+    drain.armed = false;
     if (ctx->t_gate) ctx->host_s[0] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
 }
@@ -680,13 +653,10 @@ extern "C" int mskf_ekf_update_batch_end(mskf_ctx *ctx) {
     mskf_stream *const *streams = U.streams;
     mskf_ekf_update_args *args = U.args;
     const char *hout = ctx->upd_out.h;
-    struct LayOut { size_t o_dx, o_gamma, o_rows, o_status, o_pos; };
-    std::vector<LayOut> lay(n);
-    for (int i = 0; i < n; ++i) lay[i] = LayOut{U.lay[5 * i], U.lay[5 * i + 1], U.lay[5 * i + 2], U.lay[5 * i + 3], U.lay[5 * i + 4]};
     for (int i = 0; i < n; ++i) {
         mskf_ekf_update_args &a = args[i];
         EkfStreamState &E = streams[i]->ekf_state;
-        const LayOut &L = lay[i];
+        const EkfUpdatePlan &L = U.plan[i];
         const int d = E.d;
         if (a.pos_var_out) {
             if (U.launched) std::memcpy(a.pos_var_out, hout + L.o_rows + 32, sizeof(double) * 3);

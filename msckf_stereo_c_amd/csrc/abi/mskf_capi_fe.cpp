@@ -767,7 +767,7 @@ extern "C" int mskf_fe_track_batch_end(mskf_ctx *ctx) {
     const std::vector<size_t> &out_off = ctx->pend_trk.out_off;
     const int ts = ctx->pend_trk.ts;
     const auto t_h1 = std::chrono::steady_clock::now();
-    long long tracks_t = 0, tracks_s = 0, pts = 0;
+    long long tracks_t = 0, tracks_s = 0;
     for (int i = 0; i < n; ++i) {
         const mskf_fe_track_args &a = args[i];
         const size_t np = (size_t)a.n;
@@ -780,12 +780,10 @@ extern "C" int mskf_fe_track_batch_end(mskf_ctx *ctx) {
         std::memcpy(a.status, o + 4 * sizeof(mskf_point2f) * np, np);
         // units of an LK launch = point tracks it executed: temporal (n of the temporal streams), stereo (the points that
         // passed the temporal gate, or all n of a stereo-only stream)
-        pts += (long long)np;
         if (a.do_temporal) { tracks_t += (long long)np; for (size_t k = 0; k < np; ++k) tracks_s += (a.status[k] & 1); }
         else tracks_s += (long long)np;
     }
     mskf_t_set_units(ctx, ts, MSKF_K_LK, tracks_t + tracks_s);      // point tracks of the launch: temporal + stereo
-    (void)pts;
     mskf_t_collect(ctx);
     if (ctx->t_gate) ctx->host_s[3] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h1).count();
     return MSKF_OK;

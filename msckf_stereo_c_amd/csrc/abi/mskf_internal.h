@@ -112,6 +112,17 @@ struct DrainOnError {
     ~DrainOnError() { if (armed) (void)hipStreamSynchronize(st); }     // (its result is ignored: the original error is returned)
 };
 
+// What mskf_ekf_update_batch_begin decided about one stream of a batch before it touched anything (plan_update,
+// mskf_capi_ekf.cpp); mskf_ekf_update_batch_end finds the stream's results through the output offsets.
+struct EkfUpdatePlan {
+    int route, na_max;                                // EkfStreamDev::route, ::na_max
+    int m_total, n_tri;
+    int cnt[3];                                       // features per work list of the feature kernel: [0] wave, [1] small, [2] big class
+    int grow_rows;                                    // > 0: the stack does not fit Hs, which grows to this many rows before the batch runs
+    size_t clones, feats, obs_clone, obs_z, tri;      // byte offsets of the stream's inputs in upd_in
+    size_t o_dx, o_gamma, o_pos, o_rows, o_status;    // ... and of its results in upd_out
+};
+
 struct TimingSlot { hipEvent_t a, b; int kind; long long units; };
 
 struct mskf_ctx {
@@ -158,8 +169,7 @@ struct mskf_ctx {
     } pend_trk;
     struct PendingUpdate : PendingBatch {
         bool launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
-        std::vector<size_t> lay;   // per stream: o_dx, o_gamma, o_rows, o_status, o_pos
-        std::vector<int> cnt_cls;              // scratch: features per size class of the feature kernel and stream, [3][n]
+        std::vector<EkfUpdatePlan> plan;       // per stream, written by _begin's planning step; storage reused from call to call
     } pend_upd;
     struct PendingPosVar : PendingBatch { int n = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_pv;
 };

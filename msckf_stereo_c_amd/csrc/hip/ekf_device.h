@@ -1,4 +1,5 @@
-// ekf_device.h — device-side descriptors of the MSCKF measurement-update kernels.
+// ekf_device.h — device-side descriptors of the MSCKF measurement-update kernels and, defined here and nowhere else, what the
+// host (mskf_capi_ekf.cpp) and the kernels must agree on: the limits a stream is routed by, the route bits, the mode predicates, the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -6,6 +7,28 @@
 
 #define EKF_IMU_DIM 21
 #define EKF_SLOTS 64          // feature workgroups per stream and launch (each loops over its features)
+
+// ---- kernel limits the host routes by
+#define MAX_CLONES_DEV 64         // largest clone window (mskf_ekf_cfg.max_cam_state_size): 4*64 = 256 block rows max per feature
+#define FEAT_WAVE_CLONES 4        // wave-per-feature class of the feature kernel: Jacobian observations per feature at most
+#define FEAT_SMALL_CLONES 16      // one-wavefront class: max(observations, triangulation clones) at most; above it the big class
+#define TRI_SMALL_CLONES 32       // the wave-per-feature variant triangulates over at most this many clones
+#define SU_MAX_NA 24              // k_ekf_small_update: active columns at most (four clones)
+static_assert(FEAT_WAVE_CLONES <= FEAT_SMALL_CLONES && FEAT_SMALL_CLONES <= TRI_SMALL_CLONES && TRI_SMALL_CLONES <= MAX_CLONES_DEV, "size classes nest");
+static_assert(MAX_CLONES_DEV <= 64, "clone sets are 64-bit masks (EkfFeatDev::colmask, rowmask)");
+
+// ---- EkfStreamDev::route: which kernels handle a stream's update, decided per STREAM from its own features (never from
+// the rest of the batch, so a stream's arithmetic does not depend on its neighbours)
+#define EKF_ROUTE_PAIRS 1         // pair kernels: every feature has exactly the same two Jacobian clones (the pruning update)
+#define EKF_ROUTE_WAVE 2          // wave-per-feature class: every feature <= FEAT_WAVE_CLONES observations, triangulation <= TRI_SMALL_CLONES clones
+#define EKF_ROUTE_SMALL 4         // whole update in k_ekf_small_update (<= SU_MAX_NA active columns possible); the general kernels leave it alone
+enum { GM_GRAM = 0, GM_T = 1, GM_S2 = 2, GM_PUPD = 3 };      // ekf_launch_gemm's mode
+
+// ---- qr_mode (mskf_ekf_cfg.compression_mode): auto, Gram only, Householder always, the reference literally
+// (msckf_vio.cpp:795-821): Householder QR when the stack has more rows than columns, nothing otherwise.
+enum { EKF_QR_AUTO = 0, EKF_QR_GRAM = 1, EKF_QR_HOUSEHOLDER = 2, EKF_QR_REFERENCE = 3 };
+__host__ __device__ __forceinline__ bool ekf_mode_direct(int qr_mode, int stacked, int na) { return (qr_mode == EKF_QR_AUTO || qr_mode == EKF_QR_REFERENCE) && stacked <= na; }
+__host__ __device__ __forceinline__ bool ekf_mode_householder(int qr_mode) { return qr_mode == EKF_QR_HOUSEHOLDER || qr_mode == EKF_QR_REFERENCE; }
 
 // Per feature of one update (device copy of mskf_ekf_feature + row offset of its block)
 struct EkfFeatDev {
@@ -51,10 +74,7 @@ struct EkfStreamDev {
     double *gamma;            // n_feat
     double *pos_out;          // n_feat x 3: feature positions used (triangulated when needs_init)
     double *pos_var_out;      // 3: P(12,12), P(13,13), P(14,14) after the update (epilogue of k_ekf_gemm<PUPD>), or null
-    int route;                // which kernels handle this stream's update, decided per STREAM from its own features (never from
-                              // the rest of the batch, so a stream's arithmetic does not depend on its neighbours): bit 0 pair
-                              // kernels (every feature has exactly the same two Jacobian clones), bit 1 wave-per-feature class
-                              // (every feature <= 4 observations), bit 2 fused small update (at most 4 clones touched)
+    int route;                // EKF_ROUTE_* bits, set by the host
     int na_max;               // 6 x the clones any feature of this update observed: an upper bound of the active columns (from the host)
     int qr_mode;              // mskf_ekf_cfg.compression_mode: 0 auto (Gram + Cholesky, Householder TSQR when flagged), 1 Gram only, 2 TSQR always,
                               // 3 the reference's own rule (Householder when rows > columns, uncompressed otherwise)
@@ -76,6 +96,22 @@ struct EkfStreamDev {
     int remove_index2;        // second clone to delete, > remove_index (-1 = none)
     double *P_dst;            // destination of the out-of-place clone removal
 };
+
+// ---- launchers (ekf_kernels.hip, ekf_linalg.hip): d = n descriptors in device-addressable memory, one per stream
+extern "C" {
+void ekf_launch_propagate(const EkfStreamDev *d, int n, hipStream_t st);
+void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st);
+void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave, const int *work_small, int n_small, const int *work_big, int n_big,
+                         int max_rows, int max_rows_small, int big_clones, hipStream_t st);
+void ekf_launch_pair_features(const EkfStreamDev *d, int n, int max_feat, int max_tri, hipStream_t st);
+void ekf_launch_posvar(const EkfStreamDev *d, int n, double *out, hipStream_t st);
+void ekf_launch_posvar_upd(const EkfStreamDev *d, int n, hipStream_t st);
+void ekf_launch_gemm(const EkfStreamDev *d, int n, int mode, int max_mn, hipStream_t st);
+void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int max_d, hipStream_t st);
+void ekf_launch_tsqr(const EkfStreamDev *d, int n, int max_d, int do_cap, hipStream_t st);
+void ekf_launch_trsm(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
+void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
+}
 
 struct EkfStreamState {       // host-side bookkeeping of the device buffers of one stream
     int max_clones = 0, ld = 0, d = EKF_IMU_DIM;

@@ -237,8 +237,6 @@ __global__ void k_ekf_posvar_upd(const EkfStreamDev *streams, int n) {
 }
 
 // ------------------------------------------------------------------------------------ feature blocks
-#define MAX_CLONES_DEV 64          // 4*64 = 256 block rows max per feature
-
 template <int NMEAS>
 struct TriScratchT {     // poses and rays of the 2 * n_init stereo measurements of one feature
     double R[NMEAS][9];
@@ -246,7 +244,6 @@ struct TriScratchT {     // poses and rays of the 2 * n_init stereo measurements
     double z[NMEAS][2];
 };
 typedef TriScratchT<2 * MAX_CLONES_DEV> TriScratch;
-#define TRI_SMALL_CLONES 32       // the wave-per-feature variant triangulates over at most this many clones
 
 // Levenberg-Marquardt inverse-depth triangulation, executed by wave 0 of the workgroup.
 // feature.hpp:289-450; parameters feature.hpp:46-52.
@@ -415,7 +412,6 @@ __device__ __forceinline__ size_t pk(int i, int j) { return (size_t)i * (i + 1) 
 // min(members, EKF_SLOTS), so the global gate scratch of a slot is never shared).  A (slots x streams) grid sized for
 // the stream with the most features launched mostly empty workgroups, each holding the full LDS allocation until it
 // found nothing to do: the 2 x 192 large features of a batch took 280 us that way.
-#define FEAT_SMALL_CLONES 16
 template <int MAXC, bool WAVE, int TPB>
 __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDev *streams, const int *work, int n_work, int lds_rows, int arena_doubles, int cls_lo, int cls_hi) {
     constexpr int GS = WAVE ? 64 : TPB;         // threads per feature
@@ -839,7 +835,7 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
 // gamma = r_o^T (H_o P_cc H_o^T + sigma^2 I)^-1 r_o against chi2[2 + dof_offset].
 __global__ __launch_bounds__(64) void k_ekf_triangulate(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
-    if (!(S.route & 1)) return;        // not a pair-route stream (the route is a property of the stream, ekf_device.h)
+    if (!(S.route & EKF_ROUTE_PAIRS)) return;        // not a pair-route stream (the route is a property of the stream, ekf_device.h)
     __shared__ TriScratch sTri;
     for (int t = blockIdx.x; t < S.n_tri; t += gridDim.x) {
         const int j = S.tri_idx[t];
@@ -857,7 +853,7 @@ __global__ __launch_bounds__(64) void k_ekf_triangulate(const EkfStreamDev *stre
 #define PAIR_SLAB 153          // doubles per thread: X 8 x 13 (104) + H_f 8 x 3 (24) + V 3 x 8 (24) + 1 (odd stride: no bank conflicts)
 __global__ __launch_bounds__(64) void k_ekf_pair_blocks(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
-    if (!(S.route & 1)) return;
+    if (!(S.route & EKF_ROUTE_PAIRS)) return;
     const int d = S.d, ld = S.ld;
     extern __shared__ double s_pair[];
     __shared__ double sPcc[12 * 12];
@@ -1063,7 +1059,7 @@ void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_ekf_remove_clone, dim3(32, n), dim3(WG), 0, st, d);
 }
 // work_wave / work_small / work_big: the work lists of the three size classes (see the kernel); work_wave holds the
-// features of the streams whose features all have <= 4 Jacobian observations (route bit 1)
+// features of the streams whose features all have <= FEAT_WAVE_CLONES Jacobian observations (EKF_ROUTE_WAVE)
 void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave, const int *work_small, int n_small, const int *work_big, int n_big,
                          int max_rows, int max_rows_small, int big_clones, hipStream_t st) {
     const int packed_max = ((GATE_LDS_ROWS + 1) * (GATE_LDS_ROWS + 2) / 2 + 16) * (int)sizeof(double);   // + the r_o row + slack
@@ -1072,14 +1068,15 @@ void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave
     std::call_once(attr_once, [=]() {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_feature_blocks<32, false, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, packed_max);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_feature_blocks<MAX_CLONES_DEV, false, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, packed_max);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_feature_blocks<4, true, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * tri_doubles * 8);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_feature_blocks<FEAT_WAVE_CLONES, true, WG>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * tri_doubles * 8);
     });
+    static_assert(4 * FEAT_WAVE_CLONES <= 16, "the WAVE variant's gate matrix and Cholesky panel hold 16 block rows (PAN_RS)");
     const int ALL = 1 << 30;
-    // streams whose features ALL have <= 4 Jacobian observations (and triangulations that fit the small scratch): one
-    // wavefront per feature, four per workgroup.  The class is a property of the stream (route bit 1), so its work list
+    // streams whose features ALL have <= FEAT_WAVE_CLONES Jacobian observations (and triangulations that fit the small scratch): one
+    // wavefront per feature, four per workgroup.  The class is a property of the stream (EKF_ROUTE_WAVE), so its work list
     // holds whole streams and the other two lists none of their features.
     if (n_wave > 0)
-        hipLaunchKernelGGL((k_ekf_feature_blocks<4, true, WG>), dim3((n_wave + 3) / 4), dim3(WG), (size_t)4 * tri_doubles * 8, st, d, work_wave, n_wave, 16, tri_doubles, 0, ALL);
+        hipLaunchKernelGGL((k_ekf_feature_blocks<FEAT_WAVE_CLONES, true, WG>), dim3((n_wave + 3) / 4), dim3(WG), (size_t)4 * tri_doubles * 8, st, d, work_wave, n_wave, 4 * FEAT_WAVE_CLONES, tri_doubles, 0, ALL);
     // small class: features of at most FEAT_SMALL_CLONES observations (Jacobian and triangulation), one wavefront each.
     // (A third class of <= 8 observations, 12 KiB of LDS and eight features per CU, was measured and dropped: every class
     // launch is a single latency-bound round, so a further split only adds another round to the chain.)

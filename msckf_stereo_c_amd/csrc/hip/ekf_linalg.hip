@@ -42,21 +42,11 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 //     stacked row, rows_out[1], may lie far beyond na), so the rows are addressed through a compact list of their indices
 //     (rowidx, built by ekf_compress_entry behind the active-column list).
 //   * otherwise Gram + regularised Cholesky, re-done as Householder TSQR when the factorisation raises the bias flag (bit 1).
-// qr_mode (mskf_ekf_cfg.compression_mode): 0 auto, 1 Gram only, 2 Householder always, 3 = the reference literally
-// (msckf_vio.cpp:795-821): Householder QR when the stack has more rows than columns, nothing otherwise.
-__device__ __forceinline__ bool ekf_mode_direct(int qr_mode, int stacked, int na) { return (qr_mode == 0 || qr_mode == 3) && stacked <= na; }
-__device__ __forceinline__ bool ekf_mode_householder(int qr_mode) { return qr_mode == 2 || qr_mode == 3; }
+// (the qr_mode predicates ekf_mode_direct / ekf_mode_householder: ekf_device.h)
 __device__ __forceinline__ bool ekf_direct_wanted(const EkfStreamDev &S) { return ekf_mode_direct(S.qr_mode, S.rows_out[0], S.rows_out[2]); }
 __device__ __forceinline__ bool ekf_skip_gram(const EkfStreamDev &S) { return ekf_mode_householder(S.qr_mode) || ekf_direct_wanted(S); }
 // the stream's stacked rows are used uncompressed (set by the factorisation kernel): R = H_act (rows_out[1] x na, dense, rowmask-gathered)
 __device__ __forceinline__ bool ekf_direct(const EkfStreamDev &S) { return (S.rows_out[3] & 4) != 0; }
-// streams whose whole update runs in k_ekf_small_update (route bit, set per STREAM by the host: at most SU_MAX_NA active
-// columns possible); the general kernels leave them alone and vice versa
-#define EKF_ROUTE_PAIRS 1
-#define EKF_ROUTE_WAVE 2
-#define EKF_ROUTE_SMALL 4
-
-enum { GM_GRAM = 0, GM_T = 1, GM_S2 = 2, GM_PUPD = 3 };
 
 // Per-mode compile-time shape of op(A) op(B): TA: op(A)(i,k) = A[k*ld+i] (else A[i*ld+k]); B is always B[k*ld+j].
 // KMIN_I: op(A)(i,k) == 0 for k < i (R = L^T is upper triangular); KMIN_J: op(B)(k,j) == 0 for k < j.
@@ -941,7 +931,6 @@ __global__ __launch_bounds__(256) void k_ekf_trsm(const EkfStreamDev *streams) {
 // back to back out of LDS.  Same algebra as the general path: G = [H_act|r]^T [H_act|r] + lambda I = L L^T,
 // T = L^T[0:na,0:na] P[act,:], S = T[:,act] L[0:na,0:na] + sigma^2 I = L2 L2^T, Y = L2^-1 [T | Q^T r],
 // delta_x = Y^T w, P -= Y^T Y (symmetric by construction).  All sums run in a fixed order (no atomics).
-#define SU_MAX_NA 24
 #define SU_CH 128         // stacked rows per Gram chunk
 __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
@@ -1211,7 +1200,6 @@ void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_
     });
     hipLaunchKernelGGL(k_ekf_small_update, dim3(1, n), dim3(256), lds, st, d);
 }
-int ekf_small_update_max_na(void) { return SU_MAX_NA; }
 void ekf_launch_trsm(const EkfStreamDev *d, int n, int max_d, hipStream_t st) {
     const int strips = (max_d + 1 + TS_COLS - 1) / TS_COLS;
     // the solve runs over the active rows only: n <= max_d - 21 (the IMU columns are never active).  A full 64-clone

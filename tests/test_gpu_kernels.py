@@ -536,6 +536,197 @@ def test_track_capacity_and_errors(gpu_ctx, oracle):
     s.close()
 
 
+def _update_kwargs(pr, pair=False, **extra):
+    """kwargs of Stream.ekf_update for a problem of ekf_problems, with arrays of their own (a test may spoil them)."""
+    return dict(gravity=pr["gravity"].copy(), clones=pr["clones"].copy(), positions=pr["positions"].copy(), obs_start=pr["obs_start"].copy(),
+                obs_clone=pr["obs_clone"].copy(), obs_z=pr["obs_z"].copy(), dof_offset=0 if pair else -1, apply_row_cap=not pair, **extra)
+
+
+def _empty_kwargs(pr):
+    return dict(gravity=pr["gravity"].copy(), clones=pr["clones"].copy(), positions=np.zeros((0, 3)), obs_start=np.zeros(1, np.int32),
+                obs_clone=np.zeros(0, np.int32), obs_z=np.zeros((0, 4)), dof_offset=-1, apply_row_cap=True)
+
+
+_MSKF_ERR_INVALID, _MSKF_ERR_CAPACITY = -1, -4
+_REFUSAL_REF = {}
+
+
+def _refusal_batch(calib):
+    """Three streams of a 12-clone window: a pruning-shaped stack of 2250 rows (more than the 2048 rows a stream of this
+    configuration starts with, so accepting it grows the stream's stacked-Jacobian buffer), a general one, a short one."""
+    problems = [ekf_problems.make_problem(calib, seed=61, n_clones=12, n_feat=450, pair=(10, 11), noise=0.004),
+                ekf_problems.make_problem(calib, seed=62, n_clones=12, n_feat=20),
+                ekf_problems.make_problem(calib, seed=63, n_clones=12, n_feat=8)]
+    return problems, [_update_kwargs(problems[0], pair=True), _update_kwargs(problems[1]), _update_kwargs(problems[2])]
+
+
+# what is done to the middle stream's (mskf_ekf_update_args, buffers) before the batch is offered: buffers = (clones, features,
+# obs_clone, obs_z, ...) as Stream._update_args returns them
+def _spoil_n_clones(a, buf): a.n_clones -= 1
+def _spoil_one_obs(a, buf): buf[1]["n_obs"][3] = 1
+def _spoil_too_many_obs(a, buf): buf[1]["obs_start"][0] = 0; buf[1]["n_obs"][0] = 13          # max_cam_state_size is 12
+def _spoil_obs_range(a, buf): a.n_obs -= 1                                                    # the last feature ends at n_obs
+def _spoil_init_count(a, buf): buf[1]["needs_init"][2] = 1; buf[1]["n_init"][2] = 0
+def _spoil_init_range(a, buf): buf[1]["needs_init"][2] = 1; buf[1]["init_start"][2] = a.n_obs - 1; buf[1]["n_init"][2] = 2
+def _spoil_obs_clone(a, buf): buf[2][5] = 12
+def _spoil_output(a, buf): a.delta_x = None
+
+
+_EKF_REFUSALS = {
+    "n_clones": (_spoil_n_clones, _MSKF_ERR_INVALID, "n_clones does not match the covariance dimension"),
+    "one_observation": (_spoil_one_obs, _MSKF_ERR_INVALID, None),
+    "more_observations_than_clones": (_spoil_too_many_obs, _MSKF_ERR_INVALID, None),
+    "observations_past_n_obs": (_spoil_obs_range, _MSKF_ERR_INVALID, None),
+    "init_count": (_spoil_init_count, _MSKF_ERR_INVALID, None),
+    "init_range": (_spoil_init_range, _MSKF_ERR_INVALID, None),
+    "obs_clone": (_spoil_obs_clone, _MSKF_ERR_INVALID, None),
+    "missing_output": (_spoil_output, _MSKF_ERR_INVALID, None),
+    "other_context": (None, _MSKF_ERR_INVALID, None),
+    "too_many_rows": (None, _MSKF_ERR_CAPACITY, "stacked Jacobian exceeds the row capacity"),
+}
+
+
+@pytest.mark.parametrize("case", list(_EKF_REFUSALS))
+def test_ekf_update_batch_refusals(gpu_ctx, oracle, case):
+    """mskf_ekf_update_batch_begin refuses a batch whose MIDDLE stream is wrong (a valid stream before it, whose stack
+    would grow its row buffer, and one after it): today's status code and message, no batch left pending (an _end is a
+    no-op, the next _begin is accepted), and the same three streams then compute a valid batch bit-identically to three
+    fresh streams.  Host-side refusals of bad arguments: nothing reaches the device."""
+    import ctypes as C
+    L = gpu_ctx.L
+    L.mskf_ekf_update_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(capi.EkfUpdateArgs)]
+    L.mskf_ekf_update_batch_end.argtypes = [C.c_void_p]
+    calib = oracle.euroc_calib(376, 240)
+    cfg = default_ekf_cfg(max_cam_state_size=12)
+    problems, _ = _refusal_batch(calib)
+
+    def fresh(ctx):
+        ss = [capi.Stream(ctx, calib, default_fe_cfg(), cfg) for _ in problems]
+        for s, pr in zip(ss, problems):
+            s.ekf_set_cov(pr["P"])
+        return ss
+
+    def valid_batch(ss):
+        got = gpu_ctx.ekf_update_batch(ss, _refusal_batch(calib)[1])
+        return got, [s.ekf_get_cov() for s in ss]
+
+    if not _REFUSAL_REF:
+        ss = fresh(gpu_ctx)
+        _REFUSAL_REF["got"], _REFUSAL_REF["P"] = valid_batch(ss)
+        for s in ss:
+            s.close()
+        assert all(r["rows"] > 0 for r in _REFUSAL_REF["got"])
+    ss = fresh(gpu_ctx)
+    spoil, expect, message = _EKF_REFUSALS[case]
+    kwargs = _refusal_batch(calib)[1]
+    other = None
+    handles = [s.h for s in ss]
+    if case == "other_context":
+        other = capi.Context(0)
+        handles[1] = fresh(other)[1].h
+    if case == "too_many_rows":           # 13108 two-observation features: 65540 rows > 65536
+        n = 13108
+        kwargs[1] = dict(kwargs[1], positions=np.zeros((n, 3)), obs_start=np.arange(0, 2 * n + 1, 2, dtype=np.int32),
+                         obs_clone=np.tile(np.array([10, 11], np.int32), n), obs_z=np.zeros((2 * n, 4)), dof_offset=0, apply_row_cap=False)
+    built = [capi.Stream._update_args(**kw) for kw in kwargs]
+    if spoil is not None:
+        spoil(built[1][0], built[1][1])
+    for b in built:
+        b[1][4][:] = 777.0                # delta_x: an _end that found something pending would overwrite it
+    args = (capi.EkfUpdateArgs * 3)(*[b[0] for b in built])
+    rc = L.mskf_ekf_update_batch_begin(gpu_ctx.h, 3, (C.c_void_p * 3)(*handles), args)
+    assert rc == expect
+    if message is not None:
+        assert L.mskf_last_error().decode() == message
+    assert L.mskf_ekf_update_batch_end(gpu_ctx.h) == 0
+    assert all((b[1][4] == 777.0).all() for b in built) and all(b[1][7][0] == 0 for b in built)
+    got, P = valid_batch(ss)              # (its _begin is accepted)
+    for s in ss:
+        s.close()
+    if other is not None:
+        other.close()
+    for a, b, Pa, Pb in zip(got, _REFUSAL_REF["got"], P, _REFUSAL_REF["P"]):
+        assert a["rows"] == b["rows"] and a["used_qr"] == b["used_qr"] and a["tiny_pivots"] == b["tiny_pivots"]
+        assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["gamma"], b["gamma"])
+        assert np.array_equal(a["delta_x"], b["delta_x"]) and np.array_equal(Pa, Pb)
+
+
+# Timed launches of one update batch per kind (mskf_ctx_get_timing), from DESIGN.md §2 and the comments of the launch chain:
+#   FEATURES one slot around the pair kernels and the feature-block classes, whichever of them run;
+#   SMALL    k_ekf_small_update, when some stream takes the small route (at most four clones touched);
+#   when some stream takes the general route: GEMM<GRAM> and CHOL(0) if one of them compresses by Gram (modes 0, 1),
+#   TSQR if one of them compresses by Householder (modes 2, 3), then GEMM<T>, GEMM<S2>, CHOL(1), TRSM;
+#   GEMM<PUPD> for every batch that launches anything.  A batch without features launches nothing.
+# The units are the algorithmic flops of each launch (SURVEY.md 8d) as integers, worked out from the problems' shapes
+# outside the library: they pin what the entry point accounted before it was split into plan / grow / pack / enqueue.
+_K_FEATURES, _K_TSQR, _K_GEMM, _K_CHOL, _K_TRSM, _K_SMALL, _K_COUNT = 5, 6, 7, 8, 9, 10, 14
+_PAIR = dict(n_clones=12, n_feat=40, seed=71, pair=(10, 11), noise=0.004)
+_PAIR2 = dict(n_clones=12, n_feat=25, seed=74, pair=(0, 1), noise=0.004)
+_FEW = dict(n_clones=4, n_feat=10, seed=75)           # at most four clones touched, not a pair stack
+_GEN, _GEN2 = dict(n_clones=12, n_feat=20, seed=72), dict(n_clones=12, n_feat=15, seed=73)
+_GRAM_CHAIN = {_K_FEATURES: 1, _K_GEMM: 4, _K_CHOL: 2, _K_TRSM: 1}
+_HH_CHAIN = {_K_FEATURES: 1, _K_TSQR: 1, _K_GEMM: 3, _K_CHOL: 1, _K_TRSM: 1}
+_GRAM_UNITS = {_K_FEATURES: 28093452, _K_GEMM: 29216322, _K_CHOL: 1072476, _K_TRSM: 3217428}            # (_GEN, _GEN2), compressed by Gram
+_HH_UNITS = {_K_FEATURES: 28093452, _K_TSQR: 16346610, _K_GEMM: 12869712, _K_CHOL: 536238, _K_TRSM: 3217428}     # ... by Householder
+_EKF_CHAINS = {          # batch: [(problem | None = no features, compression_mode, triangulate)], launches per kind, units per kind
+    "small_pairs": ([(_PAIR, 3, False), (_PAIR2, 3, False)], {_K_FEATURES: 1, _K_SMALL: 1, _K_GEMM: 1}, {_K_FEATURES: 5986500, _K_SMALL: 21172752}),
+    "small_pairs_triangulated": ([(_PAIR, 3, True), (_PAIR2, 3, False)], {_K_FEATURES: 1, _K_SMALL: 1, _K_GEMM: 1}, {_K_FEATURES: 5986500, _K_SMALL: 21172752}),
+    "small_not_pairs": ([(_FEW, 3, False)], {_K_FEATURES: 1, _K_SMALL: 1, _K_GEMM: 1}, {_K_FEATURES: 597144, _K_SMALL: 1310175}),
+    "general_mode0": ([(_GEN, 0, False), (_GEN2, 0, False)], _GRAM_CHAIN, _GRAM_UNITS),
+    "general_mode1": ([(_GEN, 1, False), (_GEN2, 1, False)], _GRAM_CHAIN, _GRAM_UNITS),
+    "general_mode2": ([(_GEN, 2, False), (_GEN2, 2, False)], _HH_CHAIN, _HH_UNITS),
+    "general_mode3": ([(_GEN, 3, False), (_GEN2, 3, False)], _HH_CHAIN, _HH_UNITS),
+    "small_and_general": ([(_PAIR, 0, False), (_GEN, 0, False)], {**_GRAM_CHAIN, _K_SMALL: 1}, {_K_FEATURES: 19993464, _K_GEMM: 25358868, _K_CHOL: 1072476, _K_TRSM: 3217428}),
+    "householder_and_gram": ([(_GEN, 3, False), (_GEN2, 0, False)], {**_GRAM_CHAIN, _K_TSQR: 1}, {**_GRAM_UNITS, _K_TSQR: 16346610}),
+    "all_empty": ([(None, 3, False), (None, 0, False)], {}, {}),
+    "some_empty": ([(None, 3, False), (_GEN, 0, False), (None, 0, False)], _GRAM_CHAIN, {_K_FEATURES: 16309464, _K_GEMM: 16000650, _K_CHOL: 536238, _K_TRSM: 1608714}),
+}
+
+
+@pytest.mark.parametrize("case", list(_EKF_CHAINS))
+def test_ekf_update_launch_chain(gpu_ctx, oracle, case):
+    """Which launches an update batch enqueues, by its composition: timing period 1, launches and units per kind."""
+    import ctypes as C
+    L = gpu_ctx.L
+    L.mskf_ctx_set_timing.argtypes = [C.c_void_p, C.c_int]
+    L.mskf_ctx_get_timing.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    calib = oracle.euroc_calib(376, 240)
+    batch, launches, units = _EKF_CHAINS[case]
+    base = ekf_problems.make_problem(calib, **_GEN)
+    ss, kwargs, P0 = [], [], []
+    for spec, mode, tri in batch:
+        pr = base if spec is None else ekf_problems.make_problem(calib, **spec)
+        s = capi.Stream(gpu_ctx, calib, default_fe_cfg(), default_ekf_cfg(max_cam_state_size=12, compression_mode=mode))
+        s.ekf_set_cov(pr["P"])
+        ss.append(s); P0.append(pr["P"])
+        if spec is None:
+            kwargs.append(_empty_kwargs(pr))
+        else:
+            kwargs.append(_update_kwargs(pr, pair="pair" in spec, **(dict(needs_init=np.ones(spec["n_feat"], np.int32)) if tri else {})))
+    ms, n_l, n_u = np.zeros(_K_COUNT), np.zeros(_K_COUNT, np.int64), np.zeros(_K_COUNT, np.int64)
+    assert L.mskf_ctx_set_timing(gpu_ctx.h, 1) == 0
+    try:
+        assert L.mskf_ctx_get_timing(gpu_ctx.h, ms.ctypes.data, n_l.ctypes.data, n_u.ctypes.data, 1) == 0      # reset
+        got = gpu_ctx.ekf_update_batch(ss, kwargs)
+        assert L.mskf_ctx_get_timing(gpu_ctx.h, ms.ctypes.data, n_l.ctypes.data, n_u.ctypes.data, 1) == 0
+    finally:
+        L.mskf_ctx_set_timing(gpu_ctx.h, 0)
+    P1 = [s.ekf_get_cov() for s in ss]
+    for s in ss:
+        s.close()
+    print("launch chain %s: launches %s units %s" % (case, {k: int(v) for k, v in enumerate(n_l) if v}, {k: int(v) for k, v in enumerate(n_u) if v}))
+    assert {k: int(v) for k, v in enumerate(n_l) if v} == launches
+    assert {k: int(v) for k, v in enumerate(n_u) if v} == units
+    for (spec, _, _), r, Pa, Pb in zip(batch, got, P0, P1):
+        if spec is not None:
+            assert r["rows"] > 0
+            continue
+        # a stream without features: no correction, the covariance as it was; its position variances are read out behind
+        # the others' updates when anything was launched, and "no value" (-1) when nothing ran
+        assert r["rows"] == 0 and not r["delta_x"].any() and np.array_equal(Pa, Pb)
+        assert np.array_equal(r["pos_var"], Pa[[12, 13, 14], [12, 13, 14]] if launches else np.full(3, -1.0))
+
+
 @pytest.mark.parametrize("mode,expect", [(3, {1, 2}), (0, {0, 2})])
 def test_ekf_mixed_batch_takes_each_stream_its_own_route(gpu_ctx, oracle, mode, expect):
     """One mskf_ekf_update_batch over streams of every route (EkfStreamDev::route): a pruning-shaped stream (pair kernels +
