@@ -83,6 +83,12 @@ def lib():
         L.mskf_stream_create.argtypes = [C.c_void_p, C.POINTER(Calib), C.POINTER(FeCfg), C.POINTER(EkfCfg), C.POINTER(C.c_void_p)]
         L.mskf_stream_destroy.argtypes = [C.c_void_p]
         L.mskf_fe_push_stereo.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double]
+        L.mskf_fe_push_stereo_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]
+        L.mskf_fe_grid_capacity.argtypes = [C.c_void_p]
+        L.mskf_fe_set_grid.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p, C.c_uint64]
+        L.mskf_fe_frame_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int,
+                                                C.POINTER(FeFrameArgs)]
+        L.mskf_fe_frame_batch_end.argtypes = [C.c_void_p]
         L.mskf_fe_get_cell_maxima.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.mskf_fe_track.argtypes = [C.c_void_p, C.POINTER(TrackArgs)]
         L.mskf_fe_swap.argtypes = [C.c_void_p]
@@ -108,6 +114,23 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _handles(streams):
+    """Stream handles as a C array; None stands for a null handle."""
+    return (C.c_void_p * len(streams))(*[None if s is None else s.h for s in streams])
+
+
+def _images(imgs):
+    """(C array of addresses, what keeps them alive): an entry is an h x w uint8 host image, a device address, or None."""
+    keep = [np.ascontiguousarray(x, dtype=np.uint8) if isinstance(x, np.ndarray) else x for x in imgs]
+    return (C.c_void_p * len(keep))(*[x.ctypes.data if isinstance(x, np.ndarray) else x for x in keep]), keep
+
+
+def _pts(a):
+    """Points as a contiguous POINT2F array: given as one, or as n x 2 floats."""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a) if a.dtype == POINT2F else np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2).view(POINT2F).reshape(-1)
+
+
 def _imu_steps(steps):
     """mskf_imu_step records as a contiguous IMU_STEP array (None / empty: no steps)."""
     if steps is None:
@@ -129,6 +152,7 @@ class Context:
             _chk(self.L.mskf_ctx_create_shared(shared_with.h, C.byref(self.h)))
         self.streams = []
         self._trk_pending = None
+        self._frame_pending = None
 
     def close(self):
         if self.h:
@@ -176,6 +200,54 @@ class Context:
         self.L.mskf_fe_track_batch_end.argtypes = [C.c_void_p]
         _chk(self.L.mskf_fe_track_batch_end(self.h))
         self._trk_pending = None
+
+    def push_stereo_batch(self, streams, cam0s, cam1s, on_device=0):
+        """One mskf_fe_push_stereo_batch: host images (on_device = 0) or device addresses (1: copied, 2: borrowed)."""
+        a, _keep_a = _images(cam0s)
+        b, _keep_b = _images(cam1s)
+        _chk(self.L.mskf_fe_push_stereo_batch(self.h, len(streams), _handles(streams), a, b, on_device))
+
+    def frame_batch_begin(self, streams, images, args, on_device=0):
+        """mskf_fe_frame_batch_begin: a whole front-end frame of every stream on the device.  images[i] = (cam0, cam1) as for
+        push_stereo_batch; args[i] = dict(Hpred=3 x 3 or None for the identity, R_p_c=2 x 3 x 3 or None, capacity=entries of the
+        output arrays or None for the stream's grid_capacity()).  frame_batch_end returns the results."""
+        n = len(streams)
+        a, keep_a = _images([im[0] for im in images])
+        b, keep_b = _images([im[1] for im in images])
+        fa = (FeFrameArgs * n)()
+        outs = []
+        for i, (s, kw) in enumerate(zip(streams, args)):
+            cap = kw.get("capacity")
+            cap = (s.grid_capacity() if s is not None else 0) if cap is None else cap
+            o = dict(id=np.zeros(max(cap, 1), np.uint64), lifetime=np.zeros(max(cap, 1), np.int32),
+                     **{k: np.zeros(max(cap, 1), POINT2F) for k in ("cam0", "cam1", "und0", "und1")})
+            H = np.eye(3) if kw.get("Hpred") is None else np.ascontiguousarray(kw["Hpred"], dtype=np.float64)
+            R = np.stack([np.eye(3)] * 2) if kw.get("R_p_c") is None else np.ascontiguousarray(kw["R_p_c"], dtype=np.float64)
+            fa[i].Hpred[:] = list(H.reshape(-1))
+            for c in range(2):
+                fa[i].R_p_c[c][:] = list(R.reshape(2, 9)[c])
+            fa[i].capacity = cap
+            for k, v in o.items():
+                setattr(fa[i], k, v.ctypes.data)
+            outs.append(o)
+        hs = _handles(streams)
+        _chk(self.L.mskf_fe_frame_batch_begin(self.h, n, hs, a, b, on_device, fa))
+        self._frame_pending = (fa, outs, hs, a, b, keep_a, keep_b)          # must stay alive until _end
+        return outs
+
+    def frame_batch_end(self):
+        """Per stream of the pending frame batch: the published grid (arrays cut to n) and the frame's counters."""
+        _chk(self.L.mskf_fe_frame_batch_end(self.h))
+        pending, self._frame_pending = self._frame_pending, None
+        if pending is None:
+            return []
+        res = []
+        for a, o in zip(pending[0], pending[1]):
+            r = {k: v[:a.n].copy() if v.dtype != POINT2F else v[:a.n].view(np.float32).reshape(-1, 2).copy() for k, v in o.items()}
+            r.update({k: int(getattr(a, k)) for k in ("n", "before_tracking", "after_tracking", "after_matching", "after_ransac", "n_candidates", "n_new",
+                                                      "next_feature_id", "ransac_draws")})
+            res.append(r)
+        return res
 
     def ekf_predict_batch(self, streams, steps, J):
         """One mskf_ekf_predict_batch: streams[i] propagates over steps[i] (IMU_STEP records, None = none), then augments
@@ -266,6 +338,20 @@ class Stream:
             assert cam0.shape[1] == pitch and cam1.shape == cam0.shape
             w = self.calib.width
         _chk(self.L.mskf_fe_push_stereo(self.h, _p(cam0), _p(cam1), w, h, w if pitch is None else pitch, t))
+
+    def grid_capacity(self):
+        """Entries a published grid of this stream can have; 0: the stream keeps its books on the host."""
+        return self.L.mskf_fe_grid_capacity(self.h)
+
+    def set_grid(self, id=None, lifetime=None, cam0=None, cam1=None, und0=None, und1=None, next_feature_id=0, tracking_counters=None,
+                 ransac_draws=0, n=None):
+        """mskf_fe_set_grid: hand the device the grid a host-side frame has published (no arrays: an empty grid)."""
+        arrs = [None if id is None else np.ascontiguousarray(id, dtype=np.uint64), None if lifetime is None else np.ascontiguousarray(lifetime, dtype=np.int32)]
+        arrs += [None if x is None else _pts(x) for x in (cam0, cam1, und0, und1)]
+        if n is None:
+            n = 0 if arrs[0] is None else len(arrs[0])
+        tc = None if tracking_counters is None else np.ascontiguousarray(tracking_counters, dtype=np.int32)
+        _chk(self.L.mskf_fe_set_grid(self.h, n, *[None if x is None else _p(x) for x in arrs], next_feature_id, None if tc is None else _p(tc), ransac_draws))
 
     def set_detect_floor(self, min_score):
         _chk(self.L.mskf_fe_set_detect_floor(self.h, int(min_score)))

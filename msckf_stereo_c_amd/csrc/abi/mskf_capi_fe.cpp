@@ -7,7 +7,7 @@
 #include <cstring>
 #include <chrono>
 #include <atomic>
-#include <mutex>
+#include <type_traits>
 #include <vector>
 #include "mskf_internal.h"
 
@@ -301,58 +301,65 @@ void fill_pyr(const mskf_stream *s, int idx, PyrDev &p) {
     if (s->lvl0[idx]) p.lvl[0] = s->lvl0[idx];
 }
 
+// The stream's book allocation: ONE sequence of take()s, run on a null base to obtain the size and on the allocation to
+// set the pointers (every region rounded up to 256 bytes).  D holds the capacities on entry.
+static size_t book_carve(char *base, FeBookDev &D, FeGridArr grid[3]) {
+    size_t off = 0;
+    auto take = [&](auto *&p, size_t count) {
+        p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off);
+        off += (sizeof(*p) * count + 255) & ~(size_t)255;
+    };
+    const size_t cap = (size_t)D.cap, cand_cap = (size_t)D.cand_cap, det_cap = (size_t)D.det_cap;
+    take(D.st, 1);
+    for (int g = 0; g < 3; ++g) {
+        FeGridArr &G = grid[g];
+        take(G.id, cap); take(G.lifetime, cap); take(G.code, cap); take(G.response, cap);
+        take(G.cam0, cap); take(G.cam1, cap); take(G.und0, cap); take(G.und1, cap);
+    }
+    D.tracked = grid[2];
+    take(D.det_pt, det_cap); take(D.det_score, det_cap);
+    take(D.cand_pt, cand_cap); take(D.cand_index, cand_cap); take(D.cand_score, cand_cap);
+    take(D.cand_off, (size_t)D.n_cells + 1); take(D.cand_cnt, (size_t)D.n_cells + 1); take(D.cell_count, (size_t)D.n_codes + 1);
+    take(D.t_out0, cap); take(D.t_out1, cap); take(D.t_und0, cap); take(D.t_und1, cap); take(D.t_status, cap);
+    take(D.c_out0, cand_cap); take(D.c_out1, cand_cap); take(D.c_und0, cand_cap); take(D.c_und1, cand_cap); take(D.c_status, cand_cap);
+    take(D.rs_pair, 4 * cap); take(D.rs_pt, 4 * cap); take(D.rs_scalar, 48);       // fe_book.h: the scratch of the 2-point RANSAC
+    return off;
+}
+
 // Device-side books of a stream (fe_book.h): the three feature lists, detection / candidate lists and the results of the two
-// track calls, in ONE allocation.  Streams whose grid_min / grid_max exceed the short-list bound of the kernels keep their
-// books on the host (cap stays 0).
+// track calls, in ONE allocation, and the descriptor of everything about them that never changes (Book::dev).  Streams whose
+// grid_min / grid_max exceed the short-list bound of the kernels keep their books on the host (dev.cap stays 0).
 static int book_alloc(mskf_stream *s) {
     mskf_stream::Book &K = s->book;
     const mskf_fe_cfg &fe = s->fe;
     if (fe.grid_min_feature_num > FB_MAXK || fe.grid_max_feature_num > FB_MAXK || fe.grid_min_feature_num < 0 ||
         fe.grid_max_feature_num < fe.grid_min_feature_num) return MSKF_OK;
-    K.grid_h = s->h / fe.grid_row; K.grid_w = s->w / fe.grid_col;                 // image_processor.cpp:250-251
-    if (K.grid_h <= 0 || K.grid_w <= 0) return MSKF_OK;
-    K.n_cells = fe.grid_row * fe.grid_col;
-    K.n_codes = std::max(((s->h - 1) / K.grid_h) * fe.grid_col + (s->w - 1) / K.grid_w + 1, K.n_cells);   // Q7: partial rows / columns
-    const int cap = K.n_codes * std::max(fe.grid_max_feature_num, 1) + 8;
-    const int cand_cap = K.n_cells * std::max(fe.grid_max_feature_num, 1) + 8;
-    const int det_cap = fe.det_rows * fe.det_cols;
+    FeBookDev D{};
+    D.grid_row = fe.grid_row; D.grid_col = fe.grid_col; D.grid_min = fe.grid_min_feature_num; D.grid_max = fe.grid_max_feature_num;
+    D.grid_h = s->h / fe.grid_row; D.grid_w = s->w / fe.grid_col;                 // image_processor.cpp:250-251
+    if (D.grid_h <= 0 || D.grid_w <= 0) return MSKF_OK;
+    D.n_cells = fe.grid_row * fe.grid_col;
+    D.n_codes = std::max(((s->h - 1) / D.grid_h) * fe.grid_col + (s->w - 1) / D.grid_w + 1, D.n_cells);   // Q7: partial rows / columns
+    D.cap = D.n_codes * std::max(fe.grid_max_feature_num, 1) + 8;
+    D.cand_cap = D.n_cells * std::max(fe.grid_max_feature_num, 1) + 8;
+    D.det_cap = fe.det_rows * fe.det_cols;
     // the bookkeeping kernel keeps its lists in LDS: a configuration whose lists do not fit the budget the kernel can get
     // (a very fine detector grid) keeps its books on the host
-    if (4 * fe_book_scratch_ints(cap, cand_cap, det_cap, K.n_codes, det_cap) > fe_book_lds_budget()) return MSKF_OK;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_st = take(sizeof(FeBookState));
-    size_t o_grid[3][8];
-    for (int g = 0; g < 3; ++g) {
-        o_grid[g][0] = take(8 * (size_t)cap); o_grid[g][1] = take(4 * (size_t)cap); o_grid[g][2] = take(4 * (size_t)cap); o_grid[g][3] = take(4 * (size_t)cap);
-        for (int q = 4; q < 8; ++q) o_grid[g][q] = take(8 * (size_t)cap);
-    }
-    const size_t o_det_pt = take(8 * (size_t)det_cap), o_det_sc = take(4 * (size_t)det_cap);
-    const size_t o_cpt = take(8 * (size_t)cand_cap), o_cidx = take(4 * (size_t)cand_cap), o_csc = take(4 * (size_t)cand_cap);
-    const size_t o_coff = take(4 * (size_t)(K.n_cells + 1)), o_ccnt = take(4 * (size_t)(K.n_cells + 1)), o_cell = take(4 * (size_t)(K.n_codes + 1));
-    size_t o_t[5], o_c[5];
-    for (int q = 0; q < 4; ++q) o_t[q] = take(8 * (size_t)cap);
-    o_t[4] = take((size_t)cap);
-    for (int q = 0; q < 4; ++q) o_c[q] = take(8 * (size_t)cand_cap);
-    o_c[4] = take((size_t)cand_cap);
-    const size_t o_rs_pair = take(8 * 4 * (size_t)cap), o_rs_pt = take(4 * 4 * (size_t)cap), o_rs_sc = take(8 * 48);
-    MSKF_HIPCHK(hipMalloc((void **)&K.mem, off));
-    MSKF_HIPCHK(hipMemsetAsync(K.mem, 0, off, s->ctx->stream));
+    if (4 * fe_book_scratch_ints(D.cap, D.cand_cap, D.det_cap, D.n_codes, D.det_cap) > fe_book_lds_budget()) return MSKF_OK;
+    D.det_rows = fe.det_rows; D.det_cols = fe.det_cols; D.det_cw = s->det_cw; D.det_ch = s->det_ch;
+    D.thr_score = fe.fast_threshold * 256;
+    D.q4 = (fe.compat_flags & MSKF_COMPAT_Q4_RESPONSE_INDEX) ? 1 : 0;
+    // twoPointRansac between the tracks (:482-500; commented out in the reference, Q5): iterations as :920-921
+    D.ransac = (fe.compat_flags & MSKF_COMPAT_Q5_NO_RANSAC) ? 0 : 1;
+    D.ransac_iters = static_cast<int>(std::ceil(std::log(1 - 0.99) / std::log(1 - 0.7 * 0.7)));
+    D.ransac_thr = fe.ransac_threshold;
+    D.ransac_npu[0] = 2.0 / (s->cam0.K[0] + s->cam0.K[1]); D.ransac_npu[1] = 2.0 / (s->cam1.K[0] + s->cam1.K[1]);
+    const size_t bytes = book_carve(nullptr, D, K.grid);
+    MSKF_HIPCHK(hipMalloc((void **)&K.mem, bytes));
+    MSKF_HIPCHK(hipMemsetAsync(K.mem, 0, bytes, s->ctx->stream));
     MSKF_HIPCHK(hipStreamSynchronize(s->ctx->stream));
-    char *m = K.mem;
-    K.st = (FeBookState *)(m + o_st);
-    for (int g = 0; g < 3; ++g)
-        K.grid[g] = FeGridArr{(unsigned long long *)(m + o_grid[g][0]), (int *)(m + o_grid[g][1]), (int *)(m + o_grid[g][2]), (float *)(m + o_grid[g][3]),
-                              (mskf_point2f *)(m + o_grid[g][4]), (mskf_point2f *)(m + o_grid[g][5]), (mskf_point2f *)(m + o_grid[g][6]), (mskf_point2f *)(m + o_grid[g][7])};
-    K.det_pt = (mskf_point2f *)(m + o_det_pt); K.det_score = (int *)(m + o_det_sc);
-    K.cand_pt = (mskf_point2f *)(m + o_cpt); K.cand_index = (int *)(m + o_cidx); K.cand_score = (int *)(m + o_csc);
-    K.cand_off = (int *)(m + o_coff); K.cand_cnt = (int *)(m + o_ccnt); K.cell_count = (int *)(m + o_cell);
-    K.t_out0 = (mskf_point2f *)(m + o_t[0]); K.t_out1 = (mskf_point2f *)(m + o_t[1]); K.t_und0 = (mskf_point2f *)(m + o_t[2]); K.t_und1 = (mskf_point2f *)(m + o_t[3]);
-    K.t_status = (uint8_t *)(m + o_t[4]);
-    K.c_out0 = (mskf_point2f *)(m + o_c[0]); K.c_out1 = (mskf_point2f *)(m + o_c[1]); K.c_und0 = (mskf_point2f *)(m + o_c[2]); K.c_und1 = (mskf_point2f *)(m + o_c[3]);
-    K.c_status = (uint8_t *)(m + o_c[4]);
-    K.rs_pair = (double *)(m + o_rs_pair); K.rs_pt = (float *)(m + o_rs_pt); K.rs_scalar = (double *)(m + o_rs_sc);
-    K.cap = cap; K.cand_cap = cand_cap; K.det_cap = det_cap;
+    book_carve(K.mem, D, K.grid);
+    K.dev = D;
     return MSKF_OK;
 }
 
@@ -488,109 +495,112 @@ static void fill_fe_desc(const mskf_stream *s, FeStreamDev &d) {
     d.cell_keys = (unsigned long long *)(s->ctx->cell_arena.d + s->cell_off);
 }
 
-static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, bool copy_cells);
+// The push generation as the 8-bit tag the cell keys carry in their top byte (1 .. 255; 0 is "never written").
+static inline unsigned int push_gen_tag(unsigned long long push_gen) { return (unsigned int)((push_gen - 1) % 255ULL) + 1U; }
+static inline size_t cell_key_bytes(const mskf_stream *s) { return sizeof(unsigned long long) * (size_t)s->fe.det_rows * s->fe.det_cols; }
 
-extern "C" int mskf_fe_push_stereo_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0,
-                                         const uint8_t *const *cam1, int on_device) {
-    return push_batch(ctx, n, streams, cam0, cam1, on_device, true);
-}
-
-// copy_cells = false: the per-cell maxima stay on the device (the bookkeeping kernel of a device frame reads them there)
-static int push_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, bool copy_cells) {
+// A push in the manner of the update batch: plan_push looks at the whole batch and decides everything, touching nothing (no
+// HIP call; every refusal of a push comes from here); push_accepted then waits for the staging, grows the arenas, commits
+// the streams' and the context's fields and enqueues.
+struct PushPlan {
+    size_t cell_bytes = 0;            // the batch's slice of cell_arena (stream i's slice follows stream i - 1's)
+    int max_w = 0, max_h = 0;
+    long long px_pyr = 0, px_det = 0; // timing units: output pixels of the levels 1 .. 3 of both cameras, pixels of cam0 level 0
+};
+static int plan_push(const mskf_ctx *ctx, int n, const mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, PushPlan &P) {
     if (!ctx || n <= 0 || !streams || !cam0 || !cam1) return MSKF_ERR_INVALID;
     // the pinned staging of a pending batch (descriptors, pyramid jobs, the cell arena) may still be in flight
-    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
-    if (rc != MSKF_OK) return rc;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // A push returns once its work is enqueued (the mark behind it is waited for by whoever reads the cell maxima), and its
-    // copy kernel reads the pinned job / descriptor arrays when it runs: a second push straight after the first (push, swap,
-    // push) must not overwrite them before that.  Without this wait the first push could build the pyramid the SECOND one
-    // described and leave its own image with the levels 1 .. 3 of whatever the buffer held before.
-    // This guards the push -> push hand-over of the public (copy_cells) path only: every such push records cell_ev behind its
-    // last command.  A device-frame push (copy_cells = false) records nothing; its staging is protected by the pending frame
-    // batch (mskf_refuse_if_owned above, and _end drains the stream), and after one the wait below is on an older mark that
-    // is already satisfied.
-    if (ctx->cell_mark_recorded && (rc = mskf_wait_event(ctx, &ctx->cell_ev, false)) != MSKF_OK) return rc;
-    rc = ctx->jobs.ensure((size_t)n * 2);
-    if (rc != MSKF_OK) return rc;
-    rc = ctx->desc[0].ensure(n);
-    if (rc != MSKF_OK) return rc;
-    int max_w = 0, max_h = 0;
-    size_t cell_bytes = 0;
-    {
-        for (int i = 0; i < n; ++i) { if (!streams[i] || streams[i]->ctx != ctx) return MSKF_ERR_INVALID; cell_bytes += sizeof(unsigned long long) * (size_t)streams[i]->fe.det_rows * streams[i]->fe.det_cols; }
-        if (cell_bytes > ctx->cell_arena.cap) { rc = ctx->cell_arena.ensure(cell_bytes); if (rc != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
-        ++ctx->push_gen;
-        size_t off = 0;
-        for (int i = 0; i < n; ++i) { streams[i]->cell_off = off; streams[i]->push_gen = ctx->push_gen; off += sizeof(unsigned long long) * (size_t)streams[i]->fe.det_rows * streams[i]->fe.det_cols; }
+    if (const int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        if (!s || s->ctx != ctx || !cam0[i] || !cam1[i]) return MSKF_ERR_INVALID;
+        // on_device 3: level 0 already sits in the stream's own planes (mskf_fe_push_stereo with padded rows)
+        if (on_device == 3 && (cam0[i] != s->pyr[s->i_curr0] || cam1[i] != s->pyr[s->i_curr1])) return MSKF_ERR_INVALID;
+        P.cell_bytes += cell_key_bytes(s);
+        P.max_w = std::max(P.max_w, s->w); P.max_h = std::max(P.max_h, s->h);
+        for (int l = 1; l < MSKF_LEVELS; ++l) P.px_pyr += 2LL * s->lw[l] * s->lh[l];
+        P.px_det += (long long)s->w * s->h;
     }
+    return MSKF_OK;
+}
+
+// An accepted push (the context's device is current).  copy_cells = false: the per-cell maxima stay on the device (the
+// bookkeeping kernel of a device frame reads them there).  The caller drains the stream if this fails (DrainOnError).
+static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, bool copy_cells,
+                         const PushPlan &P) {
+    hipStream_t st = ctx->stream;
+    int rc;
+    // A push returns once its work is enqueued, and its copy kernel reads the pinned job / descriptor arrays when it runs: a
+    // second push straight after the first (push, swap, push) must not overwrite them before that, or the first builds the
+    // pyramid the SECOND one described.  Every public (copy_cells) push records cell_ev behind its last command and the next
+    // one waits for it here.  A device-frame push records nothing: its staging is protected by the pending frame batch
+    // (mskf_refuse_if_owned, and _end drains the stream), and after one this wait is on an older mark, already satisfied.
+    if (ctx->cell_mark_recorded && (rc = mskf_wait_event(ctx, &ctx->cell_ev, false)) != MSKF_OK) return rc;
+    if ((rc = ctx->jobs.ensure((size_t)n * 2)) != MSKF_OK || (rc = ctx->desc[0].ensure(n)) != MSKF_OK) return rc;
+    if (P.cell_bytes > ctx->cell_arena.cap) { if ((rc = ctx->cell_arena.ensure(P.cell_bytes)) != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
+    // ---- commit: the streams belong to this push from here on
+    ++ctx->push_gen;
+    size_t off = 0;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
-        if (!s || s->ctx != ctx || !cam0[i] || !cam1[i]) return MSKF_ERR_INVALID;
-        if (on_device == 3) {
-            // level 0 already sits in the stream's own planes (mskf_fe_push_stereo with padded rows)
-            if (cam0[i] != s->pyr[s->i_curr0] || cam1[i] != s->pyr[s->i_curr1]) return MSKF_ERR_INVALID;
-            s->lvl0[s->i_curr0] = nullptr; s->lvl0[s->i_curr1] = nullptr;
-        } else if (on_device == 2) {
-            // borrowed device images: level 0 is read in place (caller keeps them valid and unchanged until the
-            // second-next push of this stream: the previous frame's cam0 is the LK template of the next frame)
-            s->lvl0[s->i_curr0] = cam0[i];
-            s->lvl0[s->i_curr1] = cam1[i];
-        } else {
-            const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-            s->lvl0[s->i_curr0] = nullptr; s->lvl0[s->i_curr1] = nullptr;
-            MSKF_HIPCHK(hipMemcpyAsync(s->pyr[s->i_curr0], cam0[i], (size_t)s->w * s->h, kind, st));
-            MSKF_HIPCHK(hipMemcpyAsync(s->pyr[s->i_curr1], cam1[i], (size_t)s->w * s->h, kind, st));
-        }
+        s->cell_off = off; off += cell_key_bytes(s);
+        s->push_gen = ctx->push_gen;
+        // on_device 2: borrowed device images, level 0 is read in place (caller keeps them valid and unchanged until the
+        // second-next push of this stream: the previous frame's cam0 is the LK template of the next frame)
+        s->lvl0[s->i_curr0] = on_device == 2 ? cam0[i] : nullptr;
+        s->lvl0[s->i_curr1] = on_device == 2 ? cam1[i] : nullptr;
         s->has_curr = true;
-        max_w = std::max(max_w, s->w); max_h = std::max(max_h, s->h);
     }
-    // pyramid levels 1..3 of both cameras of every stream: ONE launch (k_pyr_down3)
+    // ---- enqueue: level 0 of both cameras unless it is borrowed or already there, then the levels 1 .. 3 of both cameras of
+    // every stream in ONE launch (k_pyr_down3), its jobs staged together with the detector's descriptors
     static_assert(MSKF_LEVELS == 4, "k_pyr_down3 builds exactly the levels 1, 2, 3");
-    {
-        long long px = 0;
-        for (int i = 0; i < n; ++i) {
-            mskf_stream *s = streams[i];
-            for (int c = 0; c < 2; ++c) {
-                Pyr3Job &j = ctx->jobs.h[2 * (size_t)i + c];
-                const int pi = c == 0 ? s->i_curr0 : s->i_curr1;
-                uint8_t *base = s->pyr[pi];
-                j.src = s->lvl0[pi] ? s->lvl0[pi] : base + s->lvl_off[0];
-                j.d1 = base + s->lvl_off[1]; j.d2 = base + s->lvl_off[2]; j.d3 = base + s->lvl_off[3];
-                j.w0 = s->lw[0]; j.h0 = s->lh[0];
-            }
-            for (int l = 1; l < MSKF_LEVELS; ++l) px += 2LL * s->lw[l] * s->lh[l];
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int i = 0; i < n; ++i) {
+        mskf_stream *s = streams[i];
+        const uint8_t *const img[2] = {cam0[i], cam1[i]};
+        for (int c = 0; c < 2; ++c) {
+            const int pi = c == 0 ? s->i_curr0 : s->i_curr1;
+            uint8_t *base = s->pyr[pi];
+            if (on_device != 2 && on_device != 3) MSKF_HIPCHK(hipMemcpyAsync(base, img[c], (size_t)s->w * s->h, kind, st));
+            Pyr3Job &j = ctx->jobs.h[2 * (size_t)i + c];
+            j.src = s->lvl0[pi] ? s->lvl0[pi] : base + s->lvl_off[0];
+            j.d1 = base + s->lvl_off[1]; j.d2 = base + s->lvl_off[2]; j.d3 = base + s->lvl_off[3];
+            j.w0 = s->lw[0]; j.h0 = s->lh[0];
         }
-        // (one staging launch for the pyramid jobs and the detector's descriptors)
-        for (int i = 0; i < n; ++i) fill_fe_desc(streams[i], ctx->desc[0].h[i]);
-        const MskfCopy cp[2] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
-        if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
-        const int ts = mskf_t_begin(ctx, MSKF_K_PYR);
-        fe_launch_pyr_down3(ctx->jobs.d, 2 * n, max_w, max_h, st);
-        mskf_t_end(ctx, ts, px);          // units: output pixels of the three levels
+        fill_fe_desc(s, ctx->desc[0].h[i]);
     }
-    // detector per-cell maxima on cam0 level 0
-    {
-        // the keys carry the push generation in their top byte: a newer push wins every atomicMax, so the key array is
-        // cleared only when it is fresh or the 8-bit generation wraps (not once per frame)
-        const unsigned int gen = (unsigned int)((ctx->push_gen - 1) % 255ULL) + 1U;
-        if (ctx->cell_keys_dirty || gen == 1U) {
-            MSKF_HIPCHK(hipMemsetAsync(ctx->cell_arena.d, 0, ctx->cell_arena.cap, st));
-            ctx->cell_keys_dirty = false;
-        }
-        long long px = 0;
-        for (int i = 0; i < n; ++i) px += (long long)streams[i]->w * streams[i]->h;
-        const int ts = mskf_t_begin(ctx, MSKF_K_DETECT);
-        fe_launch_detect(ctx->desc[0].d, n, max_w, max_h, gen, st);
-        mskf_t_end(ctx, ts, px);
+    const MskfCopy cp[2] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
+    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+    int ts = mskf_t_begin(ctx, MSKF_K_PYR);
+    fe_launch_pyr_down3(ctx->jobs.d, 2 * n, P.max_w, P.max_h, st);
+    mskf_t_end(ctx, ts, P.px_pyr);
+    // detector per-cell maxima on cam0 level 0.  The keys carry the push generation in their top byte: a newer push wins every
+    // atomicMax, so the key array is cleared only when it is fresh or the 8-bit generation wraps (not once per frame)
+    const unsigned int gen = push_gen_tag(ctx->push_gen);
+    if (ctx->cell_keys_dirty || gen == 1U) {
+        MSKF_HIPCHK(hipMemsetAsync(ctx->cell_arena.d, 0, ctx->cell_arena.cap, st));
+        ctx->cell_keys_dirty = false;
     }
+    ts = mskf_t_begin(ctx, MSKF_K_DETECT);
+    fe_launch_detect(ctx->desc[0].d, n, P.max_w, P.max_h, gen, st);
+    mskf_t_end(ctx, ts, P.px_det);
     if (copy_cells) {
-        { const MskfCopy cp = {ctx->cell_arena.h, ctx->cell_arena.d, cell_bytes}; const int crc = mskf_copy_async(ctx, &cp, 1); if (crc != MSKF_OK) return crc; }
-        { const int erc = mskf_wait_event(ctx, &ctx->cell_ev, true); if (erc != MSKF_OK) return erc; }
+        const MskfCopy out = {ctx->cell_arena.h, ctx->cell_arena.d, P.cell_bytes};
+        if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK || (rc = mskf_wait_event(ctx, &ctx->cell_ev, true)) != MSKF_OK) return rc;
         ctx->cell_mark_recorded = true;
     }
     MSKF_HIPCHK(hipGetLastError());
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_push_stereo_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device) {
+    PushPlan P;
+    int rc;
+    if ((rc = plan_push(ctx, n, streams, cam0, cam1, on_device, P)) != MSKF_OK) return rc;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    DrainOnError drain{ctx->stream, true};
+    if ((rc = push_accepted(ctx, n, streams, cam0, cam1, on_device, true, P)) != MSKF_OK) return rc;
+    drain.armed = false;
     return MSKF_OK;
 }
 
@@ -599,19 +609,17 @@ extern "C" int mskf_fe_push_stereo(mskf_stream *s, const uint8_t *cam0, const ui
     if (!s || !cam0 || !cam1) return MSKF_ERR_INVALID;
     if (width != s->w || height != s->h || pitch < width) { mskf_set_error("image size differs from the calibration"); return MSKF_ERR_INVALID; }
     s->time_stamp = time_stamp;
+    const uint8_t *a[1] = {cam0}, *b[1] = {cam1};
+    mskf_stream *ss[1] = {s};
     if (pitch != width) {
         // padded rows: 2D copies straight into the stream's own level-0 planes (dense, pitch = width), then the batch
         // path with "level 0 already resident" (on_device = 3): no temporary allocation, nothing to free or leak
         MSKF_HIPCHK(hipSetDevice(s->ctx->device));
         MSKF_HIPCHK(hipMemcpy2DAsync(s->pyr[s->i_curr0], width, cam0, pitch, width, height, hipMemcpyHostToDevice, s->ctx->stream));
         MSKF_HIPCHK(hipMemcpy2DAsync(s->pyr[s->i_curr1], width, cam1, pitch, width, height, hipMemcpyHostToDevice, s->ctx->stream));
-        const uint8_t *a[1] = {s->pyr[s->i_curr0]}, *b[1] = {s->pyr[s->i_curr1]};
-        mskf_stream *ss[1] = {s};
-        return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, 3);
+        a[0] = s->pyr[s->i_curr0]; b[0] = s->pyr[s->i_curr1];
     }
-    const uint8_t *a[1] = {cam0}, *b[1] = {cam1};
-    mskf_stream *ss[1] = {s};
-    return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, 0);
+    return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, pitch != width ? 3 : 0);
 }
 
 extern "C" int mskf_fe_push_stereo_device(mskf_stream *s, const uint8_t *d_cam0, const uint8_t *d_cam1, int width, int height,
@@ -626,11 +634,10 @@ extern "C" int mskf_fe_push_stereo_device(mskf_stream *s, const uint8_t *d_cam0,
 
 // keys -> corners: gen (8) | score (24) | ~order (32), order = row-major position inside the cell; a key of another
 // generation (an older push, or 0) means no corner in this one
-static inline unsigned int stream_gen(const mskf_stream *s) { return (unsigned int)((s->push_gen - 1) % 255ULL) + 1U; }
 static inline long long score_of_key(unsigned long long k, unsigned int gen) { return (k >> 56) == gen ? (long long)((k >> 32) & 0xFFFFFFULL) : 0LL; }
 static inline void corner_of_key(const mskf_stream *s, int cell, unsigned long long k, mskf_corner &o) {
     o.cell = cell;
-    const long long sc = score_of_key(k, stream_gen(s));
+    const long long sc = score_of_key(k, push_gen_tag(s->push_gen));
     if (sc == 0) { o.x = 0.f; o.y = 0.f; o.score = 0; return; }
     const int cols = s->fe.det_cols, cw = s->det_cw, ch = s->det_ch;
     const unsigned int order = 0xFFFFFFFFu - (unsigned int)(k & 0xFFFFFFFFULL);
@@ -674,7 +681,7 @@ extern "C" int mskf_fe_get_cell_candidates(mskf_stream *s, int min_score, mskf_c
     const int rc = cell_keys_ready(s);
     if (rc != MSKF_OK) return rc;
     const unsigned long long *keys = (const unsigned long long *)(s->ctx->cell_arena.h + s->cell_off);
-    const unsigned int gen = stream_gen(s);
+    const unsigned int gen = push_gen_tag(s->push_gen);
     int m = 0;
     for (int cell = 0; cell < n; ++cell) {
         const unsigned long long k = keys[cell];
@@ -691,6 +698,16 @@ extern "C" int mskf_fe_track_batch(mskf_ctx *ctx, int n, mskf_stream *const *str
     return rc != MSKF_OK ? rc : mskf_fe_track_batch_end(ctx);
 }
 
+// One stream's result block of a track batch in trk_out, for np points: out0, out1, und0, und1, status.  Returns its size.
+struct TrackOut { mskf_point2f *out0, *out1, *und0, *und1; uint8_t *status; };
+static size_t track_out_block(char *base, size_t np, TrackOut &o) {       // (a null base only asks for the size)
+    const uintptr_t b = (uintptr_t)base;
+    const size_t pts = sizeof(mskf_point2f) * np;
+    o.out0 = (mskf_point2f *)b; o.out1 = (mskf_point2f *)(b + pts); o.und0 = (mskf_point2f *)(b + 2 * pts); o.und1 = (mskf_point2f *)(b + 3 * pts);
+    o.status = (uint8_t *)(b + 4 * pts);
+    return (4 * pts + np + 63) & ~(size_t)63;
+}
+
 extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_fe_track_args *args) {
     if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
     int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
@@ -702,9 +719,8 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     if (rc != MSKF_OK) return rc;
     int max_pts = 0;
     size_t in_bytes = 0, out_bytes = 0;
-    std::vector<size_t> in_off(n);
-    std::vector<size_t> &out_off = ctx->pend_trk.out_off;
-    out_off.resize(n);
+    std::vector<size_t> &in_off = ctx->pend_trk.in_off, &out_off = ctx->pend_trk.out_off;      // (no batch is pending: nobody reads them)
+    in_off.resize(n); out_off.resize(n);
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -713,9 +729,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         if (a.n > 0 && (!a.in_pts || !a.out0 || !a.out1 || !a.und0 || !a.und1 || !a.status)) return MSKF_ERR_INVALID;
         if (!s->has_curr) { mskf_set_error("no stereo pair pushed yet"); return MSKF_ERR_INVALID; }
         in_off[i] = in_bytes; out_off[i] = out_bytes;
-        const size_t np = (size_t)a.n;
-        in_bytes += (sizeof(mskf_point2f) * np + 63) & ~(size_t)63;
-        out_bytes += (4 * sizeof(mskf_point2f) * np + np + 63) & ~(size_t)63;   // out0 out1 und0 und1 status
+        TrackOut o;
+        in_bytes += (sizeof(mskf_point2f) * (size_t)a.n + 63) & ~(size_t)63;
+        out_bytes += track_out_block(nullptr, (size_t)a.n, o);
         max_pts = std::max(max_pts, a.n);
     }
     if (max_pts <= 0) return MSKF_OK;      // nothing to track: no batch pending, _end is a no-op
@@ -731,9 +747,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         std::memcpy(d.Hpred, a.Hpred, sizeof(d.Hpred));
         if (np) std::memcpy(ctx->trk_in.h + in_off[i], a.in_pts, sizeof(mskf_point2f) * np);
         d.in_pts = (const mskf_point2f *)(ctx->trk_in.d + in_off[i]);
-        char *o = ctx->trk_out.d + out_off[i];
-        d.out0 = (mskf_point2f *)o; d.out1 = d.out0 + np; d.und0 = d.out1 + np; d.und1 = d.und0 + np;
-        d.status = (uint8_t *)(d.und1 + np);
+        TrackOut o;
+        track_out_block(ctx->trk_out.d + out_off[i], np, o);
+        d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
     DrainOnError drain{st};
     {
@@ -762,28 +778,24 @@ extern "C" int mskf_fe_track_batch_end(mskf_ctx *ctx) {
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     const int rc = mskf_batch_finish(ctx, ctx->pend_trk);
     if (rc != MSKF_OK) return rc;
-    const int n = ctx->pend_trk.n;
-    const mskf_fe_track_args *args = ctx->pend_trk.args;
-    const std::vector<size_t> &out_off = ctx->pend_trk.out_off;
-    const int ts = ctx->pend_trk.ts;
+    const mskf_ctx::PendingTrack &T = ctx->pend_trk;
     const auto t_h1 = std::chrono::steady_clock::now();
     long long tracks_t = 0, tracks_s = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_track_args &a = args[i];
+    for (int i = 0; i < T.n; ++i) {
+        const mskf_fe_track_args &a = T.args[i];
         const size_t np = (size_t)a.n;
         if (!np) continue;
-        const char *o = ctx->trk_out.h + out_off[i];
-        std::memcpy(a.out0, o, sizeof(mskf_point2f) * np);
-        std::memcpy(a.out1, o + sizeof(mskf_point2f) * np, sizeof(mskf_point2f) * np);
-        std::memcpy(a.und0, o + 2 * sizeof(mskf_point2f) * np, sizeof(mskf_point2f) * np);
-        std::memcpy(a.und1, o + 3 * sizeof(mskf_point2f) * np, sizeof(mskf_point2f) * np);
-        std::memcpy(a.status, o + 4 * sizeof(mskf_point2f) * np, np);
+        TrackOut o;
+        track_out_block(ctx->trk_out.h + T.out_off[i], np, o);
+        const size_t pts = sizeof(mskf_point2f) * np;
+        std::memcpy(a.out0, o.out0, pts); std::memcpy(a.out1, o.out1, pts); std::memcpy(a.und0, o.und0, pts); std::memcpy(a.und1, o.und1, pts);
+        std::memcpy(a.status, o.status, np);
         // units of an LK launch = point tracks it executed: temporal (n of the temporal streams), stereo (the points that
         // passed the temporal gate, or all n of a stereo-only stream)
         if (a.do_temporal) { tracks_t += (long long)np; for (size_t k = 0; k < np; ++k) tracks_s += (a.status[k] & 1); }
         else tracks_s += (long long)np;
     }
-    mskf_t_set_units(ctx, ts, MSKF_K_LK, tracks_t + tracks_s);      // point tracks of the launch: temporal + stereo
+    mskf_t_set_units(ctx, T.ts, MSKF_K_LK, tracks_t + tracks_s);      // point tracks of the launch: temporal + stereo
     mskf_t_collect(ctx);
     if (ctx->t_gate) ctx->host_s[3] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h1).count();
     return MSKF_OK;
@@ -803,15 +815,20 @@ extern "C" int mskf_fe_swap(mskf_stream *s) {
 }
 
 // ------------------------------------------------------------------------------------------ a whole frame on the device
-extern "C" int mskf_fe_grid_capacity(mskf_stream *s) { return s ? s->book.cap : 0; }
+extern "C" int mskf_fe_grid_capacity(mskf_stream *s) { return s ? s->book.dev.cap : 0; }
+
+static int refuse_host_books() {
+    mskf_set_error("this stream keeps its books on the host (grid_min / grid_max above the device limit)");
+    return MSKF_ERR_UNSUPPORTED;
+}
 
 extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const int32_t *lifetime, const mskf_point2f *cam0, const mskf_point2f *cam1,
                                 const mskf_point2f *und0, const mskf_point2f *und1, uint64_t next_feature_id, const int32_t tracking_counters[3],
                                 uint64_t ransac_draws) {
     if (!s || n < 0 || (n && (!id || !lifetime || !cam0 || !cam1 || !und0 || !und1))) return MSKF_ERR_INVALID;
     mskf_stream::Book &K = s->book;
-    if (!K.cap) { mskf_set_error("this stream keeps its books on the host (grid_min / grid_max above the device limit)"); return MSKF_ERR_UNSUPPORTED; }
-    if (n > K.cap) return MSKF_ERR_CAPACITY;
+    if (!K.dev.cap) return refuse_host_books();
+    if (n > K.dev.cap) return MSKF_ERR_CAPACITY;
     mskf_ctx *ctx = s->ctx;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -838,7 +855,7 @@ extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const
     if (tracking_counters) { h.after_tracking = tracking_counters[0]; h.after_matching = tracking_counters[1]; h.after_ransac = tracking_counters[2]; }
     const MskfCopy cp[7] = {{G.id, hs, 8 * (size_t)n}, {G.lifetime, hs + n8, 4 * (size_t)n}, {G.cam0, hs + n8 + n4, 8 * (size_t)n},
                             {G.cam1, hs + 2 * n8 + n4, 8 * (size_t)n}, {G.und0, hs + 3 * n8 + n4, 8 * (size_t)n},
-                            {G.und1, hs + 4 * n8 + n4, 8 * (size_t)n}, {K.st, hs + o_st, sizeof(FeBookState)}};
+                            {G.und1, hs + 4 * n8 + n4, 8 * (size_t)n}, {K.dev.st, hs + o_st, sizeof(FeBookState)}};
     const int crc = mskf_copy_async(ctx, cp, 7);
     MSKF_HIPCHK(hipStreamSynchronize(st));
     if (crc != MSKF_OK) return crc;
@@ -848,23 +865,25 @@ extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const
 
 extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1,
                                          int on_device, mskf_fe_frame_args *args) {
-    if (!ctx || n <= 0 || !streams || !cam0 || !cam1 || !args) return MSKF_ERR_INVALID;
-    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE);
-    if (rc != MSKF_OK) return rc;
+    // ---- plan: the push's checks (arguments, no pending batch, streams, images), then the frame's own; nothing is touched
+    // before both have passed
+    PushPlan P;
+    int rc;
+    if (!args) return MSKF_ERR_INVALID;
+    if ((rc = plan_push(ctx, n, streams, cam0, cam1, on_device, P)) != MSKF_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream::Book &K = streams[i]->book;
+        if (!K.dev.cap) return refuse_host_books();
+        if (!K.grid_set) { mskf_set_error("no grid on the device yet: the first frame goes through mskf_fe_track + mskf_fe_set_grid"); return MSKF_ERR_INVALID; }
+        const mskf_fe_frame_args &a = args[i];
+        if (a.capacity < K.dev.cap || !a.id || !a.lifetime || !a.cam0 || !a.cam1 || !a.und0 || !a.und1) return MSKF_ERR_INVALID;
+    }
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    for (int i = 0; i < n; ++i) {
-        mskf_stream *s = streams[i];
-        if (!s || s->ctx != ctx) return MSKF_ERR_INVALID;
-        if (!s->book.cap) { mskf_set_error("this stream keeps its books on the host (grid_min / grid_max above the device limit)"); return MSKF_ERR_UNSUPPORTED; }
-        if (!s->book.grid_set) { mskf_set_error("no grid on the device yet: the first frame goes through mskf_fe_track + mskf_fe_set_grid"); return MSKF_ERR_INVALID; }
-        const mskf_fe_frame_args &a = args[i];
-        if (a.capacity < s->book.cap || !a.id || !a.lifetime || !a.cam0 || !a.cam1 || !a.und0 || !a.und1) return MSKF_ERR_INVALID;
-    }
     const auto t_h0 = std::chrono::steady_clock::now();
-    DrainOnError drain{st, true};        // (push_batch enqueues the images, the pyramids and the detector)
-    rc = push_batch(ctx, n, streams, cam0, cam1, on_device, false);
-    if (rc != MSKF_OK) return rc;
+    // ---- accepted: a failure from here on drains the stream before it is reported
+    DrainOnError drain{st, true};        // (the push enqueues the images, the pyramids and the detector)
+    if ((rc = push_accepted(ctx, n, streams, cam0, cam1, on_device, false, P)) != MSKF_OK) return rc;
     if ((rc = ctx->desc[1].ensure(n)) != MSKF_OK || (rc = ctx->desc[2].ensure(n)) != MSKF_OK || (rc = ctx->book_desc.ensure(n)) != MSKF_OK) return rc;
     std::vector<size_t> &out_off = ctx->pend_frame.out_off;
     out_off.resize(n);
@@ -872,64 +891,46 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     int max_prev = 0, max_cand_est = 0;
     for (int i = 0; i < n; ++i) {
         const mskf_stream::Book &K = streams[i]->book;
+        const FeBookDev &D = K.dev;
+        FeExport x;
         out_off[i] = out_bytes;
-        out_bytes += (64 + 44 * (size_t)K.cap + 255) & ~(size_t)255;
-        scratch_bytes = std::max(scratch_bytes, 4 * fe_book_scratch_ints(K.cap, K.cand_cap, K.det_cap, K.n_codes, K.det_cap));
+        out_bytes += (fe_book_export(nullptr, D.cap, x) + 255) & ~(size_t)255;
+        scratch_bytes = std::max(scratch_bytes, 4 * fe_book_scratch_ints(D.cap, D.cand_cap, D.det_cap, D.n_codes, D.det_cap));
         max_prev = std::max(max_prev, K.n_prev);
         // candidates are counted on the device: the launch is sized from the last frame's count, a block takes several point
         // groups if there are more this time
-        const int est = K.n_cand_last < 0 ? K.cand_cap / 2 : std::min(K.cand_cap, K.n_cand_last + K.n_cand_last / 2 + 32);
+        const int est = K.n_cand_last < 0 ? D.cand_cap / 2 : std::min(D.cand_cap, K.n_cand_last + K.n_cand_last / 2 + 32);
         max_cand_est = std::max(max_cand_est, est);
     }
     if ((rc = ctx->book_out.ensure(out_bytes)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
-        mskf_stream *s = streams[i];
-        mskf_stream::Book &K = s->book;
-        const mskf_fe_cfg &fe = s->fe;
+        const mskf_stream *s = streams[i];
+        const mskf_stream::Book &K = s->book;
+        const FeBookDev &D = K.dev;
         // first track call: the previous grid's cam0 points, temporal + stereo
         FeStreamDev &d1 = ctx->desc[1].h[i];
         fill_fe_desc(s, d1);
         d1.n_pts = K.n_prev; d1.n_pts_dev = nullptr; d1.do_temporal = 1;
         std::memcpy(d1.Hpred, args[i].Hpred, sizeof(d1.Hpred));
         d1.in_pts = K.grid[K.parity].cam0;
-        d1.out0 = K.t_out0; d1.out1 = K.t_out1; d1.und0 = K.t_und0; d1.und1 = K.t_und1; d1.status = K.t_status;
+        d1.out0 = (mskf_point2f *)D.t_out0; d1.out1 = (mskf_point2f *)D.t_out1; d1.und0 = (mskf_point2f *)D.t_und0; d1.und1 = (mskf_point2f *)D.t_und1; d1.status = (uint8_t *)D.t_status;
         // second track call: the candidates fe_book1 leaves in the stream's list, stereo only
         FeStreamDev &d2 = ctx->desc[2].h[i];
         fill_fe_desc(s, d2);
-        d2.n_pts = 0; d2.n_pts_dev = &K.st->n_cand; d2.do_temporal = 0;
+        d2.n_pts = 0; d2.n_pts_dev = &D.st->n_cand; d2.do_temporal = 0;
         d2.Hpred[0] = d2.Hpred[4] = d2.Hpred[8] = 1.0;
-        d2.in_pts = K.cand_pt;
-        d2.out0 = K.c_out0; d2.out1 = K.c_out1; d2.und0 = K.c_und0; d2.und1 = K.c_und1; d2.status = K.c_status;
+        d2.in_pts = D.cand_pt;
+        d2.out0 = (mskf_point2f *)D.c_out0; d2.out1 = (mskf_point2f *)D.c_out1; d2.und0 = (mskf_point2f *)D.c_und0; d2.und1 = (mskf_point2f *)D.c_und1; d2.status = (uint8_t *)D.c_status;
+        // the books: the stream's constant descriptor plus what this frame brings
         FeBookDev &B = ctx->book_desc.h[i];
-        std::memset(&B, 0, sizeof(B));
-        B.grid_row = fe.grid_row; B.grid_col = fe.grid_col; B.grid_min = fe.grid_min_feature_num; B.grid_max = fe.grid_max_feature_num;
-        B.n_codes = K.n_codes; B.n_cells = K.n_cells; B.grid_w = K.grid_w; B.grid_h = K.grid_h;
-        B.det_rows = fe.det_rows; B.det_cols = fe.det_cols; B.det_cw = s->det_cw; B.det_ch = s->det_ch;
-        B.thr_score = fe.fast_threshold * 256;
-        B.q4 = (fe.compat_flags & MSKF_COMPAT_Q4_RESPONSE_INDEX) ? 1 : 0;
-        // twoPointRansac between the tracks (:482-500; commented out in the reference, Q5): iterations as :920-921
-        B.ransac = (fe.compat_flags & MSKF_COMPAT_Q5_NO_RANSAC) ? 0 : 1;
-        B.ransac_iters = static_cast<int>(std::ceil(std::log(1 - 0.99) / std::log(1 - 0.7 * 0.7)));
-        B.ransac_thr = fe.ransac_threshold;
-        B.ransac_npu[0] = 2.0 / (s->cam0.K[0] + s->cam0.K[1]); B.ransac_npu[1] = 2.0 / (s->cam1.K[0] + s->cam1.K[1]);
+        B = D;
+        B.gen = push_gen_tag(s->push_gen);
         std::memcpy(B.R_p_c, args[i].R_p_c, sizeof(B.R_p_c));
-        B.rs_pair = K.rs_pair; B.rs_pt = K.rs_pt; B.rs_scalar = K.rs_scalar;
-        B.cap = K.cap; B.cand_cap = K.cand_cap; B.det_cap = K.det_cap;
-        B.gen = (unsigned int)((s->push_gen - 1) % 255ULL) + 1U;
-        B.st = K.st;
-        B.prev = K.grid[K.parity]; B.curr = K.grid[K.parity ^ 1]; B.tracked = K.grid[2];
-        B.t_out0 = K.t_out0; B.t_out1 = K.t_out1; B.t_und0 = K.t_und0; B.t_und1 = K.t_und1; B.t_status = K.t_status;
+        B.prev = K.grid[K.parity]; B.curr = K.grid[K.parity ^ 1];
         B.cell_keys = (const unsigned long long *)(ctx->cell_arena.d + s->cell_off);
-        B.det_pt = K.det_pt; B.det_score = K.det_score;
-        B.cand_pt = K.cand_pt; B.cand_index = K.cand_index; B.cand_score = K.cand_score; B.cand_off = K.cand_off; B.cand_cnt = K.cand_cnt;
-        B.c_out0 = K.c_out0; B.c_out1 = K.c_out1; B.c_und0 = K.c_und0; B.c_und1 = K.c_und1; B.c_status = K.c_status;
-        B.cell_count = K.cell_count;
-        char *o = ctx->book_out.d + out_off[i];
-        B.x_info = (int *)o;
-        B.x_id = (unsigned long long *)(o + 64);
-        B.x_lifetime = (int *)(o + 64 + 8 * (size_t)K.cap);
-        B.x_cam0 = (mskf_point2f *)(o + 64 + 12 * (size_t)K.cap);
-        B.x_cam1 = B.x_cam0 + K.cap; B.x_und0 = B.x_cam1 + K.cap; B.x_und1 = B.x_und0 + K.cap;
+        FeExport x;
+        fe_book_export(ctx->book_out.d + out_off[i], D.cap, x);
+        B.x_info = x.info; B.x_id = x.id; B.x_lifetime = x.lifetime; B.x_cam0 = x.cam0; B.x_cam1 = x.cam1; B.x_und0 = x.und0; B.x_und1 = x.und1;
     }
     {
         const MskfCopy cp[3] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
@@ -976,25 +977,21 @@ extern "C" int mskf_fe_frame_batch_end(mskf_ctx *ctx) {
     long long tracks1 = 0, tracks2 = 0;
     bool overflow = false;
     for (int i = 0; i < F.n; ++i) {
-        mskf_stream *s = F.streams[i];
-        mskf_stream::Book &K = s->book;
+        mskf_stream::Book &K = F.streams[i]->book;
         mskf_fe_frame_args &a = F.args[i];
-        const char *o = ctx->book_out.h + F.out_off[i];
-        const int *info = (const int *)o;
-        const int m = info[0];
-        if (m < 0 || m > K.cap || info[8]) { overflow = true; continue; }
-        a.n = m; a.n_candidates = info[1];
-        a.before_tracking = info[2]; a.after_tracking = info[3]; a.after_matching = info[4]; a.after_ransac = info[5];
-        a.next_feature_id = (uint64_t)(unsigned int)info[6] | ((uint64_t)(unsigned int)info[7] << 32);
-        a.n_new = info[9];
-        a.ransac_draws = (uint64_t)(unsigned int)info[12] | ((uint64_t)(unsigned int)info[13] << 32);
-        std::memcpy(a.id, o + 64, 8 * (size_t)m);
-        std::memcpy(a.lifetime, o + 64 + 8 * (size_t)K.cap, 4 * (size_t)m);
-        const char *p = o + 64 + 12 * (size_t)K.cap;
-        std::memcpy(a.cam0, p, 8 * (size_t)m);
-        std::memcpy(a.cam1, p + 8 * (size_t)K.cap, 8 * (size_t)m);
-        std::memcpy(a.und0, p + 16 * (size_t)K.cap, 8 * (size_t)m);
-        std::memcpy(a.und1, p + 24 * (size_t)K.cap, 8 * (size_t)m);
+        FeExport x;
+        fe_book_export(ctx->book_out.h + F.out_off[i], K.dev.cap, x);
+        const int *info = x.info;
+        const int m = info[FX_N_CURR];
+        if (m < 0 || m > K.dev.cap || info[FX_OVERFLOW]) { overflow = true; continue; }
+        a.n = m; a.n_candidates = info[FX_N_CAND];
+        a.before_tracking = info[FX_BEFORE_TRACKING]; a.after_tracking = info[FX_AFTER_TRACKING]; a.after_matching = info[FX_AFTER_MATCHING]; a.after_ransac = info[FX_AFTER_RANSAC];
+        a.next_feature_id = (uint64_t)(unsigned int)info[FX_NEXT_ID_LO] | ((uint64_t)(unsigned int)info[FX_NEXT_ID_HI] << 32);
+        a.n_new = info[FX_N_NEW];
+        a.ransac_draws = (uint64_t)(unsigned int)info[FX_RANSAC_DRAWS_LO] | ((uint64_t)(unsigned int)info[FX_RANSAC_DRAWS_HI] << 32);
+        const size_t pts = sizeof(mskf_point2f) * (size_t)m;
+        std::memcpy(a.id, x.id, sizeof(*x.id) * (size_t)m); std::memcpy(a.lifetime, x.lifetime, sizeof(*x.lifetime) * (size_t)m);
+        std::memcpy(a.cam0, x.cam0, pts); std::memcpy(a.cam1, x.cam1, pts); std::memcpy(a.und0, x.und0, pts); std::memcpy(a.und1, x.und1, pts);
         tracks1 += (long long)a.before_tracking + (a.before_tracking > 0 ? a.after_tracking : 0);
         tracks2 += a.n_candidates;
         K.n_prev = m; K.n_cand_last = a.n_candidates;

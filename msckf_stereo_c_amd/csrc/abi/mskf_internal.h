@@ -101,7 +101,13 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 //   a pending update owns ekf_desc, upd_in and upd_out;
 //   a pending position-variance read-out owns pred_arena (its kernel reads descriptors from and writes results into the host side).
 // Every _begin and every batch call that writes an arena refuses while the owner is pending: MSKF_ERR_INVALID, and the
-// error message names the pending batch.
+// error message names the pending batch.  What each step of such a call may touch:
+//   plan    (plan_push, plan_update, a _begin's own checks): reads the context and the streams, makes no HIP call; every
+//           refusal comes from here, so a refused call has changed no stream and no context and has enqueued nothing;
+//   grow    the arenas' ensure() (a push first waits for the previous push's mark): allocation only;
+//   commit  the streams' and the context's own fields (push generation, cell slices, level-0 planes, has_curr);
+//   enqueue the arenas, copies and launches, under a DrainOnError; last the mark (mskf_batch_arm), and only behind it what a
+//           finished frame rotates (parity, pyramid roles).
 enum MskfArenas { MSKF_ARENAS_FE, MSKF_ARENAS_UPDATE, MSKF_ARENAS_PRED };
 int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which);
 
@@ -165,7 +171,7 @@ struct mskf_ctx {
     // batches between their *_begin and *_end call (PendingBatch)
     struct PendingTrack : PendingBatch {
         int n = 0; const mskf_fe_track_args *args = nullptr;
-        std::vector<size_t> out_off; int ts = -1;
+        std::vector<size_t> in_off, out_off; int ts = -1;      // per stream, written by _begin's planning step; storage reused from call to call
     } pend_trk;
     struct PendingUpdate : PendingBatch {
         bool launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
@@ -214,14 +220,9 @@ struct mskf_stream {
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;
-        int cap = 0, cand_cap = 0, det_cap = 0, n_codes = 0, n_cells = 0, grid_w = 0, grid_h = 0;
-        FeBookState *st = nullptr;
-        FeGridArr grid[3];                         // [parity], [parity ^ 1]: previous / current grid; [2]: this frame's survivors
-        mskf_point2f *det_pt = nullptr; int *det_score = nullptr;
-        mskf_point2f *cand_pt = nullptr; int *cand_index = nullptr, *cand_score = nullptr, *cand_off = nullptr, *cand_cnt = nullptr, *cell_count = nullptr;
-        mskf_point2f *t_out0 = nullptr, *t_out1 = nullptr, *t_und0 = nullptr, *t_und1 = nullptr; uint8_t *t_status = nullptr;
-        mskf_point2f *c_out0 = nullptr, *c_out1 = nullptr, *c_und0 = nullptr, *c_und1 = nullptr; uint8_t *c_status = nullptr;
-        double *rs_pair = nullptr, *rs_scalar = nullptr; float *rs_pt = nullptr;     // scratch of the 2-point RANSAC (fe_book.h)
+        FeBookDev dev{};                           // what is constant for the stream's life, filled once by book_alloc (dev.cap == 0: books on the
+                                                   // host); a frame copies it and sets gen, R_p_c, prev / curr, cell_keys and the x_* pointers
+        FeGridArr grid[3];                         // [parity], [parity ^ 1]: previous / current grid; [2]: this frame's survivors (== dev.tracked)
         int parity = 0;                            // grid[parity] holds the published grid of the last frame
         int n_prev = 0, n_cand_last = -1;          // host copies of the counts (launch sizing)
         bool grid_set = false;

@@ -74,7 +74,7 @@ struct FeBookState {        // per stream, persistent in HBM
     unsigned long long ransac_draws;    // ImageProcessor::ransac_draws: numbers drawn so far by the counter-based generator of twoPointRansac
 };
 
-struct FeBookDev {          // everything the two kernels need for one stream (built by the host per frame)
+struct FeBookDev {          // everything the two kernels need for one stream (the host keeps the constant part per stream and completes it per frame)
     // configuration
     int grid_row, grid_col, grid_min, grid_max, n_codes, n_cells;
     int grid_w, grid_h;                 // pixels per grid cell (:250-251)
@@ -110,11 +110,40 @@ struct FeBookDev {          // everything the two kernels need for one stream (b
     const uint8_t *c_status;
     int *cell_count;                    // tracked features per grid code, n_codes (written by fe_book1, read by fe_book2)
     // export: what the host receives (one D2H copy per batch)
-    int *x_info;                        // 16 ints: n_curr, n_cand, before/after tracking x4, next_id lo/hi, overflow, n_new, n_det, n_tr, ransac_draws lo/hi
+    int *x_info;                        // FX_WORDS ints, indexed by FeXInfo
     unsigned long long *x_id;
     int *x_lifetime;
     mskf_point2f *x_cam0, *x_cam1, *x_und0, *x_und1;
 };
+
+// The words of x_info (fe_book2 writes them, mskf_fe_frame_batch_end reads them).
+enum FeXInfo {
+    FX_N_CURR, FX_N_CAND, FX_BEFORE_TRACKING, FX_AFTER_TRACKING, FX_AFTER_MATCHING, FX_AFTER_RANSAC, FX_NEXT_ID_LO, FX_NEXT_ID_HI,
+    FX_OVERFLOW, FX_N_NEW, FX_N_DET, FX_N_TRACKED, FX_RANSAC_DRAWS_LO, FX_RANSAC_DRAWS_HI,
+    FX_WORDS = 16
+};
+
+// One stream's export block in the batch's result arena: x_info, then the six arrays of the published grid with `cap`
+// entries each.  Returns the block's size; the host sizes the arena, fills the x_* pointers (device side of the arena) and
+// reads the results (host side) through this one definition.
+struct FeExport {
+    int *info;
+    unsigned long long *id;
+    int *lifetime;
+    mskf_point2f *cam0, *cam1, *und0, *und1;
+};
+FB_FN size_t fe_book_export(char *base, int cap, FeExport &x) {       // (a null base only asks for the size)
+    const size_t n = (size_t)cap;
+    uintptr_t p = (uintptr_t)base;
+    x.info = (int *)p; p += sizeof(int) * FX_WORDS;
+    x.id = (unsigned long long *)p; p += sizeof(unsigned long long) * n;
+    x.lifetime = (int *)p; p += sizeof(int) * n;
+    x.cam0 = (mskf_point2f *)p; p += sizeof(mskf_point2f) * n;
+    x.cam1 = (mskf_point2f *)p; p += sizeof(mskf_point2f) * n;
+    x.und0 = (mskf_point2f *)p; p += sizeof(mskf_point2f) * n;
+    x.und1 = (mskf_point2f *)p; p += sizeof(mskf_point2f) * n;
+    return (size_t)(p - (uintptr_t)base);
+}
 
 // Workgroup scratch (LDS on the device), carved from one int array by fe_book_scratch_init.
 struct FeBookScratch {
@@ -596,12 +625,12 @@ FB_FN void fe_book2(const FeBookDev &B, FeBookScratch &L) {
         st.n_curr = n_out;
         st.next_id = id0 + (unsigned long long)n_new;
         st.n_prev = n_out;
-        B.x_info[0] = n_out; B.x_info[1] = n_cand; B.x_info[2] = st.before_tracking; B.x_info[3] = st.after_tracking;
-        B.x_info[4] = st.after_matching; B.x_info[5] = st.after_ransac;
+        B.x_info[FX_N_CURR] = n_out; B.x_info[FX_N_CAND] = n_cand; B.x_info[FX_BEFORE_TRACKING] = st.before_tracking; B.x_info[FX_AFTER_TRACKING] = st.after_tracking;
+        B.x_info[FX_AFTER_MATCHING] = st.after_matching; B.x_info[FX_AFTER_RANSAC] = st.after_ransac;
         const unsigned long long nid = id0 + (unsigned long long)n_new;
-        B.x_info[6] = (int)(unsigned int)(nid & 0xFFFFFFFFULL); B.x_info[7] = (int)(unsigned int)(nid >> 32);
-        B.x_info[8] = st.overflow; B.x_info[9] = n_new; B.x_info[10] = st.n_det; B.x_info[11] = n_tr;
-        B.x_info[12] = (int)(unsigned int)(st.ransac_draws & 0xFFFFFFFFULL); B.x_info[13] = (int)(unsigned int)(st.ransac_draws >> 32);
+        B.x_info[FX_NEXT_ID_LO] = (int)(unsigned int)(nid & 0xFFFFFFFFULL); B.x_info[FX_NEXT_ID_HI] = (int)(unsigned int)(nid >> 32);
+        B.x_info[FX_OVERFLOW] = st.overflow; B.x_info[FX_N_NEW] = n_new; B.x_info[FX_N_DET] = st.n_det; B.x_info[FX_N_TRACKED] = n_tr;
+        B.x_info[FX_RANSAC_DRAWS_LO] = (int)(unsigned int)(st.ransac_draws & 0xFFFFFFFFULL); B.x_info[FX_RANSAC_DRAWS_HI] = (int)(unsigned int)(st.ransac_draws >> 32);
     }
     FB_SYNC();
 }

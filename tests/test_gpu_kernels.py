@@ -839,46 +839,202 @@ def test_compression_mode_is_validated(gpu_ctx, oracle):
             capi.Stream(gpu_ctx, calib, default_fe_cfg(), default_ekf_cfg(compression_mode=bad))
 
 
+def _status(call, *a, **kw):
+    """The mskf status a wrapper call ends with (0: accepted)."""
+    try:
+        call(*a, **kw)
+        return 0
+    except capi.MskfError as e:
+        return e.code
+
+
 def test_device_frame_entry_points_refuse_what_they_cannot_do(gpu_ctx, oracle):
     """mskf_fe_frame_batch_* (whole front-end frames on the device): no grid handed over yet, output arrays too small and
     per-cell limits above the kernels' bound are refused with a status and a message, never silently; the 2-point RANSAC
     configuration (refused until round 4, when the RANSAC moved from the host into the frame) is accepted."""
-    import ctypes as C
-    from msckf_stereo_c_amd.ctypes_types import COMPAT_REFERENCE, POINT2F
+    from msckf_stereo_c_amd.ctypes_types import COMPAT_REFERENCE
     L = gpu_ctx.L
-    L.mskf_fe_grid_capacity.argtypes = [C.c_void_p]
-    L.mskf_fe_frame_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(capi.FeFrameArgs)]
-    L.mskf_fe_set_grid.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p, C.c_uint64]
     w, h = 376, 240
     calib = oracle.euroc_calib(w, h)
     img = np.zeros((h, w), np.uint8)
 
     def frame(stream, cap):
-        ids = np.zeros(max(cap, 1), np.uint64); life = np.zeros(max(cap, 1), np.int32)
-        pts = [np.zeros(max(cap, 1), POINT2F) for _ in range(4)]
-        a = capi.FeFrameArgs()
-        a.Hpred[0] = a.Hpred[4] = a.Hpred[8] = 1.0
-        a.capacity = cap
-        a.id, a.lifetime = ids.ctypes.data, life.ctypes.data
-        a.cam0, a.cam1, a.und0, a.und1 = (p.ctypes.data for p in pts)
-        hs = (C.c_void_p * 1)(stream.h)
-        c0 = (C.c_void_p * 1)(img.ctypes.data); c1 = (C.c_void_p * 1)(img.ctypes.data)
-        return L.mskf_fe_frame_batch_begin(gpu_ctx.h, 1, hs, c0, c1, 0, (capi.FeFrameArgs * 1)(a))
+        return _status(gpu_ctx.frame_batch_begin, [stream], [(img, img)], [dict(capacity=cap)])
 
     s = capi.Stream(gpu_ctx, calib, default_fe_cfg(), default_ekf_cfg())
-    cap = L.mskf_fe_grid_capacity(s.h)
+    cap = s.grid_capacity()
     assert cap >= 4 * 5 * 4
     assert frame(s, cap) == -1 and b"no grid on the device" in L.mskf_last_error()          # MSKF_ERR_INVALID: first frame goes the phased way
-    assert L.mskf_fe_set_grid(s.h, 0, None, None, None, None, None, None, 0, None, 0) == 0
+    assert _status(s.set_grid) == 0
     assert frame(s, cap - 1) == -1                                                          # output arrays too small
-    assert L.mskf_fe_set_grid(s.h, cap + 1, None, None, None, None, None, None, 0, None, 0) == -1
+    assert _status(s.set_grid, n=cap + 1) == -1
     s.close()
     s = capi.Stream(gpu_ctx, calib, default_fe_cfg(compat=COMPAT_REFERENCE & ~8), default_ekf_cfg())     # Q5 cleared: RANSAC on
-    assert L.mskf_fe_set_grid(s.h, 0, None, None, None, None, None, None, 0, None, 0) == 0
-    assert frame(s, L.mskf_fe_grid_capacity(s.h)) == 0                                       # accepted: the RANSAC runs inside the frame
-    assert L.mskf_fe_frame_batch_end(gpu_ctx.h) == 0
+    assert _status(s.set_grid) == 0
+    assert frame(s, s.grid_capacity()) == 0                                                  # accepted: the RANSAC runs inside the frame
+    assert _status(gpu_ctx.frame_batch_end) == 0
     s.close()
     s = capi.Stream(gpu_ctx, calib, default_fe_cfg(grid_min=17, grid_max=20), default_ekf_cfg())
-    assert L.mskf_fe_grid_capacity(s.h) == 0
-    assert L.mskf_fe_set_grid(s.h, 0, None, None, None, None, None, None, 0, None, 0) == -3
+    assert s.grid_capacity() == 0
+    assert _status(s.set_grid) == -3
     s.close()
+
+
+# ---- the front-end batches refuse before they touch anything (188 x 120: the size of tests/golden/frontend_188x120.npz)
+_FE_W, _FE_H = 188, 120
+_FE_REF = {}
+
+
+def _fe_images(oracle):
+    """Pair A and pair B of three streams: frames 0, 2, 4 and 6, 8, 10 of one synthetic sequence (the camera moves from frame 1 on)."""
+    if "img" not in _FE_REF:
+        syn = oracle.Synth(seed=0x5EED0090, width=_FE_W, height=_FE_H, n_static=1, n_loop=40)
+        _FE_REF["img"] = ([syn.render(k) for k in (0, 2, 4)], [syn.render(k) for k in (6, 8, 10)])
+        _FE_REF["calib"] = syn.calib
+    return _FE_REF["img"] + (_FE_REF["calib"],)
+
+
+def _fe_streams(ctx, calib, n=3, fe=None):
+    return [capi.Stream(ctx, calib, fe or default_fe_cfg(), default_ekf_cfg()) for _ in range(n)]
+
+
+def _push_state(s):
+    """What a push leaves behind for one stream: the cell maxima, the four levels of cam0, and what a stereo-only track of the
+    maxima above the detector threshold returns (it reads both pyramids)."""
+    m = s.cell_maxima()
+    top = m[m["score"] > s.fe_cfg.fast_threshold * 256]
+    assert len(top) > 20
+    trk = s.track(np.stack([top["x"], top["y"]], axis=1), do_temporal=0)
+    return [m] + [s.get_level(1, l) for l in range(4)] + [trk[k] for k in ("out0", "out1", "und0", "und1", "status")]
+
+
+def _same(a, b):
+    assert len(a) == len(b)
+    for i, (x, y) in enumerate(zip(a, b)):
+        assert x.shape == y.shape and x.tobytes() == y.tobytes(), i
+
+
+@pytest.mark.parametrize("case", ["null_stream", "other_context", "null_cam1", "pending_track"])
+def test_fe_push_batch_refusals(gpu_ctx, oracle, case):
+    """mskf_fe_push_stereo_batch refuses a batch whose MIDDLE stream is wrong (a valid one before it) with MSKF_ERR_INVALID and
+    has then changed nothing: maxima, pyramid levels and a repeated track of all three streams are bit-identical to what the
+    accepted push of pair A left, and a valid push of pair B afterwards equals a fresh context that saw only A, then B."""
+    A, B, calib = _fe_images(oracle)
+    if "push" not in _FE_REF:
+        ctx = capi.Context(0)
+        ss = _fe_streams(ctx, calib)
+        for pair in (A, B):
+            ctx.push_stereo_batch(ss, [p[0] for p in pair], [p[1] for p in pair])
+        _FE_REF["push"] = [[s.cell_maxima()] + [s.get_level(1, l) for l in range(4)] for s in ss]
+        ctx.close()
+    ss = _fe_streams(gpu_ctx, calib)
+    gpu_ctx.push_stereo_batch(ss, [p[0] for p in A], [p[1] for p in A])
+    before = [_push_state(s) for s in ss]
+    # (the tracks above were batches of their own: the maxima of the push are still the context's latest)
+    streams, cam0s, cam1s = list(ss), [p[0] for p in B], [p[1] for p in B]
+    other = None
+    if case == "null_stream":
+        streams[1] = None
+    elif case == "other_context":
+        other = capi.Context(0)
+        streams[1] = _fe_streams(other, calib, 1)[0]
+    elif case == "null_cam1":
+        cam1s[1] = None
+    elif case == "pending_track":
+        gpu_ctx.track_batch_begin(ss[2:], [dict(pts=np.array([[40.0, 40.0], [90.0, 60.0]]), do_temporal=0)])
+    try:
+        assert _status(gpu_ctx.push_stereo_batch, streams, cam0s, cam1s) == _MSKF_ERR_INVALID
+    finally:
+        gpu_ctx.track_batch_end()
+        if other is not None:
+            other.close()
+    for s, want in zip(ss, before):
+        _same(_push_state(s), want)
+    gpu_ctx.push_stereo_batch(ss, [p[0] for p in B], [p[1] for p in B])
+    for s, want in zip(ss, _FE_REF["push"]):
+        _same([s.cell_maxima()] + [s.get_level(1, l) for l in range(4)], want)
+    for s in ss:
+        s.close()
+
+
+_FRAME_KEYS = ("id", "lifetime", "cam0", "cam1", "und0", "und1")
+_FRAME_COUNTS = ("n", "before_tracking", "after_tracking", "after_matching", "after_ransac", "n_candidates", "n_new", "next_feature_id", "ransac_draws")
+
+
+def _same_frames(got, want):
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert [g[k] for k in _FRAME_COUNTS] == [w[k] for k in _FRAME_COUNTS]
+        _same([g[k] for k in _FRAME_KEYS], [w[k] for k in _FRAME_KEYS])
+
+
+def _frame(ctx, ss, pairs, args=None):
+    ctx.frame_batch_begin(ss, pairs, args or [{} for _ in ss])
+    return ctx.frame_batch_end()
+
+
+@pytest.mark.parametrize("case,expect", [("grid_never_set", _MSKF_ERR_INVALID), ("capacity_too_small", _MSKF_ERR_INVALID), ("null_cam0", _MSKF_ERR_INVALID),
+                                         ("pending_track", _MSKF_ERR_INVALID)])
+def test_fe_frame_batch_refusals(gpu_ctx, oracle, case, expect):
+    """mskf_fe_frame_batch_begin refuses a batch whose MIDDLE stream is wrong with today's status and has then changed nothing:
+    the same three streams run the next frame bit-identically to three streams on another context that were never offered
+    the refused batch (grid, ids, lifetimes, points, counters, id counter, RANSAC draw counter)."""
+    A, B, calib = _fe_images(oracle)
+    other = capi.Context(0)
+    sets, first = [], []
+    for ctx in (gpu_ctx, other):
+        ss = _fe_streams(ctx, calib)
+        for s in ss:
+            s.set_grid()
+        first.append(_frame(ctx, ss, A))
+        sets.append(ss)
+    assert all(r["n"] > 0 for r in first[0])
+    _same_frames(first[0], first[1])
+    ss = sets[0]
+    extra = _fe_streams(gpu_ctx, calib, 1)[0]               # a stream of the context whose grid was never set
+    streams, pairs, args = list(ss), list(B), [{} for _ in ss]
+    if case == "grid_never_set":
+        streams[1] = extra
+    elif case == "capacity_too_small":
+        args[1] = dict(capacity=ss[1].grid_capacity() - 1)
+    elif case == "null_cam0":
+        pairs[1] = (None, B[1][1])
+    elif case == "pending_track":
+        extra.push_stereo(*A[0])
+        gpu_ctx.track_batch_begin([extra], [dict(pts=np.array([[40.0, 40.0], [90.0, 60.0]]), do_temporal=0)])
+    try:
+        assert _status(gpu_ctx.frame_batch_begin, streams, pairs, args) == expect
+        assert _status(gpu_ctx.frame_batch_end) == 0         # nothing pending
+    finally:
+        gpu_ctx.track_batch_end()
+    got, want = _frame(gpu_ctx, sets[0], B), _frame(other, sets[1], B)
+    assert all(r["n"] > 0 for r in want)
+    _same_frames(got, want)
+    extra.close()
+    for s in sets[0]:
+        s.close()
+    other.close()
+
+
+def test_fe_frame_batch_mixed_capacities(gpu_ctx, oracle):
+    """One frame batch of two streams whose grid configurations, hence capacities and export blocks, differ: over three frames
+    every output of each stream equals, bit for bit, the same stream run alone on a context of its own."""
+    syn = oracle.Synth(seed=0x5EED0091, width=_FE_W, height=_FE_H, n_static=1, n_loop=40)
+    cfgs = [default_fe_cfg(), default_fe_cfg(grid_row=3, grid_col=6, grid_min=2, grid_max=6)]      # (the oracle's front-end keeps 60 and 36 features on these frames)
+    frames = [syn.render(k) for k in (0, 2, 4)]
+    ss = [_fe_streams(gpu_ctx, syn.calib, 1, fe)[0] for fe in cfgs]
+    assert ss[0].grid_capacity() != ss[1].grid_capacity() and min(s.grid_capacity() for s in ss) > 0
+    for s in ss:
+        s.set_grid()
+    batch = [_frame(gpu_ctx, ss, [f, f]) for f in frames]
+    for i, fe in enumerate(cfgs):
+        ctx = capi.Context(0)
+        s = _fe_streams(ctx, syn.calib, 1, fe)[0]
+        s.set_grid()
+        for k, f in enumerate(frames):
+            alone = _frame(ctx, [s], [f])
+            assert alone[0]["n"] > 0
+            _same_frames([batch[k][i]], alone)
+        ctx.close()
+    for s in ss:
+        s.close()
