@@ -40,7 +40,8 @@ typedef struct mskf_stream mskf_stream;
 const char *mskf_last_error(void);
 int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.compression_mode, *_begin / *_end entry points; 3 (round 3): update args carry
                                  pos_var_out, mskf_fe_frame_batch_* (whole front-end frames on the device), mskf_ctx_timing_gate, mskf_ctx_set_wait_mode;
-                                 4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter) */
+                                 4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter);
+                                 added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -156,7 +157,8 @@ int mskf_fe_track_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const
  * One pending batch per context.  The same holds for every _begin / _end pair of this header:
  *   - while a batch is pending, calls that need the staging buffers it owns fail with MSKF_ERR_INVALID, and mskf_last_error
  *     names the pending batch: a track or device-frame batch blocks the front-end calls (push, track, frame), an update
- *     batch blocks the next update, a position-variance read-out blocks every prediction, augmentation and clone removal;
+ *     batch blocks the next update, a read-out (position variances or odometry covariance) blocks every prediction,
+ *     augmentation, clone removal and any other read-out;
  *   - a failed _end (the wait timed out or the stream reported an error) leaves the batch pending: its kernels may still
  *     be running.  _end may be called again; mskf_ctx_destroy drains the stream as always;
  *   - a failed _begin leaves nothing pending and nothing running: if it had enqueued work, it synchronises the context's
@@ -282,6 +284,16 @@ int mskf_ekf_get_pos_var(mskf_stream *s, double out[3]);
 int mskf_ekf_get_pos_var_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out /* 3n */);
 int mskf_ekf_get_pos_var_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out /* 3n, filled by _end */);
 int mskf_ekf_get_pos_var_batch_end(mskf_ctx *ctx);
+/* Covariance half of MsckfVio::publish (msckf_vio.cpp:1262-1293): the 6x6 body-frame pose covariance H P_imu_pose H^T, the 3x3
+ * body-frame velocity covariance and, unrotated, the three position variances of mskf_ekf_get_pos_var, 48 doubles per stream.
+ * One small kernel for the whole batch on the context's stream, behind whatever the streams' filter halves enqueued before
+ * it (no synchronisation needed after an update or a clone removal); it reads its descriptors from pinned host memory and
+ * writes the records straight into it: no staging copy.  Same _begin / _end protocol as the position variances, and the two
+ * kinds of read-out share one pending slot per context: while either is pending, the other's _begin and _end refuse too. */
+int mskf_ekf_get_odom_cov(mskf_stream *s, mskf_odom_cov *out);                                   /* batch of one; synchronises */
+int mskf_ekf_get_odom_cov_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_odom_cov *out /* n */);
+int mskf_ekf_get_odom_cov_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_odom_cov *out /* n, filled by _end */);
+int mskf_ekf_get_odom_cov_batch_end(mskf_ctx *ctx);
 int mskf_ekf_propagate(mskf_stream *s, int n_steps, const double *Phi /* n x 21x21 */, const double *Q /* n x 21x21 */);
 int mskf_ekf_augment(mskf_stream *s, const double *J /* 6x21 */);
 int mskf_ekf_update(mskf_stream *s, mskf_ekf_update_args *args);

@@ -105,6 +105,14 @@ typedef struct mskf_pose {
     double q[4];
 } mskf_pose;
 
+/* covariance half of the published odometry (msckf_vio.cpp:1262-1293), one record per pose.  R = rotation of
+ * IMUState::T_imu_body, i.e. of the INVERSE of mskf_calib.T_imu_body (:124-125); arithmetic order: DESIGN.md 3 */
+typedef struct mskf_odom_cov {
+    double pose[36];    /* row-major 6x6, body frame, order [position ; orientation]   (msckf_vio.cpp:1269-1284) */
+    double twist[9];    /* row-major 3x3 velocity covariance, body frame               (:1288-1293; the reference keeps it in the top-left of a 6x6) */
+    double pos_var[3];  /* P(12,12), P(13,13), P(14,14), IMU frame, unrotated: what onlineReset tests (:1194-1196) */
+} mskf_odom_cov;        /* 48 doubles */
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import CORNER, IMU_STEP, POINT2F, Calib, EkfCfg, FeCfg, ImuStep
+from .ctypes_types import CORNER, IMU_STEP, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, ImuStep
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -60,6 +60,7 @@ EXPORTS = [
     "mskf_ekf_update_batch_begin", "mskf_ekf_update_batch_end", "mskf_ekf_get_pos_var_batch_begin", "mskf_ekf_get_pos_var_batch_end", "mskf_ctx_timing_gate",
     "mskf_fe_grid_capacity", "mskf_fe_set_grid", "mskf_fe_frame_batch_begin", "mskf_fe_frame_batch_end", "mskf_ctx_set_wait_mode",
     "mskf_stream_rebind", "mskf_ctx_record_point", "mskf_ctx_wait_point", "mskf_point_destroy", "mskf_ekf_set_compression_mode",
+    "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
 ]
 
 
@@ -292,6 +293,29 @@ class Context:
         _chk(self.L.mskf_ekf_get_pos_var_batch_end(self.h))
         self._pv_pending = None
 
+    def ekf_odom_cov_batch(self, streams):
+        """The published pose / velocity covariance of every stream (mskf_odom_cov), an ODOM_COV array of n records."""
+        out = self.ekf_odom_cov_batch_begin(streams)
+        self.ekf_odom_cov_batch_end()
+        return out
+
+    def ekf_odom_cov_batch_begin(self, streams, out=None):
+        """Enqueue the read-out; the returned ODOM_COV array (or `out`, if given) is filled by ekf_odom_cov_batch_end."""
+        n = len(streams)
+        if out is None:
+            out = np.zeros(n, ODOM_COV)
+            out.view(np.float64)[:] = np.nan
+        self.L.mskf_ekf_get_odom_cov_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+        hs = _handles(streams)
+        _chk(self.L.mskf_ekf_get_odom_cov_batch_begin(self.h, n, hs, _p(out)))
+        self._oc_pending = (out, hs)          # both must stay alive until _end
+        return out
+
+    def ekf_odom_cov_batch_end(self):
+        self.L.mskf_ekf_get_odom_cov_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_ekf_get_odom_cov_batch_end(self.h))
+        self._oc_pending = None
+
     def hip_stream(self):
         return self.L.mskf_ctx_hip_stream(self.h)
 
@@ -446,6 +470,14 @@ class Stream:
         self.L.mskf_ekf_get_pos_var.argtypes = [C.c_void_p, C.c_void_p]
         _chk(self.L.mskf_ekf_get_pos_var(self.h, _p(out)))
         return out
+
+    def ekf_odom_cov(self):
+        """mskf_ekf_get_odom_cov: one ODOM_COV record (pose 6 x 6, twist 3 x 3, pos_var 3)."""
+        out = np.zeros(1, ODOM_COV)
+        out.view(np.float64)[:] = np.nan
+        self.L.mskf_ekf_get_odom_cov.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(self.L.mskf_ekf_get_odom_cov(self.h, _p(out)))
+        return out[0]
 
     @staticmethod
     def _update_args(gravity, clones, positions, obs_start, obs_clone, obs_z, dof_offset, apply_row_cap, needs_init=None, init_ranges=None):

@@ -114,6 +114,8 @@ static void base_desc(const mskf_stream *s, EkfStreamDev &D) {
         hm::Rigid T01 = hm::Rigid::from_rowmajor16(s->calib.T_cam1_cam0);   // CAMState::T_cam0_cam1, msckf_vio.cpp:121-122
         std::memcpy(T.R_c0_c1, T01.R.m, sizeof(T.R_c0_c1));
         for (int i = 0; i < 3; ++i) T.t_c0_c1[i] = T01.t[i];
+        hm::Rigid Tib = hm::Rigid::from_rowmajor16(s->calib.T_imu_body).inverse();    // IMUState::T_imu_body, msckf_vio.cpp:124-125
+        std::memcpy(T.R_imu_body, Tib.R.m, sizeof(T.R_imu_body));
         X->desc_valid = true;
     }
     D = X->desc_static;
@@ -264,48 +266,80 @@ extern "C" int mskf_ekf_augment(mskf_stream *s, const double *J) {
     return predict(s->ctx_ekf, 1, ss, ns, st, nullptr, nullptr, j);
 }
 
+// ---- read-outs: position variances (3 doubles per stream) and the published odometry covariance (48: mskf_odom_cov).
+// One routine and one pending slot (mskf_ctx::pend_ro) for both kinds: the kernel reads its descriptors from the pinned
+// side of pred_arena and writes its `rec` doubles per stream straight into it, behind them; _end waits and copies out.
+static int readout_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out, int rec) {
+    if (!ctx || n <= 0 || !streams || !out) return MSKF_ERR_INVALID;
+    for (int i = 0; i < n; ++i) if (!streams[i] || streams[i]->ctx_ekf != ctx) return MSKF_ERR_INVALID;
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);
+    if (rc != MSKF_OK) return rc;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t desc_bytes = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
+    const size_t bytes = desc_bytes + sizeof(double) * (size_t)rec * (size_t)n;
+    if ((rc = ctx->pred_arena.fence_wait()) != MSKF_OK || (rc = ctx->pred_arena.ensure(bytes)) != MSKF_OK) return rc;
+    EkfStreamDev *D = (EkfStreamDev *)ctx->pred_arena.h;
+    for (int i = 0; i < n; ++i) base_desc(streams[i], D[i]);
+    // (no staging copies: the kernel reads its descriptors from the pinned arena and writes the rec * n doubles straight into it)
+    DrainOnError drain{st, true};
+    double *res = (double *)(ctx->pred_arena.h + desc_bytes);
+    if (rec == 3) ekf_launch_posvar((const EkfStreamDev *)ctx->pred_arena.h, n, res, st);
+    else ekf_launch_odom_cov((const EkfStreamDev *)ctx->pred_arena.h, n, res, st);
+    mskf_ctx::PendingReadOut &V = ctx->pend_ro;
+    V.n = n; V.rec = rec; V.out = out; V.desc_bytes = desc_bytes;
+    if ((rc = mskf_batch_arm(ctx, V)) != MSKF_OK) return rc;
+    drain.armed = false;
+    return MSKF_OK;
+}
+
+static int readout_end(mskf_ctx *ctx, int rec) {
+    if (!ctx) return MSKF_ERR_INVALID;
+    mskf_ctx::PendingReadOut &V = ctx->pend_ro;
+    if (!V.active) return MSKF_OK;
+    if (V.rec != rec) return mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);      // the other kind is pending: names it and its _end
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    const int rc = mskf_batch_finish(ctx, V);
+    if (rc != MSKF_OK) return rc;
+    mskf_t_collect(ctx);
+    std::memcpy(V.out, ctx->pred_arena.h + V.desc_bytes, sizeof(double) * (size_t)V.rec * (size_t)V.n);
+    return MSKF_OK;
+}
+
 extern "C" int mskf_ekf_get_pos_var_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out) {
     const int rc = mskf_ekf_get_pos_var_batch_begin(ctx, n, streams, out);
     return rc != MSKF_OK ? rc : mskf_ekf_get_pos_var_batch_end(ctx);
 }
 
 extern "C" int mskf_ekf_get_pos_var_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, double *out) {
-    if (!ctx || n <= 0 || !streams || !out) return MSKF_ERR_INVALID;
-    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);
-    if (rc != MSKF_OK) return rc;
-    for (int i = 0; i < n; ++i) if (!streams[i] || streams[i]->ctx_ekf != ctx) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t desc_bytes = align_up(sizeof(EkfStreamDev) * (size_t)n, 64);
-    const size_t bytes = desc_bytes + sizeof(double) * 3 * (size_t)n;
-    if ((rc = ctx->pred_arena.fence_wait()) != MSKF_OK || (rc = ctx->pred_arena.ensure(bytes)) != MSKF_OK) return rc;
-    EkfStreamDev *D = (EkfStreamDev *)ctx->pred_arena.h;
-    for (int i = 0; i < n; ++i) base_desc(streams[i], D[i]);
-    // (no staging copies: the kernel reads its descriptors from the pinned arena and writes the 3 n doubles straight into it)
-    DrainOnError drain{st, true};
-    ekf_launch_posvar((const EkfStreamDev *)ctx->pred_arena.h, n, (double *)(ctx->pred_arena.h + desc_bytes), st);
-    mskf_ctx::PendingPosVar &V = ctx->pend_pv;
-    V.n = n; V.out = out; V.desc_bytes = desc_bytes;
-    if ((rc = mskf_batch_arm(ctx, V)) != MSKF_OK) return rc;
-    drain.armed = false;
-    return MSKF_OK;
+    return readout_begin(ctx, n, streams, out, 3);
 }
 
-extern "C" int mskf_ekf_get_pos_var_batch_end(mskf_ctx *ctx) {
-    if (!ctx) return MSKF_ERR_INVALID;
-    if (!ctx->pend_pv.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    const int rc = mskf_batch_finish(ctx, ctx->pend_pv);
-    if (rc != MSKF_OK) return rc;
-    mskf_t_collect(ctx);
-    std::memcpy(ctx->pend_pv.out, ctx->pred_arena.h + ctx->pend_pv.desc_bytes, sizeof(double) * 3 * (size_t)ctx->pend_pv.n);
-    return MSKF_OK;
-}
+extern "C" int mskf_ekf_get_pos_var_batch_end(mskf_ctx *ctx) { return readout_end(ctx, 3); }
 
 extern "C" int mskf_ekf_get_pos_var(mskf_stream *s, double out[3]) {
     if (!s || !out) return MSKF_ERR_INVALID;
     mskf_stream *ss[1] = {s};
     return mskf_ekf_get_pos_var_batch(s->ctx_ekf, 1, ss, out);
+}
+
+static_assert(sizeof(mskf_odom_cov) == 48 * sizeof(double), "k_ekf_odom_cov writes 48 doubles per stream");
+
+extern "C" int mskf_ekf_get_odom_cov_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_odom_cov *out) {
+    return readout_begin(ctx, n, streams, (double *)out, 48);
+}
+
+extern "C" int mskf_ekf_get_odom_cov_batch_end(mskf_ctx *ctx) { return readout_end(ctx, 48); }
+
+extern "C" int mskf_ekf_get_odom_cov_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_odom_cov *out) {
+    const int rc = mskf_ekf_get_odom_cov_batch_begin(ctx, n, streams, out);
+    return rc != MSKF_OK ? rc : mskf_ekf_get_odom_cov_batch_end(ctx);
+}
+
+extern "C" int mskf_ekf_get_odom_cov(mskf_stream *s, mskf_odom_cov *out) {
+    if (!s || !out) return MSKF_ERR_INVALID;
+    mskf_stream *ss[1] = {s};
+    return mskf_ekf_get_odom_cov_batch(s->ctx_ekf, 1, ss, out);
 }
 
 extern "C" int mskf_ekf_remove_clones_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *idx) {

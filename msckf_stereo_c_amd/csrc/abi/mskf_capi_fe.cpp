@@ -73,7 +73,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     if (c->cell_ev) (void)hipEventDestroy(c->cell_ev);
     if (c->pend_trk.done) (void)hipEventDestroy(c->pend_trk.done);
     if (c->pend_upd.done) (void)hipEventDestroy(c->pend_upd.done);
-    if (c->pend_pv.done) (void)hipEventDestroy(c->pend_pv.done);
+    if (c->pend_ro.done) (void)hipEventDestroy(c->pend_ro.done);
     if (c->owns_stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -191,7 +191,9 @@ int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which) {
             if (c->pend_upd.active) owner = "an update batch of this context is still pending (call mskf_ekf_update_batch_end)";
             break;
         case MSKF_ARENAS_PRED:
-            if (c->pend_pv.active) owner = "a position-variance read-out of this context is still pending (call mskf_ekf_get_pos_var_batch_end)";
+            if (c->pend_ro.active)
+                owner = c->pend_ro.rec == 3 ? "a position-variance read-out of this context is still pending (call mskf_ekf_get_pos_var_batch_end)"
+                                            : "an odometry-covariance read-out of this context is still pending (call mskf_ekf_get_odom_cov_batch_end)";
             break;
     }
     if (!owner) return MSKF_OK;
@@ -259,7 +261,7 @@ extern "C" int mskf_ctx_set_timing(mskf_ctx *c, int enable) {
 
 extern "C" int mskf_ctx_set_wait_mode(mskf_ctx *c, int block) {
     if (!c) return MSKF_ERR_INVALID;
-    if (c->pend_trk.active || c->pend_upd.active || c->pend_pv.active || c->pend_frame.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
+    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
     c->wait_block = block != 0;
     return MSKF_OK;
 }

@@ -99,7 +99,8 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 // Which pending batch owns which arenas of the context:
 //   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
 //   a pending update owns ekf_desc, upd_in and upd_out;
-//   a pending position-variance read-out owns pred_arena (its kernel reads descriptors from and writes results into the host side).
+//   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
+//   descriptors from and writes results into the host side).
 // Every _begin and every batch call that writes an arena refuses while the owner is pending: MSKF_ERR_INVALID, and the
 // error message names the pending batch.  What each step of such a call may touch:
 //   plan    (plan_push, plan_update, a _begin's own checks): reads the context and the streams, makes no HIP call; every
@@ -166,7 +167,7 @@ struct mskf_ctx {
     PinnedDev<Pyr3Job> jobs;
     PinnedDev<EkfStreamDev> ekf_desc;
     PinnedDev<char> upd_in, upd_out;     // inputs / results of every stream of an update batch (one copy each way)
-    PinnedDev<char> pred_arena;          // descriptors + Phi/Q or IMU steps + J of a prediction, clone removal, position-variance read-out (fenced)
+    PinnedDev<char> pred_arena;          // descriptors + Phi/Q or IMU steps + J of a prediction, clone removal, read-out (fenced)
     std::vector<mskf_stream *> streams;
     // batches between their *_begin and *_end call (PendingBatch)
     struct PendingTrack : PendingBatch {
@@ -177,7 +178,8 @@ struct mskf_ctx {
         bool launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
         std::vector<EkfUpdatePlan> plan;       // per stream, written by _begin's planning step; storage reused from call to call
     } pend_upd;
-    struct PendingPosVar : PendingBatch { int n = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_pv;
+    // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
+    struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;
 };
 // Completion marks.  mskf_wait_event(c, slot, true) marks the point the context's stream has reached, (.., false) waits
 // for that mark.  Spinning mode (default): the mark is a sequence number written into pinned host memory by a stream

@@ -5,6 +5,10 @@
 // same call order per image: do { imu_callback } while (t_imu <= t_img); stereo_callback; backend_callback
 // (reference :189-254, Q10).  No OpenCV / Pangolin: images are decoded by a small zlib-based reader of
 // 8-bit grayscale PNG (what EuRoC ships) or binary PGM, and nothing is drawn (Q17).  Writes pose_out.txt.
+// Options come from the YAML files, as in the reference.  One key of ../config/app_msckfvio.yaml is this harness's own:
+// "covariance_out: <file>" also writes the covariance half of publish() (msckf_vio.cpp:1262-1293), one line per pose in the
+// same std::fixed format: time stamp, the 36 entries of the 6x6 pose covariance, the 9 of the 3x3 velocity covariance
+// (cg::System's YAML constructor switches MsckfVio::publishCovariance on).  Without the key nothing else is written.
 #include <zlib.h>
 #include <cassert>
 #include <cstdio>

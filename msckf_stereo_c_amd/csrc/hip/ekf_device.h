@@ -49,6 +49,7 @@ struct EkfStreamDev {
     double sigma2;            // Feature::observation_noise (variance)
     double gravity[3];
     double R_c0_c1[9], t_c0_c1[3];       // CAMState::T_cam0_cam1
+    double R_imu_body[9];                // rotation of IMUState::T_imu_body = inverse of mskf_calib.T_imu_body (msckf_vio.cpp:124-125), row-major; k_ekf_odom_cov
     const double *chi2;                  // table[100], index = dof
     const mskf_clone_state *clones;      // n_clones
     EkfFeatDev *feats;                   // n_feat
@@ -106,6 +107,7 @@ void ekf_launch_features(const EkfStreamDev *d, const int *work_wave, int n_wave
 void ekf_launch_pair_features(const EkfStreamDev *d, int n, int max_feat, int max_tri, hipStream_t st);
 void ekf_launch_posvar(const EkfStreamDev *d, int n, double *out, hipStream_t st);
 void ekf_launch_posvar_upd(const EkfStreamDev *d, int n, hipStream_t st);
+void ekf_launch_odom_cov(const EkfStreamDev *d, int n, double *out, hipStream_t st);      // out: 48 doubles per stream (mskf_odom_cov)
 void ekf_launch_gemm(const EkfStreamDev *d, int n, int mode, int max_mn, hipStream_t st);
 void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int max_d, hipStream_t st);
 void ekf_launch_tsqr(const EkfStreamDev *d, int n, int max_d, int do_cap, hipStream_t st);

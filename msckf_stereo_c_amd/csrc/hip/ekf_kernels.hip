@@ -236,6 +236,39 @@ __global__ void k_ekf_posvar_upd(const EkfStreamDev *streams, int n) {
     S.pos_var_out[i % 3] = S.P[(size_t)k * S.ld + k];
 }
 
+// ------------------------------------------------------------------------------------ odometry covariance
+// Covariance half of MsckfVio::publish (msckf_vio.cpp:1262-1293) of every stream of the batch: one mskf_odom_cov (48 doubles)
+// per stream, one thread per output.  Outputs 0..35: pose = H P_imu_pose H^T with H = diag(R, R), P_imu_pose = [P_pp P_po; P_op P_oo]
+// (p = rows 12..14, o = rows 0..2); 36..44: twist = R P[6:9,6:9] R^T; 45..47: P(12,12), P(13,13), P(14,14) unrotated.
+// For a 3x3 block B of P the order of operations is fixed (the library is built with -ffp-contract=off):
+//   M[i][b]   = (R[i][0] B[0][b] + R[i][1] B[1][b]) + R[i][2] B[2][b]
+//   out[i][j] = (M[i][0] R[j][0] + M[i][1] R[j][1]) + M[i][2] R[j][2]
+// which is the reference's left-to-right H * P * H^T without the exact-zero terms of the block-diagonal H.  A thread forms
+// the one row of M it needs.  No symmetrisation (the reference does none).
+__global__ __launch_bounds__(64) void k_ekf_odom_cov(const EkfStreamDev *streams, int n, double *out) {
+    const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (t >= 48LL * n) return;
+    const int s = (int)(t / 48), o = (int)(t - 48LL * s);
+    const EkfStreamDev &S = streams[s];
+    const size_t ld = (size_t)S.ld;
+    if (o >= 45) { const int k = 12 + (o - 45); out[t] = S.P[k * ld + k]; return; }
+    int i, j, r0, c0;
+    if (o < 36) {
+        const int r = o / 6, c = o - 6 * r;
+        i = r < 3 ? r : r - 3; j = c < 3 ? c : c - 3;
+        r0 = r < 3 ? 12 : 0; c0 = c < 3 ? 12 : 0;
+    } else {
+        i = (o - 36) / 3; j = (o - 36) - 3 * i;
+        r0 = c0 = 6;
+    }
+    const double *B = S.P + r0 * ld + c0;
+    const double *Ri = S.R_imu_body + 3 * i, *Rj = S.R_imu_body + 3 * j;
+    double M[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) M[b] = (Ri[0] * B[b] + Ri[1] * B[ld + b]) + Ri[2] * B[2 * ld + b];
+    out[t] = (M[0] * Rj[0] + M[1] * Rj[1]) + M[2] * Rj[2];
+}
+
 // ------------------------------------------------------------------------------------ feature blocks
 template <int NMEAS>
 struct TriScratchT {     // poses and rays of the 2 * n_init stereo measurements of one feature
@@ -1114,5 +1147,8 @@ void ekf_launch_posvar(const EkfStreamDev *d, int n, double *out, hipStream_t st
 }
 void ekf_launch_posvar_upd(const EkfStreamDev *d, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_ekf_posvar_upd, dim3((3 * n + 63) / 64), dim3(64), 0, st, d, n);
+}
+void ekf_launch_odom_cov(const EkfStreamDev *d, int n, double *out, hipStream_t st) {
+    hipLaunchKernelGGL(k_ekf_odom_cov, dim3((unsigned)((48LL * n + 63) / 64)), dim3(64), 0, st, d, n, out);
 }
 }

@@ -190,6 +190,21 @@ int BatchGroup::step_ekf(const FrameBatch *fb) {
     for (int i = 0; i < n; ++i) any_rm |= rm_[2 * i] >= 0;
     if (any_rm) BR_CHK(mskf_ekf_remove_clones_batch(ekf_ctx_, n, streams_.data(), rm_.data()));
     lap(PH_EKF_C);
+    // publishCovariance on any stream: one read-out of the whole group's odometry covariances (msckf_vio.cpp:1262-1293) behind the
+    // clone removal; its pos_var serves onlineReset, so it takes the place of the fallback below (and costs a host wait of its own)
+    bool any_cov = false;
+    for (int i = 0; i < n; ++i) any_cov |= vio(i).publishCovariance;
+    if (any_cov) {
+        oc_.resize(n);
+        BR_CHK(mskf_ekf_get_odom_cov_batch_begin(ekf_ctx_, n, streams_.data(), oc_.data()));
+        BR_CHK(mskf_ekf_get_odom_cov_batch_end(ekf_ctx_));
+        for (int i = 0; i < n; ++i) {
+            if (vio(i).publishCovariance) vio(i).attachOdomCov(oc_[i]);
+            vio(i).phaseD(oc_[i].pos_var);
+        }
+        lap(PH_POSVAR);
+        return MSKF_OK;
+    }
     // onlineReset (msckf_vio.cpp:1186-1236) needs P(12..14) of every stream: they came back with the frame's last update;
     // only when some stream had no update at all this frame they are fetched with a launch and a wait of their own
     bool all_pv = true;

@@ -139,6 +139,7 @@ class BatchGroup {
     std::vector<const mskf_imu_step *> pred_sp_;
     std::vector<const double *> pred_jp_;
     std::vector<double> pv_;                                  // position variances fetched on their own (3 per stream)
+    std::vector<mskf_odom_cov> oc_;                           // odometry covariances of a frame (publishCovariance)
     std::vector<const uint8_t *> p0_, p1_;
     std::vector<double> t_;
     std::unique_ptr<ForkJoin> pool_, pool_ekf_;

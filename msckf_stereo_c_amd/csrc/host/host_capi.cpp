@@ -191,6 +191,16 @@ void mskfh_get_poses(void *h, int stream, mskf_pose *out) {
     const auto &p = ((MultiRunner *)h)->system(stream).msckfvio_ptr()->poses();
     std::memcpy(out, p.data(), p.size() * sizeof(mskf_pose));
 }
+// MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
+void mskfh_runner_publish_covariance(void *h, int stream, int on) {
+    MultiRunner *r = (MultiRunner *)h;
+    for (int i = 0; i < r->n_streams(); ++i) if (stream < 0 || i == stream) r->system(i).msckfvio_ptr()->publishCovariance = on != 0;
+}
+int mskfh_num_odom_covs(void *h, int stream) { return (int)((MultiRunner *)h)->system(stream).msckfvio_ptr()->odomCovs().size(); }
+void mskfh_get_odom_covs(void *h, int stream, mskf_odom_cov *out) {
+    const auto &c = ((MultiRunner *)h)->system(stream).msckfvio_ptr()->odomCovs();
+    std::memcpy(out, c.data(), c.size() * sizeof(mskf_odom_cov));
+}
 int mskfh_state_dim(void *h, int stream) { int d = 0; mskf_ekf_get_dim(((MultiRunner *)h)->system(stream).stream(), &d); return d; }
 int mskfh_get_cov(void *h, int stream, double *out, int cap) { return mskf_ekf_get_cov(((MultiRunner *)h)->system(stream).stream(), out, cap); }
 void mskfh_get_imu_state(void *h, int stream, double *out) {   // same 28-double layout as the oracle's getter

@@ -52,6 +52,7 @@ MsckfVio::MsckfVio(const mskf_calib &calib, const mskf_ekf_cfg &cfg) : calib_(ca
 MsckfVio::~MsckfVio() {
     if (pose_outfile_.is_open()) pose_outfile_.close();
     if (debug_.is_open()) debug_.close();
+    if (cov_outfile_.is_open()) cov_outfile_.close();
 }
 
 void MsckfVio::fail(const char *what, int rc) {
@@ -157,6 +158,16 @@ void MsckfVio::featureCallback(const CameraMeasurementConstPtr &msg) {
         if (rc != MSKF_OK) { fail("mskf_ekf_update", rc); return; }
     }
     phaseC();
+    if (publishCovariance) {
+        // the covariance of the published pose: P after the frame's updates and clone removal, before onlineReset (:356, :359);
+        // its pos_var is what onlineReset tests
+        mskf_odom_cov oc;
+        int rc = mskf_ekf_get_odom_cov(stream_, &oc);
+        if (rc != MSKF_OK) { fail("mskf_ekf_get_odom_cov", rc); return; }
+        attachOdomCov(oc);
+        if (cfg_.position_std_threshold > 0) phaseD(oc.pos_var);
+        return;
+    }
     if (cfg_.position_std_threshold > 0) {
         if (pos_var_valid_) { phaseD(pos_var_); return; }      // came back with the frame's last update (clone removal does not touch it)
         double pv[3];
@@ -711,6 +722,19 @@ void MsckfVio::publish(double time_stamp) {
     if (pose_outfile_.is_open()) {
         pose_outfile_ << std::fixed << time_stamp << " " << pose.p[0] << " " << pose.p[1] << " " << pose.p[2] << " " << pose.q[0] << " "
                       << pose.q[1] << " " << pose.q[2] << " " << pose.q[3] << std::endl;   // TUM format, Q15
+    }
+}
+
+// the covariance half of publish (:1262-1293), computed on the device (k_ekf_odom_cov)
+void MsckfVio::attachOdomCov(const mskf_odom_cov &c) {
+    if (!frame_active_) return;
+    if (keepTrajectory) odom_covs_.push_back(c);
+    else if (odom_covs_.empty()) odom_covs_.push_back(c); else odom_covs_[0] = c;
+    if (cov_outfile_.is_open()) {
+        cov_outfile_ << std::fixed << frame_time_;
+        for (int i = 0; i < 36; ++i) cov_outfile_ << " " << c.pose[i];
+        for (int i = 0; i < 9; ++i) cov_outfile_ << " " << c.twist[i];
+        cov_outfile_ << std::endl;
     }
 }
 

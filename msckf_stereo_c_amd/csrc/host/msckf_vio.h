@@ -98,6 +98,15 @@ class MsckfVio {
     }
 
     const std::vector<mskf_pose> &poses() const { return poses_; }
+    // publishCovariance: one record per pose, indexed like poses() (empty while the switch has never been on)
+    const std::vector<mskf_odom_cov> &odomCovs() const { return odom_covs_; }
+    // the covariance half of publish() (msckf_vio.cpp:1262-1293) for the pose just published; the caller read it with
+    // mskf_ekf_get_odom_cov* after the frame's updates and clone removal, before onlineReset (phaseD)
+    void attachOdomCov(const mskf_odom_cov &c);
+    void enableCovarianceOutput(const std::string &path) {   // one line per pose: time stamp, 36 pose entries, 9 twist entries
+        publishCovariance = true;
+        if (!cov_outfile_.is_open()) cov_outfile_.open(path);
+    }
     const IMUState &imuState() const { return state_server.imu_state; }
     int numClones() const { return (int)state_server.cam_states.size(); }
     int numUpdates() const { return n_update_; }
@@ -108,6 +117,7 @@ class MsckfVio {
     long long numResets() const { return online_reset_counter_; }
     size_t mapSize() const { return map_server.size(); }
     bool keepTrajectory = true;   // path_/points3d_ grow forever in the reference (Q20); benches may switch it off
+    bool publishCovariance = false;   // publish()'s pose / velocity covariance (:1262-1293), read from the device once per frame; set before the first frame
     const std::string &error() const { return error_; }
 
   private:
@@ -153,6 +163,7 @@ class MsckfVio {
     std::vector<cg::Vector3> path_;
     std::vector<cg::Point3f> points3d_;
     std::vector<mskf_pose> poses_;
+    std::vector<mskf_odom_cov> odom_covs_;
     MapServer map_server;
     std::vector<cg::Imu> imu_msg_buffer;
     bool is_gravity_set = false;
@@ -190,7 +201,7 @@ class MsckfVio {
     int rm_order_[2] = {-1, -1};                           // window positions of the two clones being pruned
     const CameraMeasurement *zero_tail_msg_ = nullptr;
     size_t zero_tail_start_ = 0, zero_tail_total_ = 0;
-    std::ofstream pose_outfile_, debug_;
+    std::ofstream pose_outfile_, debug_, cov_outfile_;
     int n_pub_ = 0;                                        // published frames (msckf_vio.cpp:356)
 };
 

@@ -9,9 +9,12 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         cfg_cam_imu_ = YAML::LoadFile(file_cam_imu);
         mskf_calib calib = calib_from_yaml(cfg_cam_imu_);
         mskf_fe_cfg fe = fe_cfg_from_yaml(YAML::LoadFile("../config/app_imgproc.yaml"));
-        mskf_ekf_cfg ekf = ekf_cfg_from_yaml(YAML::LoadFile("../config/app_msckfvio.yaml"));
+        const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
+        mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);
         if (ok_) { imgproc_ptr_->enableFileOutputs(); msckfvio_ptr_->enableFileOutputs(); }   // pose_out.txt, debug_imageprocessor.txt
+        // optional (not a key of the reference's file): "covariance_out: <file>" writes publish()'s covariances, one line per pose
+        if (ok_ && cfg_msckfvio["covariance_out"].IsDefined()) msckfvio_ptr_->enableCovarianceOutput(cfg_msckfvio["covariance_out"].as<std::string>());
     } catch (const std::exception &e) {   // the reference swallows init errors and only prints (system.cpp:17-33)
         std::cerr << "Cannot initialize System: " << e.what() << std::endl;
     }

@@ -62,11 +62,18 @@ class TrackingInfo(C.Structure):
                 ("after_matching", C.c_int32), ("after_ransac", C.c_int32)]
 
 
+class OdomCov(C.Structure):
+    """mskf_odom_cov (include/mskf_types.h): covariance half of the published odometry."""
+    _fields_ = [("pose", C.c_double * 36), ("twist", C.c_double * 9), ("pos_var", C.c_double * 3)]
+
+
 # numpy dtypes of the array records
 POINT2F = np.dtype([("x", "<f4"), ("y", "<f4")])
 CORNER = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<i4"), ("cell", "<i4")])
 FEATURE_MEAS = np.dtype([("id", "<u4"), ("_pad", "<u4"), ("u0", "<f8"), ("v0", "<f8"), ("u1", "<f8"), ("v1", "<f8")])
 POSE = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("q", "<f8", 4)])
+ODOM_COV = np.dtype([("pose", "<f8", (6, 6)), ("twist", "<f8", (3, 3)), ("pos_var", "<f8", 3)])
+assert ODOM_COV.itemsize == C.sizeof(OdomCov) == 384
 IMU_STEP = np.dtype([(name, "<f8", C.sizeof(ty) // 8) if C.sizeof(ty) > 8 else (name, "<f8") for name, ty in ImuStep._fields_])
 assert IMU_STEP.itemsize == C.sizeof(ImuStep)
 

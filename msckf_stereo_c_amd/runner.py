@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .capi import MskfError
-from .ctypes_types import FEATURE_MEAS, POINT2F, POSE, Calib, EkfCfg, FeCfg, ImuSample, TrackingInfo
+from .ctypes_types import FEATURE_MEAS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, ImuSample, TrackingInfo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -37,6 +37,10 @@ def lib():
         L.mskfh_runner_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.mskfh_runner_keep_trajectory.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_runner_keep_trajectory_stream.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.mskfh_runner_publish_covariance.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.mskfh_num_odom_covs.argtypes = [C.c_void_p, C.c_int]
+        L.mskfh_num_odom_covs.restype = C.c_int
+        L.mskfh_get_odom_covs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.mskfh_runner_run_timed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
         L.mskfh_runner_frames_done.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_runner_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -192,6 +196,11 @@ class Runner:
         else:
             self.L.mskfh_runner_keep_trajectory_stream(self.h, int(stream), int(keep))
 
+    def publish_covariance(self, on, stream=None):
+        """MsckfVio::publishCovariance of one stream or of all: every published pose gets its 6 x 6 pose and 3 x 3 velocity
+        covariance (one device read-out per filter frame).  Off by default; set it before the first frame."""
+        self.L.mskfh_runner_publish_covariance(self.h, -1 if stream is None else int(stream), int(on))
+
     # indexed like the MSKF_K_* kinds of mskf_hip.h; "k_ekf_augment" keeps its place and stays empty (augmentation is fused into k_ekf_propagate)
     KERNELS = ["k_pyr_down", "k_detect_cells", "k_track4", "k_ekf_propagate", "k_ekf_augment", "k_ekf_feature_blocks",
                "k_ekf_tsqr", "k_ekf_gemm", "k_ekf_chol_lds", "k_ekf_trsm", "k_ekf_small", "k_ekf_remove_clone", "k_pt_geom", "k_fe_book"]
@@ -273,6 +282,14 @@ class Runner:
         out = np.zeros(n, POSE)
         if n:
             self.L.mskfh_get_poses(self.h, stream, _p(out))
+        return out
+
+    def odom_cov(self, stream=0):
+        """ODOM_COV records aligned with poses(stream); empty unless publish_covariance is on."""
+        n = self.L.mskfh_num_odom_covs(self.h, stream)
+        out = np.zeros(n, ODOM_COV)
+        if n:
+            self.L.mskfh_get_odom_covs(self.h, stream, _p(out))
         return out
 
     def cov(self, stream=0):
