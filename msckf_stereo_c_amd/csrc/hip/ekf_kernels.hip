@@ -3,8 +3,9 @@
 //  k_ekf_propagate      : covariance part of processModel        (msckf_vio.cpp:458-469), fused with the one of
 //                         stateAugmentation (:564-582)
 //  k_ekf_remove_clone   : clone row/column deletion              (:1161-1181)
-//  k_ekf_feature_blocks : Feature::initializePosition (feature.hpp:289-450), measurementJacobian
-//                         (:610-677), featureJacobian null-space projection (:679-775), gatingTest (:909-935)
+//  k_ekf_feature_blocks : Feature::initializePosition (feature.hpp:289-450), featureJacobian null-space projection
+//                         (:679-775), gatingTest (:909-935)
+//  (ekf_meas.h)         : measurementJacobian (:610-677) and the 3 x 3 math, one source for both feature kernels and the host's dump
 //  (ekf_cap.h)          : stacking order + 1500-row cap          (:1003-1010), run by the first dense kernel of the update
 //  (ekf_linalg.hip)     : QR compression (:795-811) as Gram + Cholesky, gain / correction / covariance update (:831-904)
 //
@@ -14,7 +15,10 @@
 #include <mutex>
 #include <type_traits>
 #include "ekf_device.h"
+#include "ekf_meas.h"
 #include "chol_block.h"
+
+using namespace ekf;
 
 #define WG 256
 
@@ -33,25 +37,6 @@ __device__ __forceinline__ double block_sum(double v, double *s_red) {
     double t = 0;
     for (int i = 0; i < nw; ++i) t += s_red[i];
     return t;
-}
-
-// ------------------------------------------------------------------------------------ small math
-__device__ __forceinline__ void quat_to_rot(const double *q, double *R) {
-    // JPL: R = (2w^2-1) I - 2w [qv]x + 2 qv qv^T   
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double a = 2 * w * w - 1, tw = 2 * w;
-    R[0] = a + 2 * x * x;        R[1] = tw * z + 2 * x * y;   R[2] = -tw * y + 2 * x * z;
-    R[3] = -tw * z + 2 * y * x;  R[4] = a + 2 * y * y;        R[5] = tw * x + 2 * y * z;
-    R[6] = tw * y + 2 * z * x;   R[7] = -tw * x + 2 * z * y;  R[8] = a + 2 * z * z;
-}
-__device__ __forceinline__ void mat3_mul(const double *A, const double *B, double *C) {
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-__device__ __forceinline__ void mat3_vec(const double *A, const double *v, double *o) {
-    for (int i = 0; i < 3; ++i) o[i] = A[3 * i] * v[0] + A[3 * i + 1] * v[1] + A[3 * i + 2] * v[2];
-}
-__device__ __forceinline__ void mat3t_vec(const double *A, const double *v, double *o) {
-    for (int i = 0; i < 3; ++i) o[i] = A[i] * v[0] + A[3 + i] * v[1] + A[6 + i] * v[2];
 }
 
 // Phi (3rd-order expm of F dt with the observability fix-ups) and Q = Phi G Qc G^T Phi^T dt of one IMU step
@@ -539,53 +524,12 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
             sObsOfClone[ci] = gt;
             sCloneOfObs[gt] = ci;
             const mskf_clone_state &cam = S.clones[ci];
-            double R_w_c0[9], R_w_c1[9], tmp[3];
-            quat_to_rot(cam.q, R_w_c0);
-            mat3_mul(S.R_c0_c1, R_w_c0, R_w_c1);
-            mat3t_vec(R_w_c1, S.t_c0_c1, tmp);
-            const double t_c1_w[3] = {cam.p[0] - tmp[0], cam.p[1] - tmp[1], cam.p[2] - tmp[2]};
-            const double dp0[3] = {sPos[0] - cam.p[0], sPos[1] - cam.p[1], sPos[2] - cam.p[2]};
-            const double dp1[3] = {sPos[0] - t_c1_w[0], sPos[1] - t_c1_w[1], sPos[2] - t_c1_w[2]};
-            double p_c0[3], p_c1[3];
-            mat3_vec(R_w_c0, dp0, p_c0);
-            mat3_vec(R_w_c1, dp1, p_c1);
-            // dz_dpc0 (rows 0,1), dz_dpc1 (rows 2,3)
-            double dz[4][3] = {{1 / p_c0[2], 0, -p_c0[0] / (p_c0[2] * p_c0[2])},
-                               {0, 1 / p_c0[2], -p_c0[1] / (p_c0[2] * p_c0[2])},
-                               {1 / p_c1[2], 0, -p_c1[0] / (p_c1[2] * p_c1[2])},
-                               {0, 1 / p_c1[2], -p_c1[1] / (p_c1[2] * p_c1[2])}};
-            // dpc0_dxc = [skew(p_c0), -R_w_c0], dpc1_dxc = [R_c0_c1 skew(p_c0), -R_w_c1]
-            const double sk[9] = {0, -p_c0[2], p_c0[1], p_c0[2], 0, -p_c0[0], -p_c0[1], p_c0[0], 0};
-            double Rsk[9];
-            mat3_mul(S.R_c0_c1, sk, Rsk);
-            double Hx[4][6];
-            for (int rr = 0; rr < 4; ++rr) {
-                const double *L = rr < 2 ? sk : Rsk;
-                const double *Rm = rr < 2 ? R_w_c0 : R_w_c1;
-                for (int c = 0; c < 3; ++c) {
-                    Hx[rr][c] = dz[rr][0] * L[c] + dz[rr][1] * L[3 + c] + dz[rr][2] * L[6 + c];
-                    Hx[rr][3 + c] = -(dz[rr][0] * Rm[c] + dz[rr][1] * Rm[3 + c] + dz[rr][2] * Rm[6 + c]);
-                }
-            }
-            // observability constraint: H_x <- A - A u (u^T u)^-1 u^T ; H_f <- -H_x[:, 3:6]
-            double Rn[9], u[6], g[3] = {S.gravity[0], S.gravity[1], S.gravity[2]};
-            quat_to_rot(cam.q_null, Rn);
-            mat3_vec(Rn, g, u);
-            const double dn[3] = {sPos[0] - cam.p_null[0], sPos[1] - cam.p_null[1], sPos[2] - cam.p_null[2]};
-            u[3] = dn[1] * g[2] - dn[2] * g[1]; u[4] = dn[2] * g[0] - dn[0] * g[2]; u[5] = dn[0] * g[1] - dn[1] * g[0];
-            double uu = 0;
-            for (int k = 0; k < 6; ++k) uu += u[k] * u[k];
-            for (int rr = 0; rr < 4; ++rr) {
-                double Au = 0;
-                for (int k = 0; k < 6; ++k) Au += Hx[rr][k] * u[k];
-                for (int c = 0; c < 6; ++c) sHx[4 * gt + rr][c] = Hx[rr][c] - Au * (1.0 / uu) * u[c];
-            }
+            double R_w_c0[9], R_w_c1[9], t_c1_w[3], Rn[9], Hx[4][6], r[4];
+            cam_pose(cam, S.R_c0_c1, S.t_c0_c1, R_w_c0, R_w_c1, t_c1_w, Rn);
+            meas_jacobian(cam, R_w_c0, R_w_c1, t_c1_w, Rn, S.R_c0_c1, sPos, S.gravity, S.obs_z + 4 * o, Hx, r);
+            for (int rr = 0; rr < 4; ++rr) for (int c = 0; c < 6; ++c) sHx[4 * gt + rr][c] = Hx[rr][c];
             for (int rr = 0; rr < 4; ++rr) for (int c = 0; c < 3; ++c) sHf[4 * gt + rr][c] = -sHx[4 * gt + rr][3 + c];
-            const double *z = S.obs_z + 4 * o;
-            sr[4 * gt + 0] = z[0] - p_c0[0] / p_c0[2];
-            sr[4 * gt + 1] = z[1] - p_c0[1] / p_c0[2];
-            sr[4 * gt + 2] = z[2] - p_c1[0] / p_c1[2];
-            sr[4 * gt + 3] = z[3] - p_c1[1] / p_c1[2];
+            for (int rr = 0; rr < 4; ++rr) sr[4 * gt + rr] = r[rr];
         }
         GSYNC();
         TDBG();
@@ -647,7 +591,7 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
         GSYNC();
         TDBG();
         // ---- 5. write the projected block: rows 3..4M-1 of Q^T [H_xj | r_j], only the 6 M columns of the observed
-        //         clones and the residual column (the rest of a row is never read: rowmask, k_ekf_cap)
+        //         clones and the residual column (the rest of a row is never read: rowmask, ekf_cap.h)
         if constexpr (MAXC <= 32) {
             // a lane's columns (cc = lane, lane + 64, ...) do not depend on the row: their coefficients, clone column and
             // block position are taken into registers once, a row then costs three broadcast reads and one store per column
@@ -844,7 +788,7 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
         const bool pass = pd_ok && dof >= 1 && dof < 100 && gamma < S.chi2[dof];
         if (gt < 64) {
             // what the block's rows carry: the clone bits of its observations if it passed the gate, 0 otherwise (every row of the
-            // block: the Gram pass reads a row only where its mask says so; k_ekf_cap wrote these masks in rounds 1-3)
+            // block: the Gram pass reads a row only where its mask says so; a kernel of its own wrote these masks in rounds 1-3)
             unsigned long long cm = 0ULL;
             if (pass) for (int o = gt; o < M; o += 64) cm |= 1ULL << sCloneOfObs[o];
             for (int off = 32; off > 0; off >>= 1) cm |= __shfl_xor(cm, off);
@@ -913,14 +857,10 @@ __global__ __launch_bounds__(64) void k_ekf_pair_blocks(const EkfStreamDev *stre
         }
         if (threadIdx.x < 2) {
             const mskf_clone_state &cam = S.clones[threadIdx.x == 0 ? pa : pb];
-            double R0[9], R1[9], tmp[3];
-            quat_to_rot(cam.q, R0);
-            mat3_mul(S.R_c0_c1, R0, R1);
-            mat3t_vec(R1, S.t_c0_c1, tmp);
-            for (int i = 0; i < 9; ++i) { sRw[threadIdx.x][0][i] = R0[i]; sRw[threadIdx.x][1][i] = R1[i]; }
-            for (int i = 0; i < 3; ++i) sTc1[threadIdx.x][i] = cam.p[i] - tmp[i];
-            quat_to_rot(cam.q_null, R0);
-            for (int i = 0; i < 9; ++i) sRn[threadIdx.x][i] = R0[i];
+            double R0[9], R1[9], t1[3], Rn[9];
+            cam_pose(cam, S.R_c0_c1, S.t_c0_c1, R0, R1, t1, Rn);
+            for (int i = 0; i < 9; ++i) { sRw[threadIdx.x][0][i] = R0[i]; sRw[threadIdx.x][1][i] = R1[i]; sRn[threadIdx.x][i] = Rn[i]; }
+            for (int i = 0; i < 3; ++i) sTc1[threadIdx.x][i] = t1[i];
         }
         __syncthreads();
         if (!have) continue;
@@ -939,55 +879,15 @@ __global__ __launch_bounds__(64) void k_ekf_pair_blocks(const EkfStreamDev *stre
         const double g[3] = {S.gravity[0], S.gravity[1], S.gravity[2]};
 #pragma unroll 1
         for (int ob = 0; ob < 2; ++ob) {
-            const mskf_clone_state &cam = S.clones[ob == 0 ? pa : pb];
-            const double *R_w_c0 = sRw[ob][0], *R_w_c1 = sRw[ob][1];
-            const double dp0[3] = {pos[0] - cam.p[0], pos[1] - cam.p[1], pos[2] - cam.p[2]};
-            const double dp1[3] = {pos[0] - sTc1[ob][0], pos[1] - sTc1[ob][1], pos[2] - sTc1[ob][2]};
-            double p_c0[3], p_c1[3];
-            mat3_vec(R_w_c0, dp0, p_c0);
-            mat3_vec(R_w_c1, dp1, p_c1);
-            const double dz[4][3] = {{1 / p_c0[2], 0, -p_c0[0] / (p_c0[2] * p_c0[2])},
-                                     {0, 1 / p_c0[2], -p_c0[1] / (p_c0[2] * p_c0[2])},
-                                     {1 / p_c1[2], 0, -p_c1[0] / (p_c1[2] * p_c1[2])},
-                                     {0, 1 / p_c1[2], -p_c1[1] / (p_c1[2] * p_c1[2])}};
-            const double sk[9] = {0, -p_c0[2], p_c0[1], p_c0[2], 0, -p_c0[0], -p_c0[1], p_c0[0], 0};
-            double Rsk[9];
-            mat3_mul(S.R_c0_c1, sk, Rsk);
-            double *Xb = X + (4 * ob) * 13 + 6 * ob;          // this observation's 4 x 6 block inside X (row stride 13)
+            double Hx[4][6], r[4];
+            meas_jacobian(S.clones[ob == 0 ? pa : pb], sRw[ob][0], sRw[ob][1], sTc1[ob], sRn[ob], S.R_c0_c1, pos, g, S.obs_z + 4 * (F.obs_start + ob), Hx, r);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double l0 = rr < 2 ? sk[c] : Rsk[c], l1 = rr < 2 ? sk[3 + c] : Rsk[3 + c], l2 = rr < 2 ? sk[6 + c] : Rsk[6 + c];
-                    const double m0 = rr < 2 ? R_w_c0[c] : R_w_c1[c], m1 = rr < 2 ? R_w_c0[3 + c] : R_w_c1[3 + c], m2 = rr < 2 ? R_w_c0[6 + c] : R_w_c1[6 + c];
-                    Xb[rr * 13 + c] = dz[rr][0] * l0 + dz[rr][1] * l1 + dz[rr][2] * l2;
-                    Xb[rr * 13 + 3 + c] = -(dz[rr][0] * m0 + dz[rr][1] * m1 + dz[rr][2] * m2);
-                }
+                double *Xr = X + (4 * ob + rr) * 13;           // H_x of this observation in columns 6 ob .. 6 ob + 5, r in column 12
+                for (int c = 0; c < 6; ++c) Xr[6 * ob + c] = Hx[rr][c];
+                for (int c = 0; c < 3; ++c) Hf[(4 * ob + rr) * 3 + c] = -Hx[rr][3 + c];
+                Xr[12] = r[rr];
             }
-            double u[6];
-            mat3_vec(sRn[ob], g, u);
-            const double dn[3] = {pos[0] - cam.p_null[0], pos[1] - cam.p_null[1], pos[2] - cam.p_null[2]};
-            u[3] = dn[1] * g[2] - dn[2] * g[1]; u[4] = dn[2] * g[0] - dn[0] * g[2]; u[5] = dn[0] * g[1] - dn[1] * g[0];
-            double uu = 0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) uu += u[k] * u[k];
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                double Au = 0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) Au += Xb[rr * 13 + k] * u[k];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    const double h = Xb[rr * 13 + c] - Au * (1.0 / uu) * u[c];
-                    Xb[rr * 13 + c] = h;
-                    if (c >= 3) Hf[(4 * ob + rr) * 3 + (c - 3)] = -h;
-                }
-            }
-            const double *z = S.obs_z + 4 * (F.obs_start + ob);
-            X[(4 * ob + 0) * 13 + 12] = z[0] - p_c0[0] / p_c0[2];
-            X[(4 * ob + 1) * 13 + 12] = z[1] - p_c0[1] / p_c0[2];
-            X[(4 * ob + 2) * 13 + 12] = z[2] - p_c1[0] / p_c1[2];
-            X[(4 * ob + 3) * 13 + 12] = z[3] - p_c1[1] / p_c1[2];
         }
         // ---- three Householder reflectors of H_f, applied to H_f's remaining columns and to [H_x | r] (:757-766)
 #pragma unroll 1

@@ -8,6 +8,7 @@
 #include <iostream>
 #include "image_processor.h"
 #include "kinematics.h"
+#include "../hip/ekf_meas.h"
 
 namespace cg {
 
@@ -488,9 +489,9 @@ void MsckfVio::applyCorrection(const std::vector<double> &dx) {
 
 // featureJacobian's debug output (msckf_vio.cpp:719-723): in the frame with n_pub == 9 the reference writes the
 // un-projected stacked Jacobians H_xj (4 M x d), H_fj (4 M x 3) and the residual r_j of every feature it linearises.
-// The device keeps those only in LDS, so this (cold, file-output-only) path restates measurementJacobian (:610-677) on
-// the host from the clone states and observations the update was built from and the position the device returned.
-// Matrices are written row by row, blank separated.
+// The device keeps those only in LDS, so this (cold, file-output-only) path runs the kernels' own measurementJacobian
+// (../hip/ekf_meas.h, the same source and operation order) on the clone states and observations the update was built from
+// and the position the device returned.  Matrices are written row by row, blank separated.
 void MsckfVio::dumpFeatureJacobians() {
     if (!debug_.is_open() || n_pub_ != 9) return;
     const int d = 21 + 6 * (int)clones_.size();
@@ -499,45 +500,17 @@ void MsckfVio::dumpFeatureJacobians() {
         const mskf_ekf_feature &f = feats_[j];
         const int M = f.n_obs;
         std::vector<double> Hx((size_t)4 * M * d, 0.0), Hf((size_t)4 * M * 3, 0.0), r((size_t)4 * M, 0.0);
-        const Vector3 p_w(f.position[0], f.position[1], f.position[2]);
         for (int o = 0; o < M; ++o) {
             const int ci = obs_clone_[f.obs_start + o];
             const mskf_clone_state &cam = clones_[ci];
-            const double *z = &obs_z_[(size_t)4 * (f.obs_start + o)];
-            const hm::Mat3 R_w_c0 = kin::rotation_of(cam.q);
-            const Vector3 t_c0_w(cam.p[0], cam.p[1], cam.p[2]);
-            const hm::Mat3 R_c0_c1 = T_cam0_cam1_.R;
-            const hm::Mat3 R_w_c1 = R_c0_c1 * R_w_c0;
-            const Vector3 t_c1_w = t_c0_w - R_w_c1.transpose() * T_cam0_cam1_.t;
-            const Vector3 p_c0 = R_w_c0 * (p_w - t_c0_w), p_c1 = R_w_c1 * (p_w - t_c1_w);
-            double dz0[4][3] = {{0}}, dz1[4][3] = {{0}};
-            dz0[0][0] = 1 / p_c0[2]; dz0[1][1] = 1 / p_c0[2]; dz0[0][2] = -p_c0[0] / (p_c0[2] * p_c0[2]); dz0[1][2] = -p_c0[1] / (p_c0[2] * p_c0[2]);
-            dz1[2][0] = 1 / p_c1[2]; dz1[3][1] = 1 / p_c1[2]; dz1[2][2] = -p_c1[0] / (p_c1[2] * p_c1[2]); dz1[3][2] = -p_c1[1] / (p_c1[2] * p_c1[2]);
-            const hm::Mat3 sk = hm::skew(p_c0), Rsk = R_c0_c1 * sk;
-            double A[4][6];
+            double R_w_c0[9], R_w_c1[9], t_c1_w[3], Rn[9], H[4][6];
+            ekf::cam_pose(cam, T_cam0_cam1_.R.m, T_cam0_cam1_.t.v, R_w_c0, R_w_c1, t_c1_w, Rn);
+            ekf::meas_jacobian(cam, R_w_c0, R_w_c1, t_c1_w, Rn, T_cam0_cam1_.R.m, f.position, gravity_.v, &obs_z_[(size_t)4 * (f.obs_start + o)], H, &r[4 * o]);
             for (int i = 0; i < 4; ++i)
-                for (int c = 0; c < 3; ++c) {
-                    double a = 0, b = 0;
-                    for (int k = 0; k < 3; ++k) { a += dz0[i][k] * sk(k, c) + dz1[i][k] * Rsk(k, c); b += -dz0[i][k] * R_w_c0(k, c) - dz1[i][k] * R_w_c1(k, c); }
-                    A[i][c] = a; A[i][3 + c] = b;
-                }
-            const Vector3 g = gravity_;
-            const Vector3 u0 = kin::rotation_of(cam.q_null) * g;
-            const Vector3 u1 = hm::skew(p_w - Vector3(cam.p_null[0], cam.p_null[1], cam.p_null[2])) * g;
-            const double u[6] = {u0[0], u0[1], u0[2], u1[0], u1[1], u1[2]};
-            double uu = 0;
-            for (int k = 0; k < 6; ++k) uu += u[k] * u[k];
-            for (int i = 0; i < 4; ++i) {
-                double Au = 0;
-                for (int k = 0; k < 6; ++k) Au += A[i][k] * u[k];
                 for (int c = 0; c < 6; ++c) {
-                    const double h = A[i][c] - Au * (1.0 / uu) * u[c];
-                    Hx[(size_t)(4 * o + i) * d + 21 + 6 * ci + c] = h;
-                    if (c >= 3) Hf[(size_t)(4 * o + i) * 3 + (c - 3)] = -h;
+                    Hx[(size_t)(4 * o + i) * d + 21 + 6 * ci + c] = H[i][c];
+                    if (c >= 3) Hf[(size_t)(4 * o + i) * 3 + (c - 3)] = -H[i][c];
                 }
-            }
-            r[4 * o + 0] = z[0] - p_c0[0] / p_c0[2]; r[4 * o + 1] = z[1] - p_c0[1] / p_c0[2];
-            r[4 * o + 2] = z[2] - p_c1[0] / p_c1[2]; r[4 * o + 3] = z[3] - p_c1[1] / p_c1[2];
         }
         auto mat = [&](const char *name, const std::vector<double> &m, int cols) {
             debug_ << name << "\n";

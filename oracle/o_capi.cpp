@@ -298,6 +298,32 @@ int orc_ekf_update_problem(const mskf_calib *calib, const mskf_ekf_cfg *cfg, con
     return stack;
 }
 
+// MsckfVio::measurementJacobian (:610-677) of one observation on explicit inputs: clone = 14 doubles as above.
+// Outputs, row-major: H_x 4 x 6 (projected), H_f 4 x 3, r[4].
+void orc_measurement_jacobian(const mskf_calib *calib, const mskf_ekf_cfg *cfg, const double gravity[3], const double *clone,
+                              const double position[3], const double z[4], double *H_x_out, double *H_f_out, double *r_out) {
+    MsckfVio vio(*calib, *cfg);
+    vio.sh.gravity = V3(gravity[0], gravity[1], gravity[2]);
+    CAMState cs;
+    cs.id = 0;
+    cs.orientation = Quat(clone[0], clone[1], clone[2], clone[3]);
+    cs.position = V3(clone[4], clone[5], clone[6]);
+    cs.orientation_null = Quat(clone[7], clone[8], clone[9], clone[10]);
+    cs.position_null = V3(clone[11], clone[12], clone[13]);
+    vio.state_server.cam_states[0] = cs;
+    Feature &f = vio.map_server[0];
+    f.id = 0;
+    f.position = V3(position[0], position[1], position[2]);
+    f.is_initialized = true;
+    f.observations[0] = {z[0], z[1], z[2], z[3]};
+    Mat H_x, H_f;
+    vio.measurementJacobian(0, 0, H_x, H_f, r_out);
+    for (int i = 0; i < 4; ++i) {
+        for (int j = 0; j < 6; ++j) H_x_out[6 * i + j] = H_x(i, j);
+        for (int j = 0; j < 3; ++j) H_f_out[3 * i + j] = H_f(i, j);
+    }
+}
+
 // batched LM triangulation (feature.hpp:289-450) on explicit inputs: returns validity per feature
 void orc_triangulate(const mskf_calib *calib, int n_clones, const double *clones, int n_feat, const int *obs_start,
                      const int *obs_clone, const double *obs_z, double *positions, uint8_t *valid) {

@@ -377,6 +377,20 @@ def ekf_update_problem(calib, ekf_cfg, gravity, clones, P, positions, obs_start,
     return dict(rows=rows, gamma=gamma, passed=passed, delta_x=dx, P=P)
 
 
+def measurement_jacobian(calib, ekf_cfg, gravity, clone, position, z):
+    """MsckfVio::measurementJacobian (msckf_vio.cpp:610-677) of one observation -> (H_x 4 x 6, H_f 4 x 3, r[4])."""
+    clone = np.ascontiguousarray(clone, dtype=np.float64).reshape(14)
+    position = np.ascontiguousarray(position, dtype=np.float64).reshape(3)
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(4)
+    g = np.ascontiguousarray(gravity, dtype=np.float64).reshape(3)
+    Hx, Hf, r = np.zeros((4, 6)), np.zeros((4, 3)), np.zeros(4)
+    f = lib().orc_measurement_jacobian
+    f.argtypes = [C.POINTER(Calib), C.POINTER(EkfCfg)] + [C.c_void_p] * 7
+    f.restype = None
+    f(C.byref(calib), C.byref(ekf_cfg), _p(g), _p(clone), _p(position), _p(z), _p(Hx), _p(Hf), _p(r))
+    return Hx, Hf, r
+
+
 def triangulate(calib, clones, obs_start, obs_clone, obs_z):
     clones = np.ascontiguousarray(clones, dtype=np.float64)
     obs_start = np.ascontiguousarray(obs_start, dtype=np.int32)

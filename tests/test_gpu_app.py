@@ -69,3 +69,16 @@ def test_run_euroc_single_thread_on_synthetic_mav0(tmp_path, oracle):
     hf = np.array([[float(v) for v in line.split()] for line in jac[2].splitlines()[1:] if line.strip()])
     assert hx.shape[0] == hf.shape[0] and hx.shape[0] % 4 == 0 and hf.shape[1] == 3 and (hx.shape[1] - 21) % 6 == 0
     assert np.all(hx[:, :21] == 0) and np.abs(hx).max() > 0          # clone columns only (:713)
+    # every triple of the dump: each 4-row group of H_xj (one observation) has exactly one non-zero 6-column clone block, H_fj of
+    # the group is minus columns 3..5 of that block (the same digits: both are printed from the same numbers), r_j has a row per row
+    assert (len(jac) - 1) % 3 == 0
+    for t in range(1, len(jac), 3):
+        assert jac[t].startswith("H_xj:") and jac[t + 1].startswith("H_fj:") and jac[t + 2].startswith("r_j:")
+        hxt, hft, rj = ([[float(v) for v in line.split()] for line in jac[t + k].splitlines()[1:] if line.strip()] for k in range(3))
+        hxt, hft = np.array(hxt), np.array(hft)
+        assert hxt.shape[0] % 4 == 0 and hft.shape == (hxt.shape[0], 3) and len(rj) == hxt.shape[0] and all(len(v) == 1 for v in rj)
+        for o in range(hxt.shape[0] // 4):
+            blocks = hxt[4 * o:4 * o + 4, 21:].reshape(4, -1, 6)
+            used = np.flatnonzero(np.any(blocks != 0, axis=(0, 2)))
+            assert len(used) == 1, (t, o, used)
+            assert np.array_equal(hft[4 * o:4 * o + 4], -blocks[:, used[0], 3:6]), (t, o)
