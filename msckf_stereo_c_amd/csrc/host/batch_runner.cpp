@@ -45,8 +45,8 @@ void ForkJoin::run(int n, const std::function<void(int)> &fn) {
 BatchGroup::BatchGroup(int device, int n, const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ekf_cfg &ekf, int host_threads, int ekf_host_threads) {
     // per-stream host phases of a group are independent: optional helper threads for the front-end / filter stages
     const int ht_fe = std::max(1, host_threads), ht_ekf = std::max(1, ekf_host_threads > 0 ? ekf_host_threads : host_threads);
-    if (ht_fe > 1) pool_.reset(new ForkJoin(ht_fe));
-    if (ht_ekf > 1) pool_ekf_.reset(new ForkJoin(ht_ekf));
+    if (ht_fe > 1) { pool_.reset(new ForkJoin(ht_fe)); par_fe_ = [this](int cnt, const std::function<void(int)> &fn) { pool_->run(cnt, fn); }; }
+    if (ht_ekf > 1) { pool_ekf_.reset(new ForkJoin(ht_ekf)); par_ekf_ = [this](int cnt, const std::function<void(int)> &fn) { pool_ekf_->run(cnt, fn); }; }
     int rc = mskf_ctx_create(device, &ctx_);
     if (rc == MSKF_OK) rc = mskf_ctx_create_prio(device, 1, &ekf_ctx_);     // the filter is the serial chain of a frame: its queue is dispatched first
     if (rc != MSKF_OK) { error_ = mskf_last_error(); return; }
@@ -57,10 +57,11 @@ BatchGroup::BatchGroup(int device, int n, const mskf_calib &calib, const mskf_fe
         systems_.back()->copy_draw_buffers = false;
         systems_.back()->imgproc_ptr_->setCompactTail(true);      // the Q1 tail of the message as a count (image_processor.h)
         streams_.push_back(systems_.back()->stream());
+        ips_.push_back(systems_.back()->imgproc_ptr_.get()); vios_.push_back(systems_.back()->msckfvio_ptr().get());
         // the filter half of every stream runs on its own context (own HIP stream): no device data is shared
         if (mskf_stream_set_ekf_ctx(streams_.back(), ekf_ctx_) != MSKF_OK) { error_ = mskf_last_error(); return; }
     }
-    a1_.resize(n); a2_.resize(n); u_.resize(n); p0_.resize(n); p1_.resize(n); t_.resize(n);
+    p0_.resize(n); p1_.resize(n); t_.resize(n);
     seq.resize(n);
     ok_ = true;
 }
@@ -73,158 +74,50 @@ BatchGroup::~BatchGroup() {
     if (ctx_) mskf_ctx_destroy(ctx_);
 }
 
-void BatchGroup::imu(int i, const mskf_imu_sample &s) {
+static std::shared_ptr<Imu> imu_msg(const mskf_imu_sample &s) {
     std::shared_ptr<Imu> m(new Imu);
     m->time_stamp = s.time_stamp;
     m->angular_velocity = Vector3(s.angular_velocity[0], s.angular_velocity[1], s.angular_velocity[2]);
     m->linear_acceleration = Vector3(s.linear_acceleration[0], s.linear_acceleration[1], s.linear_acceleration[2]);
-    systems_[i]->imu_callback(m);
+    return m;
 }
 
-#define BR_CHK(expr) do { int _rc = (expr); if (_rc != MSKF_OK) { error_ = std::string(#expr) + ": " + mskf_last_error(); return _rc; } } while (0)
+void BatchGroup::imu(int i, const mskf_imu_sample &s) { systems_[i]->imu_callback(imu_msg(s)); }
 
-// Front-end of one frame of every stream (System::stereo_callback): push (pyramids + detector) -> track (temporal LK,
-// stereo LK, gates) -> host bucketing / candidates -> track (candidates) -> host (ids, prune, publish).
+// Front-end of one frame of every stream (System::stereo_callback): ImageProcessor::runFrame over the group, on the context
+// and into the accumulator of whoever runs the stage; the Systems then see the published messages.
 int BatchGroup::step_fe(const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, const double *t, bool is_draw) {
     const int n = size();
     if (!ok_ || n == 0) return MSKF_ERR_INVALID;
-    auto tp = std::chrono::steady_clock::now();
-    double *acc = acc_fe_ ? acc_fe_ : phase_s;
-    auto lap = [&](int ph) { auto t2 = std::chrono::steady_clock::now(); acc[ph] += std::chrono::duration<double>(t2 - tp).count(); tp = t2; };
-    // Every frame after a stream's first runs as ONE device call (mskf_fe_frame_batch_*): pyramids, detector, both track calls
-    // and the bookkeeping between and after them; the host prepares the prediction and takes the grid.
-    {
-        bool all_dev = true;
-        for (int i = 0; i < n && all_dev; ++i) all_dev = systems_[i]->imgproc_ptr_->canDeviceFrame();
-        if (all_dev) {
-            fa_.resize(n);
-            bool ok = true;
-            for (int i = 0; i < n; ++i) ok = systems_[i]->imgproc_ptr_->frameBegin(t[i], fa_[i]) && ok;
-            if (!ok) { error_ = "frameBegin failed: " + systems_[0]->imgproc_ptr_->error(); return MSKF_ERR_INVALID; }
-            lap(PH_PREP1);
-            BR_CHK(mskf_fe_frame_batch_begin(ctx_, n, streams_.data(), cam0, cam1, on_device, fa_.data()));
-            lap(PH_PUSH);
-            BR_CHK(mskf_fe_frame_batch_end(ctx_));
-            lap(PH_TRACK1);
-            par(pool_.get(), n, [&](int i) {
-                systems_[i]->imgproc_ptr_->frameEnd(fa_[i], is_draw);
-                systems_[i]->set_feature_msg(systems_[i]->imgproc_ptr_->feature_msg_ptr_);
-            });
-            lap(PH_AFTER2);
-            return MSKF_OK;
-        }
-    }
-    // image size comes from the calibration the stream was created with
-    for (int i = 0; i < n; ++i) systems_[i]->imgproc_ptr_->phaseBegin(t[i], 0, 0);
-    BR_CHK(mskf_fe_push_stereo_batch(ctx_, n, streams_.data(), cam0, cam1, on_device));
-    lap(PH_PUSH);
-    if (systems_[0]->imgproc_ptr_->isFirstImage()) BR_CHK(mskf_ctx_sync(ctx_));   // first frame: detections are read right away
-    par(pool_.get(), n, [&](int i) { systems_[i]->imgproc_ptr_->phasePrepare1(a1_[i]); });
-    lap(PH_PREP1);
-    BR_CHK(mskf_fe_track_batch_begin(ctx_, n, streams_.data(), a1_.data()));
-    BR_CHK(mskf_fe_track_batch_end(ctx_));     // (the detector's per-cell maxima of this push have arrived with it)
-    lap(PH_TRACK1);
-    par(pool_.get(), n, [&](int i) { systems_[i]->imgproc_ptr_->phaseAfter1(a2_[i]); });
-    lap(PH_AFTER1);
-    BR_CHK(mskf_fe_track_batch_begin(ctx_, n, streams_.data(), a2_.data()));
-    BR_CHK(mskf_fe_track_batch_end(ctx_));
-    lap(PH_TRACK2);
-    par(pool_.get(), n, [&](int i) {
-        systems_[i]->imgproc_ptr_->phaseAfter2(is_draw);
-        systems_[i]->set_feature_msg(systems_[i]->imgproc_ptr_->feature_msg_ptr_);
-    });
-    lap(PH_AFTER2);
+    std::string what;
+    const int rc = ImageProcessor::runFrame(ctx_, n, ips_.data(), streams_.data(), cam0, cam1, on_device, t, is_draw, fe_scratch_, par_fe_,
+                                            acc_fe_ ? acc_fe_ : phase_s, what);
+    if (rc != MSKF_OK) { error_ = what + ": " + mskf_last_error(); return rc; }
+    for (int i = 0; i < n; ++i) systems_[i]->set_feature_msg(ips_[i]->feature_msg_ptr_);
     return MSKF_OK;
 }
 
-// Filter of one frame of every stream (System::backend_callback -> MsckfVio::featureCallback): predict (IMU propagation +
-// augmentation) -> lost-feature update -> host -> pruning update -> clone removal -> position variances.
+// Filter of one frame of every stream (System::backend_callback -> MsckfVio::featureCallback): MsckfVio::runFrame over the
+// group, on the messages of the hand-off (a pipelined run) or of the Systems, each with its zero-tail hint.
 int BatchGroup::step_ekf(const FrameBatch *fb) {
     const int n = size();
-    auto tp = std::chrono::steady_clock::now();
-    double *acc = acc_ekf_ ? acc_ekf_ : phase_s;
-    auto lap = [&](int ph) { auto t2 = std::chrono::steady_clock::now(); acc[ph] += std::chrono::duration<double>(t2 - tp).count(); tp = t2; };
-    auto vio = [&](int i) -> MsckfVio & { return *systems_[i]->msckfvio_ptr(); };
-    std::vector<std::shared_ptr<CameraMeasurement>> msgs(n);
+    std::vector<CameraMeasurementConstPtr> msgs(n);
     for (int i = 0; i < n; ++i) {
-        if (fb) { msgs[i] = fb->msg[i]; vio(i).setZeroTailHint(msgs[i].get(), fb->tail_start[i], fb->total[i]); }
+        if (fb) { msgs[i] = fb->msg[i]; vios_[i]->setZeroTailHint(msgs[i].get(), fb->tail_start[i], fb->total[i]); }
         else {
             msgs[i] = systems_[i]->feature_msg();
-            vio(i).setZeroTailHint(msgs[i].get(), systems_[i]->imgproc_ptr_->zeroTailStart(), systems_[i]->imgproc_ptr_->messageSize());
+            vios_[i]->setZeroTailHint(msgs[i].get(), ips_[i]->zeroTailStart(), ips_[i]->messageSize());
         }
     }
-    // streams with a non-empty update -> one batched launch (the args stay in upd_a_ until the *_end call)
-    auto updates = [&]() -> int {
-        upd_s_.clear(); upd_a_.clear();
-        for (int i = 0; i < n; ++i) if (u_[i].n_feat > 0) { upd_s_.push_back(streams_[i]); upd_a_.push_back(u_[i]); }
-        if (upd_s_.empty()) return MSKF_OK;
-        const int rc = mskf_ekf_update_batch_begin(ekf_ctx_, (int)upd_s_.size(), upd_s_.data(), upd_a_.data());
-        return rc != MSKF_OK ? rc : mskf_ekf_update_batch_end(ekf_ctx_);
-    };
-    par(pool_ekf_.get(), n, [&](int i) { vio(i).phaseA(msgs[i], u_[i], true); });
-    bool any = false;
-    for (int i = 0; i < n; ++i) any |= vio(i).frameActive();
-    if (!any) { lap(PH_EKF_A); return MSKF_OK; }
-    pred_ns_.assign(n, 0); pred_sp_.assign(n, nullptr); pred_jp_.assign(n, nullptr);
-    for (int i = 0; i < n; ++i) {
-        MsckfVio &v = vio(i);
-        const bool act = v.frameActive();
-        pred_ns_[i] = act ? (int)v.predictSteps().size() : 0;
-        pred_sp_[i] = pred_ns_[i] ? v.predictSteps().data() : nullptr;
-        pred_jp_[i] = act ? v.predictJ() : nullptr;
-    }
-    BR_CHK(mskf_ekf_predict_batch(ekf_ctx_, n, streams_.data(), pred_ns_.data(), pred_sp_.data(), pred_jp_.data()));
-    lap(PH_EKF_A);
-    BR_CHK(updates());
-    lap(PH_UPD1);
-    par(pool_ekf_.get(), n, [&](int i) { if (vio(i).frameActive()) vio(i).phaseB(u_[i]); else std::memset(&u_[i], 0, sizeof(u_[i])); });
-    lap(PH_EKF_B);
-    BR_CHK(updates());
-    lap(PH_UPD2);
-    rm_.assign(2 * (size_t)n, -1);
-    par(pool_ekf_.get(), n, [&](int i) {
-        vio(i).phaseC(true);
-        rm_[2 * i] = vio(i).pendingRemovals()[0]; rm_[2 * i + 1] = vio(i).pendingRemovals()[1];
-    });
-    bool any_rm = false;
-    for (int i = 0; i < n; ++i) any_rm |= rm_[2 * i] >= 0;
-    if (any_rm) BR_CHK(mskf_ekf_remove_clones_batch(ekf_ctx_, n, streams_.data(), rm_.data()));
-    lap(PH_EKF_C);
-    // publishCovariance on any stream: one read-out of the whole group's odometry covariances (msckf_vio.cpp:1262-1293) behind the
-    // clone removal; its pos_var serves onlineReset, so it takes the place of the fallback below (and costs a host wait of its own)
-    bool any_cov = false;
-    for (int i = 0; i < n; ++i) any_cov |= vio(i).publishCovariance;
-    if (any_cov) {
-        oc_.resize(n);
-        BR_CHK(mskf_ekf_get_odom_cov_batch_begin(ekf_ctx_, n, streams_.data(), oc_.data()));
-        BR_CHK(mskf_ekf_get_odom_cov_batch_end(ekf_ctx_));
-        for (int i = 0; i < n; ++i) {
-            if (vio(i).publishCovariance) vio(i).attachOdomCov(oc_[i]);
-            vio(i).phaseD(oc_[i].pos_var);
-        }
-        lap(PH_POSVAR);
-        return MSKF_OK;
-    }
-    // onlineReset (msckf_vio.cpp:1186-1236) needs P(12..14) of every stream: they came back with the frame's last update;
-    // only when some stream had no update at all this frame they are fetched with a launch and a wait of their own
-    bool all_pv = true;
-    for (int i = 0; i < n && all_pv; ++i) all_pv = !vio(i).frameActive() || vio(i).havePosVar();
-    if (all_pv) {
-        for (int i = 0; i < n; ++i) if (vio(i).frameActive()) vio(i).phaseD(vio(i).posVar());
-    } else {
-        pv_.assign(3 * (size_t)n, 0.0);
-        BR_CHK(mskf_ekf_get_pos_var_batch_begin(ekf_ctx_, n, streams_.data(), pv_.data()));
-        BR_CHK(mskf_ekf_get_pos_var_batch_end(ekf_ctx_));
-        for (int i = 0; i < n; ++i) vio(i).phaseD(&pv_[3 * i]);
-    }
-    lap(PH_POSVAR);
-    return MSKF_OK;
+    std::string what;
+    const int rc = MsckfVio::runFrame(ekf_ctx_, n, vios_.data(), streams_.data(), msgs.data(), ekf_scratch_, par_ekf_, acc_ekf_ ? acc_ekf_ : phase_s, what);
+    if (rc != MSKF_OK) error_ = what + ": " + mskf_last_error();
+    return rc;
 }
 
 int BatchGroup::step(const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, const double *t, bool is_draw) {
-    int rc = step_fe(cam0, cam1, on_device, t, is_draw);
-    if (rc != MSKF_OK) return rc;
-    return step_ekf(nullptr);
+    const int rc = step_fe(cam0, cam1, on_device, t, is_draw);
+    return rc != MSKF_OK ? rc : step_ekf(nullptr);
 }
 
 static double ns_to_sec(long long ns) {   // apps/run_euroc_single_thread.cpp:164-166,192 (Q9)
@@ -245,10 +138,7 @@ int BatchGroup::feed_imu(int k, bool to_fe, bool to_ekf) {
         do {
             if (cur >= q.n_imu) { error_ = "IMU sequence exhausted"; return MSKF_ERR_CAPACITY; }
             const mskf_imu_sample &s = q.imu[cur++];
-            std::shared_ptr<Imu> m(new Imu);
-            m->time_stamp = s.time_stamp;
-            m->angular_velocity = Vector3(s.angular_velocity[0], s.angular_velocity[1], s.angular_velocity[2]);
-            m->linear_acceleration = Vector3(s.linear_acceleration[0], s.linear_acceleration[1], s.linear_acceleration[2]);
+            const std::shared_ptr<Imu> m = imu_msg(s);
             if (to_fe) systems_[i]->imgproc_ptr_->imuCallback(m);      // System::imu_callback, system.cpp:45-48
             if (to_ekf) systems_[i]->msckfvio_ptr()->imuCallback(m);
             t_imu = s.time_stamp;
@@ -431,17 +321,17 @@ int MultiRunner::run_balanced(int first, int warmup, int steps, int max_extra, d
         groups_[g]->set_gates(false);
         groups_[g]->mark_dump.fe_valid = groups_[g]->mark_dump.ekf_valid = false;
         groups_[g]->handoff.clear();
-        for (int k = 0; k < BatchGroup::PH_COUNT; ++k) groups_[g]->window_phase_s[k] = 0;
+        for (int k = 0; k < PH_COUNT; ++k) groups_[g]->window_phase_s[k] = 0;
     }
     std::mutex mu;
     std::condition_variable cv;
     std::atomic<int> err{MSKF_OK};
     // a worker's accounting follows the shared window at its frame boundaries; the phase times of worker w are kept in group w's
     // arrays whichever batches it ran
-    static const int fe_phases[] = {BatchGroup::PH_PUSH, BatchGroup::PH_PREP1, BatchGroup::PH_TRACK1, BatchGroup::PH_AFTER1, BatchGroup::PH_TRACK2,
-                                    BatchGroup::PH_AFTER2, BatchGroup::PH_IMU, BatchGroup::PH_HANDOFF, BatchGroup::PH_FE_QWAIT};
-    static const int ekf_phases[] = {BatchGroup::PH_EKF_A, BatchGroup::PH_UPD1, BatchGroup::PH_EKF_B, BatchGroup::PH_UPD2, BatchGroup::PH_EKF_C,
-                                     BatchGroup::PH_POSVAR, BatchGroup::PH_EKF_QWAIT, BatchGroup::PH_IMU_EKF};
+    static const int fe_phases[] = {PH_PUSH, PH_PREP1, PH_TRACK1, PH_AFTER1, PH_TRACK2,
+                                    PH_AFTER2, PH_IMU, PH_HANDOFF, PH_FE_QWAIT};
+    static const int ekf_phases[] = {PH_EKF_A, PH_UPD1, PH_EKF_B, PH_UPD2, PH_EKF_C,
+                                     PH_POSVAR, PH_EKF_QWAIT, PH_IMU_EKF};
     std::vector<mskf_ctx *> fe_ctx(nb), ekf_ctx(nb);      // worker w = the two contexts group w created (captured before any batch moves)
     for (int w = 0; w < nb; ++w) { fe_ctx[w] = groups_[w]->ctx(); ekf_ctx[w] = groups_[w]->ekf_ctx(); }
     auto gate = [&](int w, bool fe, bool on) {
@@ -490,7 +380,7 @@ int MultiRunner::run_balanced(int first, int warmup, int steps, int max_extra, d
                     if (b >= 0 || all_done) break;
                     cv.wait(lk);
                 }
-                acc[BatchGroup::PH_FE_QWAIT] += now_s() - tq;
+                acc[PH_FE_QWAIT] += now_s() - tq;
                 if (b < 0) break;
                 B[b].fe_busy = true;
             }
@@ -536,7 +426,7 @@ int MultiRunner::run_balanced(int first, int warmup, int steps, int max_extra, d
                     if (b >= 0 || !pending) break;
                     cv.wait(lk);
                 }
-                acc[BatchGroup::PH_EKF_QWAIT] += now_s() - tq;
+                acc[PH_EKF_QWAIT] += now_s() - tq;
                 if (b < 0) break;
                 B[b].ekf_busy = true;
                 fb = std::move(groups_[b]->handoff.front());

@@ -1,6 +1,7 @@
 // batch_runner.h — steps many independent VIO streams (cg::System objects) in lockstep so that every
 // device phase of a frame is ONE batched C-ABI call (mskf_fe_push_stereo_batch, mskf_fe_track_batch,
-// mskf_ekf_update_batch, ...).  Streams are independent units: no data crosses streams.
+// mskf_ekf_update_batch, ...): the frame sequences ImageProcessor::runFrame and MsckfVio::runFrame over a group.
+// Streams are independent units: no data crosses streams.
 // A BatchGroup owns two mskf_ctx (front-end and filter, one HIP stream each); a MultiRunner runs several groups, in lockstep
 // on their own host threads or as one pipelined run, so the host bookkeeping of one group overlaps the kernels of another.
 #pragma once
@@ -107,10 +108,7 @@ class BatchGroup {
     mskf_ctx *ekf_ctx() const { return ekf_ctx_; }
     std::vector<StreamSequence> seq;
     const std::string &error() const { return error_; }
-    // phases of the front-end thread: PH_IMU .. PH_FE_QWAIT (without PH_EKF_*); of the filter thread: PH_EKF_QWAIT, PH_IMU_EKF, PH_EKF_A .. PH_POSVAR
-    enum { PH_PUSH = 0, PH_PREP1, PH_TRACK1, PH_AFTER1, PH_TRACK2, PH_AFTER2, PH_EKF_A, PH_UPD1, PH_EKF_B, PH_UPD2, PH_EKF_C, PH_POSVAR, PH_IMU,
-           PH_HANDOFF, PH_FE_QWAIT, PH_EKF_QWAIT, PH_IMU_EKF, PH_COUNT };
-    double phase_s[PH_COUNT] = {0};   // wall seconds per phase of step() (host bookkeeping vs device calls)
+    double phase_s[PH_COUNT] = {0};   // wall seconds per phase of step() (frame_seq.h PH_*: host bookkeeping vs device calls)
     double window_phase_s[PH_COUNT] = {0};   // the same inside the last TimedWindow (each stage between its own marks)
     // what local stream 0 had computed at the end of its batch's own frames of a pipelined run (the sentinel of bench.py):
     // front-end state after the last of them, filter state after the same frame
@@ -130,20 +128,12 @@ class BatchGroup {
     std::string error_;
     std::vector<std::unique_ptr<System>> systems_;
     std::vector<mskf_stream *> streams_;
-    std::vector<mskf_fe_track_args> a1_, a2_;
-    std::vector<mskf_fe_frame_args> fa_;
-    std::vector<mskf_ekf_update_args> u_;
-    std::vector<mskf_stream *> upd_s_;                        // streams with a non-empty update, and their args (valid until *_end)
-    std::vector<mskf_ekf_update_args> upd_a_;
-    std::vector<int32_t> pred_ns_, rm_;                       // prediction steps and clone removals per stream
-    std::vector<const mskf_imu_step *> pred_sp_;
-    std::vector<const double *> pred_jp_;
-    std::vector<double> pv_;                                  // position variances fetched on their own (3 per stream)
-    std::vector<mskf_odom_cov> oc_;                           // odometry covariances of a frame (publishCovariance)
+    std::vector<ImageProcessor *> ips_; std::vector<MsckfVio *> vios_;                  // the two halves of systems_, as the frame sequences take them
+    ImageProcessor::FrameScratch fe_scratch_; MsckfVio::FrameScratch ekf_scratch_;      // argument records of the frame in flight
     std::vector<const uint8_t *> p0_, p1_;
     std::vector<double> t_;
     std::unique_ptr<ForkJoin> pool_, pool_ekf_;
-    static void par(ForkJoin *pool, int n, const std::function<void(int)> &fn) { if (pool) pool->run(n, fn); else for (int i = 0; i < n; ++i) fn(i); }
+    ParFor par_fe_, par_ekf_;                                 // pool_->run / pool_ekf_->run; empty without helper threads
 };
 
 class MultiRunner {

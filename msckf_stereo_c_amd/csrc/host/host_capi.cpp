@@ -68,13 +68,13 @@ void mskfh_runner_window(void *h, int g, double out[7]) {
 // wall seconds per phase inside the last timed window, summed over groups (each stage between its own marks)
 void mskfh_runner_get_window_phases(void *h, double *out) {
     MultiRunner *r = (MultiRunner *)h;
-    for (int k = 0; k < BatchGroup::PH_COUNT; ++k) out[k] = 0;
+    for (int k = 0; k < PH_COUNT; ++k) out[k] = 0;
     for (int g = 0; g < r->n_groups(); ++g)
-        for (int k = 0; k < BatchGroup::PH_COUNT; ++k) out[k] += r->group(g).window_phase_s[k];
+        for (int k = 0; k < PH_COUNT; ++k) out[k] += r->group(g).window_phase_s[k];
 }
 void mskfh_runner_get_window_phases_group(void *h, int g, double *out) {
     MultiRunner *r = (MultiRunner *)h;
-    for (int k = 0; k < BatchGroup::PH_COUNT; ++k) out[k] = r->group(g).window_phase_s[k];
+    for (int k = 0; k < PH_COUNT; ++k) out[k] = r->group(g).window_phase_s[k];
 }
 // state of local stream 0 of group g when its stages closed the window; returns the feature count (-1: no window closed)
 int mskfh_runner_mark_dump_size(void *h, int g) {
@@ -129,12 +129,12 @@ void mskfh_runner_get_abi_host_time(void *h, double *out, int reset) {
         for (mskf_ctx *c : {r->group(g).ctx(), r->group(g).ekf_ctx()}) { double t[4]; if (mskf_ctx_get_host_time(c, t, reset) == MSKF_OK) for (int k = 0; k < 4; ++k) out[k] += t[k]; }
 }
 
-// wall seconds per step() phase summed over groups (BatchGroup::PH_*), optionally reset
+// wall seconds per step() phase summed over groups (PH_*), optionally reset
 void mskfh_runner_get_phases(void *h, double *out, int reset) {
     MultiRunner *r = (MultiRunner *)h;
-    for (int k = 0; k < BatchGroup::PH_COUNT; ++k) out[k] = 0;
+    for (int k = 0; k < PH_COUNT; ++k) out[k] = 0;
     for (int g = 0; g < r->n_groups(); ++g)
-        for (int k = 0; k < BatchGroup::PH_COUNT; ++k) { out[k] += r->group(g).phase_s[k]; if (reset) r->group(g).phase_s[k] = 0; }
+        for (int k = 0; k < PH_COUNT; ++k) { out[k] += r->group(g).phase_s[k]; if (reset) r->group(g).phase_s[k] = 0; }
 }
 
 // host bookkeeping accounting (host_prof.h): seconds per slot summed over all streams/threads; returns the slot count

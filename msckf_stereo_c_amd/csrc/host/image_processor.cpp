@@ -155,31 +155,65 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         own_stream_ = true;
         mskf_fe_set_detect_floor(stream_, cfg_.fast_threshold * 256);
     }
-    if (canDeviceFrame()) {
-        // every frame after the first: one call, the bookkeeping between the tracks runs on the device
-        mskf_fe_frame_args fa;
-        if (!frameBegin(cam0_img.time_stamp, fa)) return;
-        mskf_stream *ss[1] = {stream_};
-        const uint8_t *a[1] = {cam0_img.image.data()}, *b[1] = {cam1_img.image.data()};
-        int frc = mskf_fe_frame_batch_begin(mskf_stream_ctx(stream_), 1, ss, a, b, 0, &fa);
-        if (frc == MSKF_OK) frc = mskf_fe_frame_batch_end(mskf_stream_ctx(stream_));
-        if (frc != MSKF_OK) { fail("mskf_fe_frame_batch", frc); return; }
-        frameEnd(fa, is_draw);
+    if (w != calib_.width || h != calib_.height) {
+        error_ = "mskf_fe_push_stereo: image size differs from the calibration";
+        std::fprintf(stderr, "ImageProcessor: mskf_fe_push_stereo failed (%d): image size differs from the calibration\n", MSKF_ERR_INVALID);
         return;
     }
-    phaseBegin(cam0_img.time_stamp, w, h);
-    int rc = mskf_fe_push_stereo(stream_, cam0_img.image.data(), cam1_img.image.data(), w, h, w, cam0_img.time_stamp);
-    if (rc != MSKF_OK) { fail("mskf_fe_push_stereo", rc); return; }
-    mskf_fe_track_args a1, a2;
-    phasePrepare1(a1);
-    rc = mskf_fe_track(stream_, &a1);
-    if (rc != MSKF_OK) { fail("mskf_fe_track", rc); return; }
-    phaseAfter1(a2);
-    if (a2.n > 0) {
-        rc = mskf_fe_track(stream_, &a2);
-        if (rc != MSKF_OK) { fail("mskf_fe_track", rc); return; }
+    ImageProcessor *self = this;
+    const uint8_t *a = cam0_img.image.data(), *b = cam1_img.image.data();
+    FrameScratch scratch;
+    std::string what;
+    const int rc = runFrame(mskf_stream_ctx(stream_), 1, &self, &stream_, &a, &b, 0, &cam0_img.time_stamp, is_draw, scratch, ParFor(), nullptr, what);
+    if (rc != MSKF_OK) fail(what.c_str(), rc);
+}
+
+int ImageProcessor::runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, const uint8_t *const *cam0,
+                             const uint8_t *const *cam1, int on_device, const double *t, bool is_draw, FrameScratch &s, const ParFor &par,
+                             double *acc, std::string &err) {
+    PhaseLaps lap(acc);
+    // Every frame after a stream's first runs as ONE device call (mskf_fe_frame_batch_*): pyramids, detector, both track calls
+    // and the bookkeeping between and after them; the host prepares the prediction and takes the grid.
+    bool all_dev = true;
+    for (int i = 0; i < n && all_dev; ++i) all_dev = ip[i]->canDeviceFrame();
+    if (all_dev) {
+        s.fa.resize(n);
+        bool ok = true;
+        for (int i = 0; i < n; ++i) ok = ip[i]->frameBegin(t[i], s.fa[i]) && ok;
+        if (!ok) { err = "frameBegin"; return MSKF_ERR_INVALID; }
+        lap(PH_PREP1);
+        FRAME_CHK(mskf_fe_frame_batch_begin, (ctx, n, streams, cam0, cam1, on_device, s.fa.data()));
+        lap(PH_PUSH);
+        FRAME_CHK(mskf_fe_frame_batch_end, (ctx));
+        lap(PH_TRACK1);
+        par_for(par, n, [&](int i) { ip[i]->frameEnd(s.fa[i], is_draw); });
+        lap(PH_AFTER2);
+        return MSKF_OK;
     }
-    phaseAfter2(is_draw);
+    auto track = [&](const std::vector<mskf_fe_track_args> &a) -> int {
+        FRAME_CHK(mskf_fe_track_batch_begin, (ctx, n, streams, a.data()));
+        FRAME_CHK(mskf_fe_track_batch_end, (ctx));
+        return MSKF_OK;
+    };
+    s.a1.resize(n); s.a2.resize(n);
+    for (int i = 0; i < n; ++i) ip[i]->phaseBegin(t[i], 0, 0);     // image size: the calibration the stream was created with
+    FRAME_CHK(mskf_fe_push_stereo_batch, (ctx, n, streams, cam0, cam1, on_device));
+    lap(PH_PUSH);
+    if (ip[0]->isFirstImage()) FRAME_CHK(mskf_ctx_sync, (ctx));   // first frame: detections are read right away
+    par_for(par, n, [&](int i) { ip[i]->phasePrepare1(s.a1[i]); });
+    lap(PH_PREP1);
+    int rc = track(s.a1);                          // (the detector's per-cell maxima of this push arrive with it)
+    if (rc != MSKF_OK) return rc;
+    lap(PH_TRACK1);
+    par_for(par, n, [&](int i) { ip[i]->phaseAfter1(s.a2[i]); });
+    lap(PH_AFTER1);
+    bool any2 = false;                             // no stream has candidates (a first frame): the batch would enqueue nothing
+    for (int i = 0; i < n; ++i) any2 |= s.a2[i].n > 0;
+    if (any2 && (rc = track(s.a2)) != MSKF_OK) return rc;
+    lap(PH_TRACK2);
+    par_for(par, n, [&](int i) { ip[i]->phaseAfter2(is_draw); });
+    lap(PH_AFTER2);
+    return MSKF_OK;
 }
 
 static void fill_args(mskf_fe_track_args &a, int n, int do_temporal, std::vector<mskf_point2f> &in, std::vector<mskf_point2f> &o0,
@@ -644,6 +678,11 @@ void ImageProcessor::frameEnd(const mskf_fe_frame_args &a, bool is_draw) {
     ransac_draws = (unsigned long long)a.ransac_draws;
     ++device_frames_;
     stage_ = 0;
+    finishFrame(is_draw);        // (the pyramid rotation of :194 is part of the device call)
+}
+
+// the end of both kinds of frame: the drawing containers, the message, prev <- the grid just published
+void ImageProcessor::finishFrame(bool is_draw) {
     if (is_draw) {   // :163-184
         prev_ids_.assign(prev_.id.begin(), prev_.id.end());
         prev_cam0_points_.clear(); prev_cam1_points_.clear(); curr_cam0_points_.clear(); curr_cam1_points_.clear();
@@ -652,8 +691,8 @@ void ImageProcessor::frameEnd(const mskf_fe_frame_args &a, bool is_draw) {
     }
     hostprof::Scope hp_pub(hostprof::FE_PUBLISH);
     publish();
-    if (!(cfg_.compat_flags & MSKF_COMPAT_Q2_PREV_ALIAS)) cam0_prev_time = cam0_curr_time;
-    std::swap(prev_, curr_);     // (the pyramid rotation of :194 is part of the device call)
+    if (!(cfg_.compat_flags & MSKF_COMPAT_Q2_PREV_ALIAS)) cam0_prev_time = cam0_curr_time;   // :192-200
+    std::swap(prev_, curr_);
 }
 
 void ImageProcessor::phaseAfter2(bool is_draw) {
@@ -667,17 +706,7 @@ void ImageProcessor::phaseAfter2(bool is_draw) {
         curr_.clear();
     }
     stage_ = 0;
-    if (is_draw) {   // :163-184
-        prev_ids_.assign(prev_.id.begin(), prev_.id.end());
-        prev_cam0_points_.clear(); prev_cam1_points_.clear(); curr_cam0_points_.clear(); curr_cam1_points_.clear();
-        for (size_t k = 0; k < prev_.size(); ++k) { prev_cam0_points_[prev_.id[k]] = Point2f(prev_.cam0[k].x, prev_.cam0[k].y); prev_cam1_points_[prev_.id[k]] = Point2f(prev_.cam1[k].x, prev_.cam1[k].y); }
-        for (size_t k = 0; k < curr_.size(); ++k) { curr_cam0_points_[curr_.id[k]] = Point2f(curr_.cam0[k].x, curr_.cam0[k].y); curr_cam1_points_[curr_.id[k]] = Point2f(curr_.cam1[k].x, curr_.cam1[k].y); }
-    }
-    hostprof::Scope hp_pub(hostprof::FE_PUBLISH);
-    publish();
-    // :192-200
-    if (!(cfg_.compat_flags & MSKF_COMPAT_Q2_PREV_ALIAS)) cam0_prev_time = cam0_curr_time;
-    std::swap(prev_, curr_);     // prev <- the grid just published
+    finishFrame(is_draw);
     mskf_fe_swap(stream_);
 }
 

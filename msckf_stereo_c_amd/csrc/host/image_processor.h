@@ -4,8 +4,8 @@
 // feature_msg_ptr_, the five id/point containers, processor_config).  All pixel work goes through the
 // C-ABI (include/mskf_hip.h): pyramids, detector maxima, pyramidal LK + stereo matching + gates run
 // as HIP kernels; this class keeps the reference's bookkeeping (grid buckets, sorting, ids, message).
-// stereoCallback() is exactly phasePush -> phasePrepare1 -> track -> phaseAfter1 -> track -> phaseAfter2;
-// BatchRunner drives the same phases for many streams with one batched device call per phase.
+// The order of a frame (host phase -> batched device call -> host phase -> ...) is written once, over n streams, in
+// runFrame(): stereoCallback() is runFrame() with n = 1, BatchGroup calls it with its group.
 #pragma once
 #include <fstream>
 #include <map>
@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../../include/mskf_hip.h"
 #include "cg_types.h"
+#include "frame_seq.h"
 #include "yaml_lite.h"
 
 namespace cg {
@@ -68,7 +69,17 @@ class ImageProcessor {
     typedef std::shared_ptr<ImageProcessor> Ptr;
     typedef std::shared_ptr<const ImageProcessor> ConstPtr;
 
-    // ---- device attachment + phased interface (BatchRunner)
+    // ---- the front-end of one frame of n streams of one context: push (pyramids + detector) -> track (temporal LK, stereo
+    // LK, gates) -> host bucketing / candidates -> track (candidates) -> host (ids, prune, publish); as ONE device call
+    // (mskf_fe_frame_batch_*) when every stream canDeviceFrame(), otherwise phased for all.  Image size: the streams' own.
+    // `par` shares the per-stream host phases, `acc` (or nullptr) receives the wall time per PH_* phase.  Returns the
+    // status of the call that failed and its name in `err`.
+    struct FrameScratch { std::vector<mskf_fe_track_args> a1, a2; std::vector<mskf_fe_frame_args> fa; };   // argument records, valid until the call's *_end
+    static int runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, const uint8_t *const *cam0,
+                        const uint8_t *const *cam1, int on_device, const double *t, bool is_draw, FrameScratch &scratch, const ParFor &par,
+                        double *acc, std::string &err);
+
+    // ---- device attachment + the phases runFrame() runs
     // (the detector floor: this class only ever asks for the cells above its threshold, image_processor.cpp:132)
     void attach(mskf_stream *s) { stream_ = s; if (s) mskf_fe_set_detect_floor(s, cfg_.fast_threshold * 256); }
     mskf_stream *stream() const { return stream_; }
@@ -148,6 +159,7 @@ class ImageProcessor {
         return static_cast<int>(p.y / grid_height) * cfg_.grid_col + static_cast<int>(p.x / grid_width);
     }
     void publish();
+    void finishFrame(bool is_draw);
     void fail(const char *what, int rc);
 
     YAML::Node cfg_cam_imu_;

@@ -147,42 +147,90 @@ bool MsckfVio::resetCallback() {
 
 // :306-375
 void MsckfVio::featureCallback(const CameraMeasurementConstPtr &msg) {
-    mskf_ekf_update_args upd;
-    if (!phaseA(msg, upd)) return;
-    if (upd.n_feat > 0) {
-        int rc = mskf_ekf_update(stream_, &upd);
-        if (rc != MSKF_OK) { fail("mskf_ekf_update", rc); return; }
-    }
-    phaseB(upd);
-    if (upd.n_feat > 0) {
-        int rc = mskf_ekf_update(stream_, &upd);
-        if (rc != MSKF_OK) { fail("mskf_ekf_update", rc); return; }
-    }
-    phaseC();
-    if (publishCovariance) {
-        // the covariance of the published pose: P after the frame's updates and clone removal, before onlineReset (:356, :359);
-        // its pos_var is what onlineReset tests
-        mskf_odom_cov oc;
-        int rc = mskf_ekf_get_odom_cov(stream_, &oc);
-        if (rc != MSKF_OK) { fail("mskf_ekf_get_odom_cov", rc); return; }
-        attachOdomCov(oc);
-        if (cfg_.position_std_threshold > 0) phaseD(oc.pos_var);
-        return;
-    }
-    if (cfg_.position_std_threshold > 0) {
-        if (pos_var_valid_) { phaseD(pos_var_); return; }      // came back with the frame's last update (clone removal does not touch it)
-        double pv[3];
-        int rc = mskf_ekf_get_pos_var(stream_, pv);
-        if (rc != MSKF_OK) { fail("mskf_ekf_get_pos_var", rc); return; }
-        phaseD(pv);
-    }
+    MsckfVio *self = this;
+    FrameScratch scratch;
+    std::string what;
+    const int rc = runFrame(mskf_stream_ekf_ctx(stream_), 1, &self, &stream_, &msg, scratch, ParFor(), nullptr, what);
+    if (rc != MSKF_OK) fail(what.c_str(), rc);
 }
 
-bool MsckfVio::phaseA(const CameraMeasurementConstPtr &msg, mskf_ekf_update_args &upd, bool defer_device) {
+int MsckfVio::runFrame(mskf_ctx *ekf_ctx, int n, MsckfVio *const *vio, mskf_stream *const *streams, const CameraMeasurementConstPtr *msgs,
+                       FrameScratch &s, const ParFor &par, double *acc, std::string &err) {
+    PhaseLaps lap(acc);
+    // streams with a non-empty update -> one batched launch (the args stay in upd_a until the *_end call)
+    auto updates = [&]() -> int {
+        s.upd_s.clear(); s.upd_a.clear();
+        for (int i = 0; i < n; ++i) if (s.u[i].n_feat > 0) { s.upd_s.push_back(streams[i]); s.upd_a.push_back(s.u[i]); }
+        if (s.upd_s.empty()) return MSKF_OK;
+        FRAME_CHK(mskf_ekf_update_batch_begin, (ekf_ctx, (int)s.upd_s.size(), s.upd_s.data(), s.upd_a.data()));
+        FRAME_CHK(mskf_ekf_update_batch_end, (ekf_ctx));
+        return MSKF_OK;
+    };
+    s.u.resize(n);
+    par_for(par, n, [&](int i) { vio[i]->phaseA(msgs[i], s.u[i]); });
+    bool any = false;
+    for (int i = 0; i < n; ++i) any |= vio[i]->frameActive();
+    if (!any) { lap(PH_EKF_A); return MSKF_OK; }
+    s.pred_ns.assign(n, 0); s.pred_sp.assign(n, nullptr); s.pred_jp.assign(n, nullptr);
+    for (int i = 0; i < n; ++i) {
+        const MsckfVio &v = *vio[i];
+        s.pred_ns[i] = v.frameActive() ? (int)v.predictSteps().size() : 0;
+        s.pred_sp[i] = s.pred_ns[i] ? v.predictSteps().data() : nullptr;
+        s.pred_jp[i] = v.frameActive() ? v.predictJ() : nullptr;
+    }
+    FRAME_CHK(mskf_ekf_predict_batch, (ekf_ctx, n, streams, s.pred_ns.data(), s.pred_sp.data(), s.pred_jp.data()));
+    lap(PH_EKF_A);
+    int rc = updates();
+    if (rc != MSKF_OK) return rc;
+    lap(PH_UPD1);
+    par_for(par, n, [&](int i) { if (vio[i]->frameActive()) vio[i]->phaseB(s.u[i]); else std::memset(&s.u[i], 0, sizeof(s.u[i])); });
+    lap(PH_EKF_B);
+    if ((rc = updates()) != MSKF_OK) return rc;
+    lap(PH_UPD2);
+    s.rm.assign(2 * (size_t)n, -1);
+    par_for(par, n, [&](int i) {
+        vio[i]->phaseC();
+        s.rm[2 * i] = vio[i]->pendingRemovals()[0]; s.rm[2 * i + 1] = vio[i]->pendingRemovals()[1];
+    });
+    bool any_rm = false;
+    for (int i = 0; i < n; ++i) any_rm |= s.rm[2 * i] >= 0;
+    if (any_rm) FRAME_CHK(mskf_ekf_remove_clones_batch, (ekf_ctx, n, streams, s.rm.data()));
+    lap(PH_EKF_C);
+    // publishCovariance on any stream: one read-out of all the streams' odometry covariances (msckf_vio.cpp:1262-1293) behind the
+    // clone removal, before onlineReset (:356, :359); its pos_var is what onlineReset tests, so it takes the place of the
+    // fallback below (and costs a host wait of its own)
+    bool any_cov = false;
+    for (int i = 0; i < n; ++i) any_cov |= vio[i]->publishCovariance;
+    if (any_cov) {
+        s.oc.resize(n);
+        FRAME_CHK(mskf_ekf_get_odom_cov_batch_begin, (ekf_ctx, n, streams, s.oc.data()));
+        FRAME_CHK(mskf_ekf_get_odom_cov_batch_end, (ekf_ctx));
+        for (int i = 0; i < n; ++i) {
+            if (vio[i]->publishCovariance) vio[i]->attachOdomCov(s.oc[i]);
+            vio[i]->phaseD(s.oc[i].pos_var);
+        }
+        lap(PH_POSVAR);
+        return MSKF_OK;
+    }
+    // onlineReset (msckf_vio.cpp:1186-1236) needs P(12..14) of every stream with a position_std_threshold: they came back with
+    // the frame's last update (clone removal does not touch them); only when such a stream had no update at all this frame
+    // they are fetched with a launch and a wait of their own
+    bool fetch = false;
+    for (int i = 0; i < n; ++i) fetch |= vio[i]->frameActive() && vio[i]->cfg_.position_std_threshold > 0 && !vio[i]->havePosVar();
+    if (fetch) {
+        s.pv.assign(3 * (size_t)n, 0.0);
+        FRAME_CHK(mskf_ekf_get_pos_var_batch_begin, (ekf_ctx, n, streams, s.pv.data()));
+        FRAME_CHK(mskf_ekf_get_pos_var_batch_end, (ekf_ctx));
+    }
+    for (int i = 0; i < n; ++i) vio[i]->phaseD(fetch ? &s.pv[3 * i] : vio[i]->posVar());
+    lap(PH_POSVAR);
+    return MSKF_OK;
+}
+
+bool MsckfVio::phaseA(const CameraMeasurementConstPtr &msg, mskf_ekf_update_args &upd) {
     std::memset(&upd, 0, sizeof(upd));
     frame_active_ = false;
     pos_var_valid_ = false;
-    defer_device_ = defer_device;
     have_J_ = false;
     imu_steps_.clear();
     if (!is_gravity_set) return false;
@@ -232,10 +280,6 @@ void MsckfVio::batchImuProcessing(double time_bound) {
     }
     s.id = next_state_id_++;
     imu_msg_buffer.erase(imu_msg_buffer.begin(), imu_msg_buffer.begin() + used);
-    if (!imu_steps_.empty() && !defer_device_) {
-        int rc = mskf_ekf_propagate_imu(stream_, (int)imu_steps_.size(), imu_steps_.data());
-        if (rc != MSKF_OK) fail("mskf_ekf_propagate_imu", rc);
-    }
 }
 
 // :482-531
@@ -307,10 +351,6 @@ void MsckfVio::stateAugmentation(double time) {
         J[i * 21 + 15 + i] = 1.0;
         J[(3 + i) * 21 + 12 + i] = 1.0;
         J[(3 + i) * 21 + 18 + i] = 1.0;
-    }
-    if (!defer_device_) {
-        int rc = mskf_ekf_augment(stream_, J);
-        if (rc != MSKF_OK) fail("mskf_ekf_augment", rc);
     }
 }
 
@@ -623,7 +663,7 @@ void MsckfVio::buildPruneUpdate(mskf_ekf_update_args &upd) {
     finishArgs(upd, 0, 0);   // Q12 dof = #involved, no row cap in the pruning path
 }
 
-void MsckfVio::phaseC(bool defer_device) {
+void MsckfVio::phaseC() {
     pending_rm_[0] = pending_rm_[1] = -1;
     if (!frame_active_) return;
     if (prune_pending_) {
@@ -645,12 +685,6 @@ void MsckfVio::phaseC(bool defer_device) {
             auto it = state_server.cam_states.find(cid);
             free_clone_slots_.push_back(it->second.slot);
             state_server.cam_states.erase(it);
-        }
-        if (!defer_device) {
-            mskf_stream *ss[1] = {stream_};
-            int rc = mskf_ekf_remove_clones_batch(mskf_stream_ekf_ctx(stream_), 1, ss, pending_rm_);
-            if (rc != MSKF_OK) fail("mskf_ekf_remove_clones_batch", rc);
-            pending_rm_[0] = pending_rm_[1] = -1;
         }
         prune_pending_ = false;
     }

@@ -5,8 +5,9 @@
 // featureCallback(), get_path(), get_points3d()).  The covariance never leaves the GPU: propagation,
 // augmentation, triangulation, Jacobians, gating, QR and the Kalman update run behind the C-ABI
 // (include/mskf_hip.h); this class integrates the 16-dim nominal state, keeps the clone / feature maps
-// and applies the returned correction vector.  featureCallback() is phaseA -> update -> phaseB ->
-// update -> phaseC; BatchRunner drives the same phases for many streams with batched device calls.
+// and applies the returned correction vector.  The order of a frame (phaseA -> predict -> update -> phaseB -> update ->
+// phaseC -> clone removal -> read-out -> phaseD) is written once, over n streams, in runFrame(): featureCallback() is
+// runFrame() with n = 1, BatchGroup calls it with its group.  The phases themselves never touch the device.
 #pragma once
 #include <array>
 #include <fstream>
@@ -17,6 +18,7 @@
 #include "../../../include/mskf_hip.h"
 #include "cg_types.h"
 #include "feature_store.h"
+#include "frame_seq.h"
 #include "yaml_lite.h"
 
 namespace cg {
@@ -66,20 +68,33 @@ class MsckfVio {
     typedef std::shared_ptr<MsckfVio> Ptr;
     typedef std::shared_ptr<const MsckfVio> ConstPtr;
 
-    // ---- device attachment + phased interface
+    // ---- the filter of one frame of n streams of one (filter) context: phaseA -> mskf_ekf_predict_batch (IMU propagation +
+    // augmentation) -> lost-feature update batch -> phaseB -> pruning update batch -> phaseC -> mskf_ekf_remove_clones_batch ->
+    // odometry covariances (publishCovariance on any stream), or the position variances on their own when an active stream
+    // needs them (position_std_threshold > 0) and no update of the frame brought them back -> phaseD.  The update batches take
+    // the streams with features only.  `par`, `acc`, the return value and `err`: as ImageProcessor::runFrame.
+    struct FrameScratch {      // argument records of the frame's calls
+        std::vector<mskf_ekf_update_args> u, upd_a;           // per stream; of the streams with a non-empty update (with upd_s: valid until *_end)
+        std::vector<mskf_stream *> upd_s;
+        std::vector<int32_t> pred_ns, rm;                     // prediction steps and clone removals per stream
+        std::vector<const mskf_imu_step *> pred_sp; std::vector<const double *> pred_jp;
+        std::vector<double> pv; std::vector<mskf_odom_cov> oc;   // position variances fetched on their own (3 per stream); odometry covariances
+    };
+    static int runFrame(mskf_ctx *ekf_ctx, int n, MsckfVio *const *vio, mskf_stream *const *streams, const CameraMeasurementConstPtr *msgs,
+                        FrameScratch &scratch, const ParFor &par, double *acc, std::string &err);
+
+    // ---- device attachment + the phases runFrame() runs (host only: what the device is to do they leave in predictSteps() /
+    // predictJ(), the update arguments and pendingRemovals())
     void attach(mskf_stream *s) { stream_ = s; }
     mskf_stream *stream() const { return stream_; }
-    // phase A: IMU propagation, augmentation, observations; fills the lost-feature update (n_feat may be 0)
-    // defer_device: do not issue the propagation / augmentation here; the caller batches them from
-    // predictSteps() / predictJ() with mskf_ekf_predict_batch before running the update
-    bool phaseA(const CameraMeasurementConstPtr &msg, mskf_ekf_update_args &upd, bool defer_device = false);
+    // phase A: IMU propagation and augmentation of the nominal state, observations; fills the lost-feature update (n_feat may be 0)
+    bool phaseA(const CameraMeasurementConstPtr &msg, mskf_ekf_update_args &upd);
     const std::vector<mskf_imu_step> &predictSteps() const { return imu_steps_; }
     const double *predictJ() const { return have_J_ ? J_ : nullptr; }
     // phase B: apply the lost-feature update, then prepare the pruning update (n_feat may be 0)
     void phaseB(mskf_ekf_update_args &upd);
-    // phase C: apply the pruning update, delete clones, publish; returns false if nothing ran this frame
-    // defer_device: the caller removes the clones listed in pendingRemovals() with mskf_ekf_remove_clones_batch
-    void phaseC(bool defer_device = false);
+    // phase C: apply the pruning update, delete clones (the device's copies: pendingRemovals()), publish
+    void phaseC();
     const int32_t *pendingRemovals() const { return pending_rm_; }   // two clone indices (current state order) or -1
     // phase D: online reset decision from the position variances (msckf_vio.cpp:1186-1236)
     void phaseD(const double pos_var[3]);
@@ -195,7 +210,7 @@ class MsckfVio {
     long long rows_sum_ = 0;
     std::vector<StateIDType> rm_cam_state_ids_;
     bool prune_pending_ = false;
-    bool defer_device_ = false, have_J_ = false;
+    bool have_J_ = false;
     double J_[6 * 21];
     int32_t pending_rm_[2] = {-1, -1};
     int rm_order_[2] = {-1, -1};                           // window positions of the two clones being pruned

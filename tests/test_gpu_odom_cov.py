@@ -354,12 +354,30 @@ def _write_mav0(tmp_path, syn, calib, n_frames):
     return mav0, cfg, [_app_time(t0_ns + k * dt_ns) for k in range(n_frames)], imu
 
 
+def _feed_like_the_app(run, syn, times, imu):
+    """The frames of _write_mav0 through stream 0 of a Runner in the app's order: IMU samples up to the first one past the image."""
+    from msckf_stereo_c_amd.ctypes_types import ImuSample
+    j = 0
+    for k, t_img in enumerate(times):
+        while True:
+            t, w, acc = imu[j]
+            j += 1
+            m = ImuSample()
+            m.time_stamp = t
+            m.angular_velocity[:] = w
+            m.linear_acceleration[:] = acc
+            run.imu(0, m)
+            if not (t <= t_img):
+                break
+        a, b = syn.render(k)
+        run.step([a], [b], [t_img])
+
+
 def test_app_writes_the_covariance_file(tmp_path, oracle):
     """run_euroc_single_thread with `covariance_out: cov_out.txt` in app_msckfvio.yaml: one line per line of pose_out.txt with
     the same time stamps, 1 + 36 + 9 numbers each; the last line is the last record of a Runner fed the same files' content, to
     the six decimals the std::fixed stream format prints; pose_out.txt is byte for byte what the app writes without the option."""
     from msckf_stereo_c_amd import build
-    from msckf_stereo_c_amd.ctypes_types import ImuSample
     build.build_all()
     n_frames = 32
     syn = oracle.Synth(seed=0x5EED0095, width=RUN_W, height=RUN_H, n_static=21, motion_scale=2.0)
@@ -387,20 +405,7 @@ def test_app_writes_the_covariance_file(tmp_path, oracle):
     run = RN.Runner(calib, default_fe_cfg(), default_ekf_cfg(), 1, 1)
     try:
         run.publish_covariance(True)
-        j = 0
-        for k in range(n_frames):
-            while True:
-                t, w, acc = imu[j]
-                j += 1
-                m = ImuSample()
-                m.time_stamp = t
-                m.angular_velocity[:] = w
-                m.linear_acceleration[:] = acc
-                run.imu(0, m)
-                if not (t <= times[k]):
-                    break
-            a, b = syn.render(k)
-            run.step([a], [b], [times[k]])
+        _feed_like_the_app(run, syn, times, imu)
         oc = run.odom_cov(0)
         assert len(oc) == len(cov_lines)
         last = np.array([float(v) for v in cov_lines[-1].split()])
@@ -408,5 +413,51 @@ def test_app_writes_the_covariance_file(tmp_path, oracle):
         want = _row(oc[-1:])[0][:45]
         assert np.abs(want).max() > 1e-4                                        # digits to compare survive the six decimals
         assert np.abs(last[1:] - want).max() <= 1e-6, np.abs(last[1:] - want).max()       # one unit of the last printed place
+    finally:
+        run.close()
+
+
+def test_app_equals_a_runner_of_one_line_by_line(tmp_path, oracle):
+    """The single-stream callbacks (System::stereo_callback / backend_callback, what the app runs) against a Runner(..., 1, 1) fed
+    the same files' content: EVERY line of pose_out.txt and of the covariance file equals, as text, the Runner's record of the
+    same frame printed "%.6f" per number (the app's std::fixed six decimals; both sides round correctly).
+    42 frames, not 32: the camera stands still for 21 frames, the filter's first frame is frame 20 (200 IMU samples), and the
+    app's window of 20 clones is full at frame 39 and again at frame 41, so the run has frames without an update (the variance
+    read-out of its own), lost-feature updates, two pruning updates and two clone removals."""
+    from msckf_stereo_c_amd import build
+    build.build_all()
+    n_frames = 42
+    syn = oracle.Synth(seed=0x5EED0095, width=RUN_W, height=RUN_H, n_static=21, motion_scale=2.0)
+    calib = OC.calib_with_imu_body(syn.calib, R_BODY, t=(0.1, -0.2, 0.05))
+    mav0, cfg, times, imu = _write_mav0(tmp_path, syn, calib, n_frames)
+    with open(cfg / "app_msckfvio.yaml", "a") as f:
+        f.write("\ncovariance_out: cov_out.txt\n")
+    work = tmp_path / "build"
+    work.mkdir()
+    exe = os.path.join(ROOT, "msckf_stereo_c_amd", "_build", "run_euroc_single_thread")
+    res = subprocess.run([exe, str(mav0)], cwd=work, capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    pose_lines = (work / "pose_out.txt").read_text().splitlines()
+    cov_lines = (work / "cov_out.txt").read_text().splitlines()
+    ekf = default_ekf_cfg()
+    run = RN.Runner(calib, default_fe_cfg(), ekf, 1, 1)
+    try:
+        run.keep_trajectory(True)
+        run.publish_covariance(True)
+        _feed_like_the_app(run, syn, times, imu)
+        poses, oc = run.poses(0), run.odom_cov(0)
+        cap = ekf.max_cam_state_size
+        print("poses %d, updates %d, clones %d of %d, resets %d" % (len(poses), run.num_updates(0), run.num_clones(0), cap, run.num_resets(0)))
+        # the run reached every path of the filter's frame
+        assert run.num_updates(0) > 0
+        # a full window is pruned by two in the same frame: cap - 2 or cap - 1 clones after a frame, and at least `cap` filter frames
+        assert len(poses) >= cap and run.num_clones(0) in (cap - 2, cap - 1)
+        assert run.num_resets(0) == 0
+        assert len(poses) > run.num_updates(0)               # some published frame had no update: its variances were fetched on their own
+        fmt = lambda row: " ".join("%.6f" % v for v in row)
+        assert len(pose_lines) == len(poses) and len(cov_lines) == len(oc) == len(poses)
+        for k in range(len(poses)):
+            assert pose_lines[k] == fmt([poses["t"][k]] + list(poses["p"][k]) + list(poses["q"][k])), k
+            assert cov_lines[k] == fmt([poses["t"][k]] + list(_row(oc[k:k + 1])[0][:45])), k
     finally:
         run.close()
