@@ -41,7 +41,8 @@ const char *mskf_last_error(void);
 int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.compression_mode, *_begin / *_end entry points; 3 (round 3): update args carry
                                  pos_var_out, mskf_fe_frame_batch_* (whole front-end frames on the device), mskf_ctx_timing_gate, mskf_ctx_set_wait_mode;
                                  4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter);
-                                 added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end */
+                                 added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end;
+                                 mskf_fe_set_equalize, mskf_fe_get_equalize */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -208,6 +209,30 @@ int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const int32_t *l
 int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1,
                               int on_device, mskf_fe_frame_args *args);
 int mskf_fe_frame_batch_end(mskf_ctx *ctx);
+
+/* ---- opt-in equalisation of the pushed images
+ * Off by default.  With mode 1 (global histogram equalisation) or 2 (CLAHE) every push of the stream equalises level 0 of
+ * both cameras on the device before the pyramid and the detector read it (DESIGN.md §3 has the arithmetic, which restates
+ * OpenCV's equalizeHist and 8-bit CLAHE::apply): at most three more launches per push call, for all equalising streams of the
+ * call together; streams with mode 0 take no part and see no change.  The result is written into the stream's own level-0
+ * plane, whatever the push delivered: host images and device images (on_device 1) are equalised from where the push put or
+ * found them, a BORROWED device image (on_device 2) is read once during the push and not needed afterwards (the caller may
+ * overwrite it as soon as the push's work is done; the stream never writes it).  The pyramid, the detector, both track calls,
+ * the device frame and mskf_fe_get_level all read the equalised plane.
+ * The three launches are not timed by the per-kernel timing (there is no MSKF_K_* kind for them).
+ * mskf_fe_set_equalize validates before it touches anything: MSKF_ERR_INVALID for an unknown mode, tiles_x / tiles_y < 1 or
+ * more tiles than pixels in a dimension, a negative or non-finite clip_limit (0 = no clip), and while a track or device-frame
+ * batch of the stream's context is pending (mskf_last_error names it).  It allocates the stream's LUT and histogram scratch
+ * (call it outside a run: replacing an earlier setting synchronises the device) and takes effect with the next push.
+ * The scratch is 2 x 256 x tiles_x x tiles_y bytes per stream and the histogram launch has one workgroup per tile: tile counts
+ * far beyond the usual 8 x 8 are accepted up to one tile per pixel, but cost memory and launches in proportion. */
+typedef struct mskf_fe_equalize {
+    int32_t mode;                 /* 0 off, 1 global, 2 CLAHE */
+    int32_t tiles_x, tiles_y, _pad;
+    double clip_limit;
+} mskf_fe_equalize;
+int mskf_fe_set_equalize(mskf_stream *s, const mskf_fe_equalize *cfg);
+int mskf_fe_get_equalize(mskf_stream *s, mskf_fe_equalize *out);
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);

@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import CORNER, IMU_STEP, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, ImuStep
+from .ctypes_types import CORNER, EQUALIZE_MODES, IMU_STEP, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize, ImuStep
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -61,6 +61,7 @@ EXPORTS = [
     "mskf_fe_grid_capacity", "mskf_fe_set_grid", "mskf_fe_frame_batch_begin", "mskf_fe_frame_batch_end", "mskf_ctx_set_wait_mode",
     "mskf_stream_rebind", "mskf_ctx_record_point", "mskf_ctx_wait_point", "mskf_point_destroy", "mskf_ekf_set_compression_mode",
     "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
+    "mskf_fe_set_equalize", "mskf_fe_get_equalize",
 ]
 
 
@@ -379,6 +380,19 @@ class Stream:
 
     def set_detect_floor(self, min_score):
         _chk(self.L.mskf_fe_set_detect_floor(self.h, int(min_score)))
+
+    def set_equalize(self, mode, tiles=(8, 8), clip_limit=40.0):
+        """mskf_fe_set_equalize: mode 0 / "off", 1 / "hist" (global), 2 / "clahe"; tiles = (tiles_x, tiles_y).  From the next push on."""
+        cfg = FeEqualize(int(EQUALIZE_MODES.get(mode, mode)), int(tiles[0]), int(tiles[1]), 0, float(clip_limit))
+        self.L.mskf_fe_set_equalize.argtypes = [C.c_void_p, C.POINTER(FeEqualize)]
+        _chk(self.L.mskf_fe_set_equalize(self.h, C.byref(cfg)))
+
+    def get_equalize(self):
+        """(mode, (tiles_x, tiles_y), clip_limit) as the stream holds them."""
+        cfg = FeEqualize()
+        self.L.mskf_fe_get_equalize.argtypes = [C.c_void_p, C.POINTER(FeEqualize)]
+        _chk(self.L.mskf_fe_get_equalize(self.h, C.byref(cfg)))
+        return cfg.mode, (cfg.tiles_x, cfg.tiles_y), cfg.clip_limit
 
     def cell_maxima(self):
         n = self.fe_cfg.det_rows * self.fe_cfg.det_cols

@@ -63,7 +63,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     for (auto &e : c->t_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (int i = 0; i < 3; ++i) c->desc[i].release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
-    c->jobs.release();
+    c->jobs.release(); c->eq_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
     if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
     c->ekf_desc.release();
@@ -477,6 +477,7 @@ extern "C" void mskf_stream_destroy(mskf_stream *s) {
     if (s->ctx_ekf && s->ctx_ekf != s->ctx) (void)hipStreamSynchronize(s->ctx_ekf->stream);
     for (int i = 0; i < 3; ++i) if (s->pyr[i]) (void)hipFree(s->pyr[i]);
     if (s->book.mem) (void)hipFree(s->book.mem);
+    if (s->eq.mem) (void)hipFree(s->eq.mem);
     mskf_ekf_stream_free(s);
     auto &v = s->home_ctx->streams;
     for (size_t i = 0; i < v.size(); ++i) if (v[i] == s) { v.erase(v.begin() + i); break; }
@@ -500,6 +501,76 @@ static void fill_fe_desc(const mskf_stream *s, FeStreamDev &d) {
 // The push generation as the 8-bit tag the cell keys carry in their top byte (1 .. 255; 0 is "never written").
 static inline unsigned int push_gen_tag(unsigned long long push_gen) { return (unsigned int)((push_gen - 1) % 255ULL) + 1U; }
 static inline size_t cell_key_bytes(const mskf_stream *s) { return sizeof(unsigned long long) * (size_t)s->fe.det_rows * s->fe.det_cols; }
+
+// ---- opt-in equalisation of pushed images (include/mskf_hip.h; arithmetic and job layout: fe_equalize.h)
+static int eq_validate(const mskf_stream *s, const mskf_fe_equalize *cfg) {
+    if (!s || !cfg) return MSKF_ERR_INVALID;
+    if (cfg->mode != EQ_OFF && cfg->mode != EQ_GLOBAL && cfg->mode != EQ_CLAHE) { mskf_set_error("equalize: unknown mode (0 off, 1 global, 2 CLAHE)"); return MSKF_ERR_INVALID; }
+    if (cfg->tiles_x < 1 || cfg->tiles_y < 1) { mskf_set_error("equalize: tiles_x and tiles_y must be at least 1"); return MSKF_ERR_INVALID; }
+    if (cfg->tiles_x > s->w || cfg->tiles_y > s->h) { mskf_set_error("equalize: more tiles than pixels in a dimension"); return MSKF_ERR_INVALID; }
+    if (!std::isfinite(cfg->clip_limit) || cfg->clip_limit < 0.0) { mskf_set_error("equalize: clip_limit must be finite and not negative"); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_equalize(mskf_stream *s, const mskf_fe_equalize *cfg) {
+    if (const int rc = eq_validate(s, cfg)) return rc;        // no HIP call before this
+    mskf_stream::Equalize E;                                   // everything is decided here, the stream changes at the end
+    E.cfg = *cfg; E.cfg._pad = 0;
+    size_t lut_bytes = 0, part_bytes = 0;
+    if (cfg->mode == EQ_CLAHE) {
+        E.geom = eq_geometry(s->w, s->h, cfg->tiles_x, cfg->tiles_y);
+        E.clip = eq_clip(cfg->clip_limit, E.geom.tw * E.geom.th);
+        lut_bytes = 256 * (size_t)cfg->tiles_x * cfg->tiles_y;
+    } else if (cfg->mode == EQ_GLOBAL) {
+        E.strip_rows = eq_strip_rows(s->h);
+        E.n_strips = (s->h + E.strip_rows - 1) / E.strip_rows;
+        lut_bytes = 256;
+        part_bytes = sizeof(int) * 256 * (size_t)E.n_strips;
+    }
+    MSKF_HIPCHK(hipSetDevice(s->ctx->device));
+    if (lut_bytes) {
+        MSKF_HIPCHK(hipMalloc((void **)&E.mem, 2 * (lut_bytes + part_bytes)));
+        for (int c = 0; c < 2; ++c) {
+            E.lut[c] = (uint8_t *)E.mem + c * lut_bytes;
+            E.part[c] = part_bytes ? (int *)(E.mem + 2 * lut_bytes + c * part_bytes) : nullptr;
+        }
+    }
+    if (s->eq.mem) {
+        // pushes that still read the old scratch finish first: the whole device, since the stream may have been pushed on another
+        // context before a rebind (mskf_stream_rebind); the call is made outside a run, so the wait costs nothing that matters
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) { if (E.mem) (void)hipFree(E.mem); mskf_set_error(hipGetErrorString(e)); return MSKF_ERR_HIP; }
+        (void)hipFree(s->eq.mem);
+    }
+    s->eq = E;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_equalize(mskf_stream *s, mskf_fe_equalize *out) {
+    if (!s || !out) return MSKF_ERR_INVALID;
+    *out = s->eq.cfg;
+    return MSKF_OK;
+}
+
+// The equalising images of a push: their jobs, and the grid that covers the largest of them.
+struct EqLaunch {
+    int n = 0, max_units = 1, any_global = 0, max_regions = 1, splits = 1;
+    void add(EqJob *jobs, const mskf_stream *s, int cam, const uint8_t *src, uint8_t *dst) {
+        const mskf_stream::Equalize &E = s->eq;
+        EqJob &j = jobs[n++];
+        j.src = src; j.dst = dst; j.part = E.part[cam]; j.lut = E.lut[cam];
+        j.w = s->w; j.h = s->h; j.mode = E.cfg.mode;
+        j.tiles_x = E.cfg.tiles_x; j.tiles_y = E.cfg.tiles_y; j.tw = E.geom.tw; j.th = E.geom.th; j.clip = E.clip;
+        j.strip_rows = E.strip_rows; j.n_strips = E.n_strips; j._pad = 0;
+        const bool clahe = j.mode == EQ_CLAHE;
+        max_units = std::max(max_units, clahe ? j.tiles_x * j.tiles_y : j.n_strips);
+        any_global |= clahe ? 0 : 1;
+        max_regions = std::max(max_regions, eq_regions(j.mode, j.tiles_x, j.tiles_y));
+        // a workgroup of the apply kernel takes about 4096 pixels (sixteen per lane) of its region: a region is about a tile
+        const int rw = clahe ? j.tw : j.w, rh = clahe ? j.th : j.h, rows = std::max(1, 4096 / std::max(rw, 1));
+        splits = std::max(splits, std::min(64, (rh + rows - 1) / rows));
+    }
+};
 
 // A push in the manner of the update batch: plan_push looks at the whole batch and decides everything, touching nothing (no
 // HIP call; every refusal of a push comes from here); push_accepted then waits for the staging, grows the arenas, commits
@@ -539,6 +610,10 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     // (mskf_refuse_if_owned, and _end drains the stream), and after one this wait is on an older mark, already satisfied.
     if (ctx->cell_mark_recorded && (rc = mskf_wait_event(ctx, &ctx->cell_ev, false)) != MSKF_OK) return rc;
     if ((rc = ctx->jobs.ensure((size_t)n * 2)) != MSKF_OK || (rc = ctx->desc[0].ensure(n)) != MSKF_OK) return rc;
+    // the streams that equalise their level 0 (mskf_fe_set_equalize): none by default, and then nothing below differs
+    int n_eq = 0;
+    for (int i = 0; i < n; ++i) n_eq += streams[i]->eq.cfg.mode != EQ_OFF ? 2 : 0;
+    if (n_eq && (rc = ctx->eq_jobs.ensure((size_t)n_eq)) != MSKF_OK) return rc;
     if (P.cell_bytes > ctx->cell_arena.cap) { if ((rc = ctx->cell_arena.ensure(P.cell_bytes)) != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
     // ---- commit: the streams belong to this push from here on
     ++ctx->push_gen;
@@ -549,21 +624,28 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         s->push_gen = ctx->push_gen;
         // on_device 2: borrowed device images, level 0 is read in place (caller keeps them valid and unchanged until the
         // second-next push of this stream: the previous frame's cam0 is the LK template of the next frame)
-        s->lvl0[s->i_curr0] = on_device == 2 ? cam0[i] : nullptr;
-        s->lvl0[s->i_curr1] = on_device == 2 ? cam1[i] : nullptr;
+        // (an equalising stream writes the equalised image into its own plane: nothing stays borrowed)
+        const bool borrow = on_device == 2 && s->eq.cfg.mode == EQ_OFF;
+        s->lvl0[s->i_curr0] = borrow ? cam0[i] : nullptr;
+        s->lvl0[s->i_curr1] = borrow ? cam1[i] : nullptr;
         s->has_curr = true;
     }
     // ---- enqueue: level 0 of both cameras unless it is borrowed or already there, then the levels 1 .. 3 of both cameras of
     // every stream in ONE launch (k_pyr_down3), its jobs staged together with the detector's descriptors
     static_assert(MSKF_LEVELS == 4, "k_pyr_down3 builds exactly the levels 1, 2, 3");
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    EqLaunch eql;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const uint8_t *const img[2] = {cam0[i], cam1[i]};
+        const bool eq = s->eq.cfg.mode != EQ_OFF;
+        // an equalising stream reads a device image where the caller has it (on_device 1 and 2 alike) and writes its own plane
+        const bool eq_from_caller = eq && (on_device == 1 || on_device == 2);
         for (int c = 0; c < 2; ++c) {
             const int pi = c == 0 ? s->i_curr0 : s->i_curr1;
             uint8_t *base = s->pyr[pi];
-            if (on_device != 2 && on_device != 3) MSKF_HIPCHK(hipMemcpyAsync(base, img[c], (size_t)s->w * s->h, kind, st));
+            if (on_device != 2 && on_device != 3 && !eq_from_caller) MSKF_HIPCHK(hipMemcpyAsync(base, img[c], (size_t)s->w * s->h, kind, st));
+            if (eq) eql.add(ctx->eq_jobs.h, s, c, eq_from_caller ? img[c] : base, base + s->lvl_off[0]);
             Pyr3Job &j = ctx->jobs.h[2 * (size_t)i + c];
             j.src = s->lvl0[pi] ? s->lvl0[pi] : base + s->lvl_off[0];
             j.d1 = base + s->lvl_off[1]; j.d2 = base + s->lvl_off[2]; j.d3 = base + s->lvl_off[3];
@@ -571,8 +653,11 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         }
         fill_fe_desc(s, ctx->desc[0].h[i]);
     }
-    const MskfCopy cp[2] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
-    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+    const MskfCopy cp[3] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n},
+                            {ctx->eq_jobs.d, ctx->eq_jobs.h, sizeof(EqJob) * (size_t)eql.n}};
+    if ((rc = mskf_copy_async(ctx, cp, eql.n ? 3 : 2)) != MSKF_OK) return rc;
+    // histogram, LUT, apply (fe_equalize.h): untimed, there is no MSKF_K_* kind for them
+    if (eql.n) fe_launch_equalize(ctx->eq_jobs.d, eql.n, eql.max_units, eql.any_global, eql.max_regions, eql.splits, st);
     int ts = mskf_t_begin(ctx, MSKF_K_PYR);
     fe_launch_pyr_down3(ctx->jobs.d, 2 * n, P.max_w, P.max_h, st);
     mskf_t_end(ctx, ts, P.px_pyr);

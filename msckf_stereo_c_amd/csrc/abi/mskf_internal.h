@@ -6,6 +6,7 @@
 #include "../../../include/mskf_hip.h"
 #include "../hip/fe_device.h"
 #include "../hip/fe_book.h"
+#include "../hip/fe_equalize.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -20,6 +21,7 @@ int mskf_wait(mskf_ctx *c);
 void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts, hipStream_t st);
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
+void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 }
 
 void mskf_set_error(const std::string &s);
@@ -165,6 +167,7 @@ struct mskf_ctx {
     bool cell_mark_recorded = false;  // a push has recorded cell_ev: the next push waits for it before it reuses the staging
     bool cell_keys_dirty = true;      // the key array holds bytes no generation tag explains (fresh allocation): clear before use
     PinnedDev<Pyr3Job> jobs;
+    PinnedDev<EqJob> eq_jobs;         // the equalising streams' images of a push (a front-end arena like jobs; empty until a stream turns it on)
     PinnedDev<EkfStreamDev> ekf_desc;
     PinnedDev<char> upd_in, upd_out;     // inputs / results of every stream of an update batch (one copy each way)
     PinnedDev<char> pred_arena;          // descriptors + Phi/Q or IMU steps + J of a prediction, clone removal, read-out (fenced)
@@ -219,6 +222,15 @@ struct mskf_stream {
     int det_cw = 0, det_ch = 0;
     int det_floor = 0;                // mskf_fe_set_detect_floor
     double time_stamp = 0;
+    // ---- opt-in equalisation of pushed level-0 images (mskf_fe_set_equalize; fe_equalize.h)
+    struct Equalize {
+        mskf_fe_equalize cfg{0, 8, 8, 0, 40.0};
+        EqGeom geom{};                             // mode 2
+        int clip = 0, strip_rows = 0, n_strips = 0;
+        char *mem = nullptr;                       // one allocation: the LUTs of both cameras, then (mode 1) their partial histograms
+        uint8_t *lut[2] = {nullptr, nullptr};
+        int *part[2] = {nullptr, nullptr};
+    } eq;
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

@@ -1124,6 +1124,180 @@ extern "C" void fe_launch_book(const FeBookDev *books_dev, int n_streams, int wh
     hipLaunchKernelGGL(k_fe_book, dim3(n_streams), dim3(256), scratch_bytes, st, books_dev, which);
 }
 
+// ------------------------------------------------------------------------------------------ equalisation (fe_equalize.h)
+// Opt-in equalisation of level 0 of a push, ahead of k_pyr_down3 and k_detect_cells: at most three launches for both
+// cameras of every stream of the push that has it on (blockIdx.y = image).
+//   k_eq_hist  : a workgroup owns a CLAHE tile, or a strip of rows of a globally equalised image.  16-byte loads of the
+//                aligned chunks that cover a row of its region (bytes outside the region masked; a chunk that reaches past
+//                either end of the plane, and the reflected columns of the virtual extension, byte by byte); LDS integer
+//                atomics into one sub-histogram per wavefront.  A tile goes on to its LUT in the same workgroup (clip,
+//                closed-form redistribution, scan: 256 bytes out); a strip writes its 256 counts to scratch (no global
+//                atomics, nothing to clear).
+//   k_eq_lut   : global mode only, one workgroup per image: sums the strips, scans, writes the 256-byte LUT.
+//   k_eq_apply : a workgroup owns a region between tile centres (the whole image in global mode), or a share of its rows;
+//                the four LUTs of the region sit in LDS as one dword per level; a lane owns sixteen pixels: the 16-byte
+//                chunks of the DESTINATION plane, whole ones stored as one dword x 4, the ends of a row byte by byte.
+#include "fe_equalize.h"
+namespace {
+struct __attribute__((packed, aligned(1))) eq_u4 { uint32_t v[4]; };
+// inclusive scan over the 256 threads of the workgroup (s: 256 ints of LDS, free on return after a barrier)
+__device__ __forceinline__ int eq_block_scan(int v, int *s, int tid) {
+    s[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int t = tid >= off ? s[tid - off] : 0;
+        __syncthreads();
+        s[tid] += t;
+        __syncthreads();
+    }
+    return s[tid];
+}
+__device__ __forceinline__ void eq_count16(int *hw, const uint32_t v[4], int lo, int hi) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k >= lo && k < hi) atomicAdd(&hw[(v[k >> 2] >> (8 * (k & 3))) & 255u], 1);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_eq_hist(const EqJob *jobs) {
+    const EqJob j = jobs[blockIdx.y];
+    const int unit = blockIdx.x, tid = threadIdx.x;
+    const int n_units = j.mode == EQ_CLAHE ? j.tiles_x * j.tiles_y : j.n_strips;
+    if (unit >= n_units) return;
+    __shared__ int s_hist[4][256];
+    __shared__ int s_scan[256];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_hist[k][tid] = 0;
+    __syncthreads();
+    // the region in coordinates of the (virtually extended) image: rows r0 .. r1 - 1, columns c0 .. c1 - 1
+    int r0, r1, c0, c1;
+    if (j.mode == EQ_CLAHE) {
+        const int ty = unit / j.tiles_x, tx = unit - ty * j.tiles_x;
+        r0 = ty * j.th; r1 = r0 + j.th; c0 = tx * j.tw; c1 = c0 + j.tw;
+    } else {
+        r0 = unit * j.strip_rows; r1 = min(j.h, r0 + j.strip_rows); c0 = 0; c1 = j.w;
+    }
+    int *hw = s_hist[tid >> 6];
+    const int w = j.w, h = j.h, cr = min(c1, w);          // columns c0 .. cr - 1 are columns of the image itself
+    if (cr > c0) {
+        const uintptr_t img_b = (uintptr_t)j.src, img_e = img_b + (size_t)w * h;
+        const int nch = (cr - c0 + 15) / 16 + 1;           // aligned chunks that can touch a row segment of cr - c0 bytes
+        const int n_items = (r1 - r0) * nch;
+        for (int idx = tid; idx < n_items; idx += 256) {
+            const int rr = idx / nch, ch = idx - rr * nch;
+            const uintptr_t a = img_b + (size_t)eq_src_row(r0 + rr, h) * w + c0, e = a + (size_t)(cr - c0);
+            const uintptr_t q = (a & ~(uintptr_t)15) + 16 * (uintptr_t)ch;
+            if (q >= e) continue;
+            const int lo = a > q ? (int)(a - q) : 0, hi = e - q < 16 ? (int)(e - q) : 16;
+            if (q >= img_b && q + 16 <= img_e) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(q);
+                const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
+                eq_count16(hw, vv, lo, hi);
+            } else {
+                for (int k = lo; k < hi; ++k) atomicAdd(&hw[*reinterpret_cast<const uint8_t *>(q + k)], 1);
+            }
+        }
+    }
+    if (c1 > w) {                                          // columns of the virtual extension
+        const int cv0 = max(c0, w), nv = c1 - cv0, n_items = (r1 - r0) * nv;
+        for (int idx = tid; idx < n_items; idx += 256) {
+            const int rr = idx / nv, c = cv0 + idx - rr * nv;
+            atomicAdd(&hw[j.src[(size_t)eq_src_row(r0 + rr, h) * w + eq_src_col(c, w)]], 1);
+        }
+    }
+    __syncthreads();
+    const int cnt = s_hist[0][tid] + s_hist[1][tid] + s_hist[2][tid] + s_hist[3][tid];
+    if (j.mode != EQ_CLAHE) { j.part[256 * unit + tid] = cnt; return; }
+    (void)eq_block_scan(eq_excess(cnt, j.clip), s_scan, tid);
+    const int clipped = s_scan[255];
+    __syncthreads();
+    const int cum = eq_block_scan(eq_redistributed(cnt, tid, j.clip, clipped), s_scan, tid);
+    j.lut[256 * (size_t)unit + tid] = (uint8_t)eq_clahe_entry(cum, eq_clahe_scale(j.tw * j.th));
+}
+
+__global__ __launch_bounds__(256) void k_eq_lut(const EqJob *jobs) {
+    const EqJob j = jobs[blockIdx.x];
+    if (j.mode != EQ_GLOBAL) return;
+    const int tid = threadIdx.x;
+    __shared__ int s_scan[256], s_cnt[256], s_i0;
+    int cnt = 0;
+    for (int s = 0; s < j.n_strips; ++s) cnt += j.part[256 * s + tid];
+    s_cnt[tid] = cnt;
+    if (tid == 0) s_i0 = 255;
+    __syncthreads();
+    if (cnt > 0) atomicMin(&s_i0, tid);
+    const int cum = eq_block_scan(cnt, s_scan, tid);      // (its barriers also publish s_i0)
+    const int i0 = s_i0;
+    j.lut[tid] = (uint8_t)eq_global_entry(tid, i0, s_cnt[i0], cum, j.w * j.h);
+}
+
+__global__ __launch_bounds__(256) void k_eq_apply(const EqJob *jobs, int splits) {
+    const EqJob j = jobs[blockIdx.y];
+    const int region = blockIdx.x / splits, split = blockIdx.x - region * splits, tid = threadIdx.x;
+    if (region >= eq_regions(j.mode, j.tiles_x, j.tiles_y)) return;
+    const bool clahe = j.mode == EQ_CLAHE;
+    const int w = j.w, h = j.h;
+    int x0 = 0, x1 = w, y0 = 0, y1 = h, t1x = 0, t2x = 0, t1y = 0, t2y = 0;
+    float inv_tw = 0.f, inv_th = 0.f;
+    if (clahe) {
+        // region (ry, rx): the pixels whose unclamped first tile is (ry - 1, rx - 1)
+        const int nrx = j.tiles_x + 1, ry = region / nrx, rx = region - ry * nrx;
+        inv_tw = eq_inv(j.tw); inv_th = eq_inv(j.th);
+        x0 = rx == 0 ? 0 : eq_axis_first(rx - 1, j.tw, inv_tw, w); x1 = rx == j.tiles_x ? w : eq_axis_first(rx, j.tw, inv_tw, w);
+        y0 = ry == 0 ? 0 : eq_axis_first(ry - 1, j.th, inv_th, h); y1 = ry == j.tiles_y ? h : eq_axis_first(ry, j.th, inv_th, h);
+        t1x = max(rx - 1, 0); t2x = min(rx, j.tiles_x - 1); t1y = max(ry - 1, 0); t2y = min(ry, j.tiles_y - 1);
+    }
+    const int rp = (y1 - y0 + splits - 1) / splits, ya = y0 + split * rp, yb = min(y1, ya + rp);
+    if (ya >= yb || x0 >= x1) return;
+    __shared__ uint32_t s_lut[256];
+    if (clahe) {
+        const uint8_t *r1 = j.lut + 256 * (size_t)(t1y * j.tiles_x), *r2 = j.lut + 256 * (size_t)(t2y * j.tiles_x);
+        s_lut[tid] = (uint32_t)r1[256 * t1x + tid] | ((uint32_t)r1[256 * t2x + tid] << 8) | ((uint32_t)r2[256 * t1x + tid] << 16) | ((uint32_t)r2[256 * t2x + tid] << 24);
+    } else s_lut[tid] = j.lut[tid];
+    __syncthreads();
+    const int nch = (x1 - x0 + 15) / 16 + 1, n_items = (yb - ya) * nch;
+    for (int idx = tid; idx < n_items; idx += 256) {
+        const int rr = idx / nch, ch = idx - rr * nch, y = ya + rr;
+        const size_t row = (size_t)y * w, pb = row + x0, pe = row + x1;
+        const size_t P = (pb & ~(size_t)15) + 16 * (size_t)ch;
+        if (P >= pe) continue;
+        const int lo = pb > P ? (int)(pb - P) : 0, hi = pe - P < 16 ? (int)(pe - P) : 16;
+        const bool whole = lo == 0 && hi == 16;
+        uint32_t in[4] = {0u, 0u, 0u, 0u}, out[4] = {0u, 0u, 0u, 0u};
+        if (whole) { const eq_u4 v = *reinterpret_cast<const eq_u4 *>(j.src + P); in[0] = v.v[0]; in[1] = v.v[1]; in[2] = v.v[2]; in[3] = v.v[3]; }
+        else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) if (k >= lo && k < hi) in[k >> 2] |= (uint32_t)j.src[P + k] << (8 * (k & 3));
+        }
+        EqAxis ay = {0, 0, 0.f, 0.f};
+        if (clahe) ay = eq_axis(y, inv_th, j.tiles_y);
+        const int xb = (int)(P - row);
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t v = (in[k >> 2] >> (8 * (k & 3))) & 255u, L = s_lut[v];
+            uint32_t o = L;
+            if (clahe) {
+                const EqAxis ax = eq_axis(xb + k, inv_tw, j.tiles_x);
+                o = (uint32_t)eq_interp((int)(L & 255u), (int)((L >> 8) & 255u), (int)((L >> 16) & 255u), (int)(L >> 24), ax.a, ax.a1, ay.a, ay.a1);
+            }
+            out[k >> 2] |= o << (8 * (k & 3));
+        }
+        if (whole) *reinterpret_cast<uint4 *>(j.dst + P) = make_uint4(out[0], out[1], out[2], out[3]);
+        else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) if (k >= lo && k < hi) j.dst[P + k] = (uint8_t)(out[k >> 2] >> (8 * (k & 3)));
+        }
+    }
+}
+
+// max_units: most tiles / strips of a job; max_regions, splits: the apply kernel's grid (eq_regions, shares of a region's rows)
+extern "C" void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st) {
+    if (n_jobs <= 0) return;
+    hipLaunchKernelGGL(k_eq_hist, dim3(max_units, n_jobs), dim3(256), 0, st, jobs_dev);
+    if (any_global) hipLaunchKernelGGL(k_eq_lut, dim3(n_jobs), dim3(256), 0, st, jobs_dev);
+    hipLaunchKernelGGL(k_eq_apply, dim3(max_regions * splits, n_jobs), dim3(256), 0, st, jobs_dev, splits);
+}
+
 // completion mark of the spinning wait (mskf_wait_event): one thread stores a sequence number into pinned host memory
 // once everything enqueued before it on the stream (the D2H copies included) is done
 __global__ void k_mark(volatile unsigned int *flag, unsigned int seq) {

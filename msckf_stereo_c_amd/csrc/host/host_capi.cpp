@@ -191,6 +191,15 @@ void mskfh_get_poses(void *h, int stream, mskf_pose *out) {
     const auto &p = ((MultiRunner *)h)->system(stream).msckfvio_ptr()->poses();
     std::memcpy(out, p.data(), p.size() * sizeof(mskf_pose));
 }
+// ImageProcessor::setEqualize (mskf_fe_set_equalize) of one stream, or of all (stream < 0); call before the first frame.
+// Returns the first status that is not MSKF_OK (mskf_last_error has the text).
+int mskfh_runner_set_equalize(void *h, int stream, const mskf_fe_equalize *cfg) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setEqualize(*cfg); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
 void mskfh_runner_publish_covariance(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

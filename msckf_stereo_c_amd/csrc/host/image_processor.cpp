@@ -58,6 +58,27 @@ mskf_fe_cfg fe_cfg_from_yaml(const YAML::Node &y) {
     return c;
 }
 
+mskf_fe_equalize equalize_from_yaml(const YAML::Node &y) {
+    mskf_fe_equalize c{0, 8, 8, 0, 40.0};
+    if (y["equalize"].IsDefined()) {
+        const std::string m = y["equalize"].as<std::string>();
+        if (m == "off") c.mode = 0; else if (m == "hist") c.mode = 1; else if (m == "clahe") c.mode = 2;
+        else throw YAML::Exception("yaml: equalize must be off, hist or clahe, not " + m);
+    }
+    if (y["clahe_clip_limit"].IsDefined()) c.clip_limit = y["clahe_clip_limit"].as<double>();
+    if (y["clahe_tiles_x"].IsDefined()) c.tiles_x = y["clahe_tiles_x"].as<int>();
+    if (y["clahe_tiles_y"].IsDefined()) c.tiles_y = y["clahe_tiles_y"].as<int>();
+    return c;
+}
+
+int ImageProcessor::setEqualize(const mskf_fe_equalize &cfg) {
+    if (!initialized_ || !stream_) { eq_cfg_ = cfg; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
+    const int rc = mskf_fe_set_equalize(stream_, &cfg);
+    if (rc != MSKF_OK) { fail("mskf_fe_set_equalize", rc); return rc; }      // refused: equalize() keeps reporting what the stream holds
+    eq_cfg_ = cfg;
+    return rc;
+}
+
 ImageProcessor::ImageProcessor(YAML::Node cfg_cam_imu)
     : feature_msg_ptr_(new CameraMeasurement), cfg_cam_imu_(cfg_cam_imu), have_yaml_(true) {
     std::memset(&calib_, 0, sizeof(calib_));
@@ -87,6 +108,7 @@ bool ImageProcessor::loadParameters() {
         calib_ = calib_from_yaml(cfg_cam_imu_);
         YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");   // Q16
         cfg_ = fe_cfg_from_yaml(cfg_imgproc);
+        eq_cfg_ = equalize_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
     processor_config.grid_col = cfg_.grid_col;
@@ -115,6 +137,9 @@ bool ImageProcessor::initialize() {
     if (!loadParameters()) return false;
     occupancy_.assign((size_t)cfg_.det_rows * cfg_.det_cols, 0);
     if (have_yaml_) debug_.open("debug_imageprocessor.txt");
+    initialized_ = true;
+    // the opt-in equalisation of the pushed images; a stream that never asked for it is not touched
+    if (stream_ && eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return false;
     return true;
 }
 
@@ -154,6 +179,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if (rc != MSKF_OK) { fail("mskf_stream_create", rc); return; }
         own_stream_ = true;
         mskf_fe_set_detect_floor(stream_, cfg_.fast_threshold * 256);
+        if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return;
     }
     if (w != calib_.width || h != calib_.height) {
         error_ = "mskf_fe_push_stereo: image size differs from the calibration";

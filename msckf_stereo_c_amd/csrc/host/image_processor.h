@@ -21,6 +21,9 @@ namespace cg {
 
 mskf_calib calib_from_yaml(const YAML::Node &cfg_cam_imu);
 mskf_fe_cfg fe_cfg_from_yaml(const YAML::Node &cfg_imgproc);
+// optional keys of the same file (not keys of the reference): equalize: off | hist | clahe, clahe_clip_limit, clahe_tiles_x,
+// clahe_tiles_y (mskf_fe_set_equalize; absent = off, 40.0, 8, 8).  Throws YAML::Exception on an unknown equalize value.
+mskf_fe_equalize equalize_from_yaml(const YAML::Node &cfg_imgproc);
 
 // twoPointRansac of image_processor.cpp:911-1135 on points already undistorted to normalised coordinates; `ransac_draws`
 // is the state of the counter-based draw generator (see ImageProcessor::twoPointRansac)
@@ -82,6 +85,10 @@ class ImageProcessor {
     // ---- device attachment + the phases runFrame() runs
     // (the detector floor: this class only ever asks for the cells above its threshold, image_processor.cpp:132)
     void attach(mskf_stream *s) { stream_ = s; if (s) mskf_fe_set_detect_floor(s, cfg_.fast_threshold * 256); }
+    // opt-in equalisation of the pushed images (mskf_fe_set_equalize).  Before initialize(): kept, and set on the stream there (or
+    // when a stand-alone processor creates its stream); afterwards, before the first frame: set at once.  Returns the setter's status.
+    int setEqualize(const mskf_fe_equalize &cfg);
+    const mskf_fe_equalize &equalize() const { return eq_cfg_; }
     mskf_stream *stream() const { return stream_; }
     void phaseBegin(double time_stamp, int width, int height);      // timestamps, Q2 aliasing, grid size (Q7)
     void phasePrepare1(mskf_fe_track_args &args);                   // first frame: detections; else prev features
@@ -164,6 +171,8 @@ class ImageProcessor {
 
     YAML::Node cfg_cam_imu_;
     bool have_yaml_ = false;
+    mskf_fe_equalize eq_cfg_{0, 8, 8, 0, 40.0};
+    bool initialized_ = false;
     mskf_calib calib_;
     mskf_fe_cfg cfg_;
     mskf_stream *stream_ = nullptr;

@@ -8,7 +8,9 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
     try {
         cfg_cam_imu_ = YAML::LoadFile(file_cam_imu);
         mskf_calib calib = calib_from_yaml(cfg_cam_imu_);
-        mskf_fe_cfg fe = fe_cfg_from_yaml(YAML::LoadFile("../config/app_imgproc.yaml"));
+        const YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");
+        mskf_fe_cfg fe = fe_cfg_from_yaml(cfg_imgproc);
+        equalize_ = equalize_from_yaml(cfg_imgproc);
         const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);
@@ -35,6 +37,7 @@ void System::setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ek
     if (rc != MSKF_OK) { std::cerr << "Cannot create the device stream: " << mskf_last_error() << std::endl; return; }
     imgproc_ptr_.reset(new cg::ImageProcessor(calib, fe));
     imgproc_ptr_->attach(stream_);
+    imgproc_ptr_->setEqualize(equalize_);      // (kept until initialize())
     if (!imgproc_ptr_->initialize()) { std::cerr << "Cannot initialize Image Processor..." << std::endl; return; }
     msckfvio_ptr_.reset(new cg::MsckfVio(calib, ekf));
     msckfvio_ptr_->attach(stream_);

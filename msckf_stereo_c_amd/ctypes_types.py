@@ -67,6 +67,15 @@ class OdomCov(C.Structure):
     _fields_ = [("pose", C.c_double * 36), ("twist", C.c_double * 9), ("pos_var", C.c_double * 3)]
 
 
+class FeEqualize(C.Structure):
+    """mskf_fe_equalize (include/mskf_hip.h): opt-in equalisation of the pushed images; mode 0 off, 1 global, 2 CLAHE."""
+    _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("_pad", C.c_int32), ("clip_limit", C.c_double)]
+
+
+assert C.sizeof(FeEqualize) == 24
+EQUALIZE_MODES = {"off": 0, "hist": 1, "clahe": 2}
+
+
 # numpy dtypes of the array records
 POINT2F = np.dtype([("x", "<f4"), ("y", "<f4")])
 CORNER = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<i4"), ("cell", "<i4")])

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .capi import MskfError
-from .ctypes_types import FEATURE_MEAS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, ImuSample, TrackingInfo
+from .ctypes_types import EQUALIZE_MODES, FEATURE_MEAS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, ImuSample, TrackingInfo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -38,6 +38,7 @@ def lib():
         L.mskfh_runner_keep_trajectory.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_runner_keep_trajectory_stream.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mskfh_runner_publish_covariance.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.mskfh_runner_set_equalize.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeEqualize)]
         L.mskfh_num_odom_covs.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_num_odom_covs.restype = C.c_int
         L.mskfh_get_odom_covs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -195,6 +196,15 @@ class Runner:
             self.L.mskfh_runner_keep_trajectory(self.h, int(keep))
         else:
             self.L.mskfh_runner_keep_trajectory_stream(self.h, int(stream), int(keep))
+
+    def set_equalize(self, mode, tiles=(8, 8), clip_limit=40.0, stream=None):
+        """Opt-in equalisation of the pushed images of one stream or of all (mskf_fe_set_equalize): mode "off" / 0, "hist" / 1
+        (global histogram equalisation), "clahe" / 2 with tiles = (tiles_x, tiles_y) and clip_limit.  Call before the first frame."""
+        cfg = FeEqualize(int(EQUALIZE_MODES.get(mode, mode)), int(tiles[0]), int(tiles[1]), 0, float(clip_limit))
+        rc = self.L.mskfh_runner_set_equalize(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
 
     def publish_covariance(self, on, stream=None):
         """MsckfVio::publishCovariance of one stream or of all: every published pose gets its 6 x 6 pose and 3 x 3 velocity
