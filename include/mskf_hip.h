@@ -42,7 +42,7 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  pos_var_out, mskf_fe_frame_batch_* (whole front-end frames on the device), mskf_ctx_timing_gate, mskf_ctx_set_wait_mode;
                                  4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter);
                                  added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end;
-                                 mskf_fe_set_equalize, mskf_fe_get_equalize */
+                                 mskf_fe_set_equalize, mskf_fe_get_equalize; mskf_fe_set_input_format, mskf_fe_get_input_format */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -115,7 +115,9 @@ void mskf_point_destroy(mskf_point *point);
  */
 
 /* Upload one stereo pair (host memory, row pitch in bytes), build the 4-level pyramids of both
- * cameras and the detector's per-cell maxima of cam0 level 0.  Asynchronous on the context stream. */
+ * cameras and the detector's per-cell maxima of cam0 level 0.  Asynchronous on the context stream.
+ * The image pointers of every push mean raw bytes in the stream's input format (mskf_fe_set_input_format; 8-bit grey by
+ * default): pitch >= width * bytes per pixel here, and "dense" means pitch == width * bytes per pixel everywhere else. */
 int mskf_fe_push_stereo(mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch,
                         double time_stamp);
 /* Same with the images already resident in device memory (dense, pitch == width). */
@@ -233,6 +235,37 @@ typedef struct mskf_fe_equalize {
 } mskf_fe_equalize;
 int mskf_fe_set_equalize(mskf_stream *s, const mskf_fe_equalize *cfg);
 int mskf_fe_get_equalize(mskf_stream *s, mskf_fe_equalize *out);
+
+/* ---- opt-in input pixel formats: 16-bit grey, interleaved colour and 8-bit Bayer images, converted on the device
+ * MSKF_PIX_GRAY8 by default, and then nothing new runs.  With another format every push of the stream takes raw bytes in that
+ * format through the same pointers (const uint8_t *, rows dense or `pitch` bytes apart as the entry point says) and converts
+ * them to the 8-bit grey level 0 of both cameras on the device before anything else reads it (DESIGN.md §3 has the integer
+ * arithmetic): one more launch per push call, for all converting streams of the call together; streams on GRAY8 take no
+ * part and see no change; streams of different formats mix freely in a batch.  From level 0 on everything is as if the caller
+ * had pushed the converted 8-bit image: the equalisation, if on, runs on the converted plane, in place.
+ *   GRAY16: little-endian unsigned 16-bit, g = min(v >> shift, 255) (12-bit data: shift 4, 10-bit: 2, full 16-bit: 8); image
+ *           pointers and pitch must be 2-byte aligned (a push that is not is refused and changes nothing);
+ *   RGB8 / BGR8 / RGBA8 / BGRA8: interleaved, the fourth byte is ignored; Y = (9798 R + 19235 G + 3735 B + 16384) >> 15;
+ *   BAYER_*8: 8-bit mosaic, bilinear demosaic with REFLECT_101 borders, then the same luma.  The name spells the 2 x 2 tile at
+ *           the image's top-left corner in reading order (row 0: x = 0, 1; row 1: x = 0, 1).  This is NOT OpenCV's naming.
+ * The result is written into the stream's own level-0 plane, whatever the push delivered: host images (on_device 0) are
+ * copied into the stream's raw staging and converted from there; device images (on_device 1 and 2) are converted from where
+ * the caller has them.  Nothing stays borrowed: a borrowed image (on_device 2) is read once during the push and never
+ * written, and the caller may overwrite it as soon as the push's work is done (mskf_ctx_sync).
+ * The launch is not timed by the per-kernel timing (there is no MSKF_K_* kind for it).
+ * mskf_fe_set_input_format validates before it touches anything: MSKF_ERR_INVALID for an unknown format, a shift outside
+ * 0 .. 8, a shift other than 0 with a format other than GRAY16, and while a track or device-frame batch of the stream's
+ * context is pending (mskf_last_error names it).  For a format other than GRAY8 it allocates the stream's raw staging
+ * (2 x width x height x bytes per pixel of device memory, for host pushes); setting GRAY8 again releases it and the stream is
+ * exactly as before.  Call it outside a run (replacing an earlier setting synchronises the device); it takes effect with
+ * the next push. */
+enum {
+    MSKF_PIX_GRAY8 = 0, MSKF_PIX_GRAY16 = 1, MSKF_PIX_RGB8 = 2, MSKF_PIX_BGR8 = 3, MSKF_PIX_RGBA8 = 4, MSKF_PIX_BGRA8 = 5,
+    MSKF_PIX_BAYER_RGGB8 = 6, MSKF_PIX_BAYER_GRBG8 = 7, MSKF_PIX_BAYER_GBRG8 = 8, MSKF_PIX_BAYER_BGGR8 = 9
+};
+typedef struct mskf_fe_input_format { int32_t format; int32_t shift; } mskf_fe_input_format;
+int mskf_fe_set_input_format(mskf_stream *s, const mskf_fe_input_format *cfg);
+int mskf_fe_get_input_format(mskf_stream *s, mskf_fe_input_format *out);
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);

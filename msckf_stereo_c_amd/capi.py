@@ -5,7 +5,8 @@ import os
 
 import numpy as np
 
-from .ctypes_types import CORNER, EQUALIZE_MODES, IMU_STEP, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize, ImuStep
+from .ctypes_types import (CORNER, EQUALIZE_MODES, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
+                           FeInputFormat, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -61,7 +62,7 @@ EXPORTS = [
     "mskf_fe_grid_capacity", "mskf_fe_set_grid", "mskf_fe_frame_batch_begin", "mskf_fe_frame_batch_end", "mskf_ctx_set_wait_mode",
     "mskf_stream_rebind", "mskf_ctx_record_point", "mskf_ctx_wait_point", "mskf_point_destroy", "mskf_ekf_set_compression_mode",
     "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
-    "mskf_fe_set_equalize", "mskf_fe_get_equalize",
+    "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
 ]
 
 
@@ -121,9 +122,11 @@ def _handles(streams):
     return (C.c_void_p * len(streams))(*[None if s is None else s.h for s in streams])
 
 
-def _images(imgs):
-    """(C array of addresses, what keeps them alive): an entry is an h x w uint8 host image, a device address, or None."""
-    keep = [np.ascontiguousarray(x, dtype=np.uint8) if isinstance(x, np.ndarray) else x for x in imgs]
+def _images(imgs, streams=None):
+    """(C array of addresses, what keeps them alive): an entry is a host image in its stream's input format (h x w uint8 by
+    default; Stream.set_input_format), a device address, or None."""
+    fmts = [0 if streams is None or s is None else s.input_format for s in (imgs if streams is None else streams)]
+    keep = [raw_raster(x, f) if isinstance(x, np.ndarray) else x for x, f in zip(imgs, fmts)]
     return (C.c_void_p * len(keep))(*[x.ctypes.data if isinstance(x, np.ndarray) else x for x in keep]), keep
 
 
@@ -205,8 +208,8 @@ class Context:
 
     def push_stereo_batch(self, streams, cam0s, cam1s, on_device=0):
         """One mskf_fe_push_stereo_batch: host images (on_device = 0) or device addresses (1: copied, 2: borrowed)."""
-        a, _keep_a = _images(cam0s)
-        b, _keep_b = _images(cam1s)
+        a, _keep_a = _images(cam0s, streams)
+        b, _keep_b = _images(cam1s, streams)
         _chk(self.L.mskf_fe_push_stereo_batch(self.h, len(streams), _handles(streams), a, b, on_device))
 
     def frame_batch_begin(self, streams, images, args, on_device=0):
@@ -214,8 +217,8 @@ class Context:
         push_stereo_batch; args[i] = dict(Hpred=3 x 3 or None for the identity, R_p_c=2 x 3 x 3 or None, capacity=entries of the
         output arrays or None for the stream's grid_capacity()).  frame_batch_end returns the results."""
         n = len(streams)
-        a, keep_a = _images([im[0] for im in images])
-        b, keep_b = _images([im[1] for im in images])
+        a, keep_a = _images([im[0] for im in images], streams)
+        b, keep_b = _images([im[1] for im in images], streams)
         fa = (FeFrameArgs * n)()
         outs = []
         for i, (s, kw) in enumerate(zip(streams, args)):
@@ -343,6 +346,7 @@ class Stream:
         self.ctx, self.L = ctx, ctx.L
         self.calib, self.fe_cfg, self.ekf_cfg = calib, fe_cfg, ekf_cfg
         self.h = C.c_void_p()
+        self.input_format = 0          # MSKF_PIX_GRAY8 (set_input_format keeps it)
         _chk(self.L.mskf_stream_create(ctx.h, C.byref(calib), C.byref(fe_cfg), C.byref(ekf_cfg), C.byref(self.h)))
         ctx.streams.append(self)
 
@@ -355,14 +359,18 @@ class Stream:
 
     # ---- front-end
     def push_stereo(self, cam0, cam1, t=0.0, pitch=None):
-        """cam0 / cam1: h x w images, or (pitch given) h x pitch buffers whose first w = calib.width columns are the image."""
-        cam0 = np.ascontiguousarray(cam0, dtype=np.uint8)
-        cam1 = np.ascontiguousarray(cam1, dtype=np.uint8)
-        h, w = cam0.shape
+        """cam0 / cam1: h x w images, or (pitch given) h x pitch buffers whose first w = calib.width columns are the image.
+        With an input format (set_input_format): images of its dtype and shape ((h, w) uint16, (h, w, 3 | 4) uint8, (h, w) uint8),
+        or (pitch given) h x pitch uint8 buffers of raw bytes whose first w * bytes-per-pixel columns are the image."""
         if pitch is not None:
-            assert cam0.shape[1] == pitch and cam1.shape == cam0.shape
-            w = self.calib.width
-        _chk(self.L.mskf_fe_push_stereo(self.h, _p(cam0), _p(cam1), w, h, w if pitch is None else pitch, t))
+            cam0, cam1 = np.ascontiguousarray(cam0, dtype=np.uint8), np.ascontiguousarray(cam1, dtype=np.uint8)
+            assert cam0.ndim == 2 and cam0.shape[1] == pitch and cam1.shape == cam0.shape
+            h, w = cam0.shape[0], self.calib.width
+        else:
+            cam0, cam1 = raw_raster(cam0, self.input_format), raw_raster(cam1, self.input_format)
+            assert cam1.shape == cam0.shape
+            h, w = cam0.shape[:2]
+        _chk(self.L.mskf_fe_push_stereo(self.h, _p(cam0), _p(cam1), w, h, w * INPUT_FORMAT_BPP[self.input_format] if pitch is None else pitch, t))
 
     def grid_capacity(self):
         """Entries a published grid of this stream can have; 0: the stream keeps its books on the host."""
@@ -393,6 +401,23 @@ class Stream:
         self.L.mskf_fe_get_equalize.argtypes = [C.c_void_p, C.POINTER(FeEqualize)]
         _chk(self.L.mskf_fe_get_equalize(self.h, C.byref(cfg)))
         return cfg.mode, (cfg.tiles_x, cfg.tiles_y), cfg.clip_limit
+
+    def set_input_format(self, fmt, shift=0):
+        """mskf_fe_set_input_format: fmt is a name ("gray8", "gray16", "rgb8", "bgr8", "rgba8", "bgra8", "bayer_rggb8", "bayer_grbg8",
+        "bayer_gbrg8", "bayer_bggr8") or its number; shift (0 .. 8) goes with gray16: g = min(v >> shift, 255).  From the next push on."""
+        if isinstance(fmt, str) and fmt not in INPUT_FORMATS:
+            raise MskfError("unknown input format %r" % (fmt,), -1)
+        cfg = FeInputFormat(int(INPUT_FORMATS.get(fmt, fmt)), int(shift))
+        self.L.mskf_fe_set_input_format.argtypes = [C.c_void_p, C.POINTER(FeInputFormat)]
+        _chk(self.L.mskf_fe_set_input_format(self.h, C.byref(cfg)))
+        self.input_format = cfg.format
+
+    def get_input_format(self):
+        """(format number, shift) as the stream holds them."""
+        cfg = FeInputFormat()
+        self.L.mskf_fe_get_input_format.argtypes = [C.c_void_p, C.POINTER(FeInputFormat)]
+        _chk(self.L.mskf_fe_get_input_format(self.h, C.byref(cfg)))
+        return cfg.format, cfg.shift
 
     def cell_maxima(self):
         n = self.fe_cfg.det_rows * self.fe_cfg.det_cols

@@ -63,7 +63,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     for (auto &e : c->t_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (int i = 0; i < 3; ++i) c->desc[i].release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
-    c->jobs.release(); c->eq_jobs.release();
+    c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
     if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
     c->ekf_desc.release();
@@ -478,6 +478,7 @@ extern "C" void mskf_stream_destroy(mskf_stream *s) {
     for (int i = 0; i < 3; ++i) if (s->pyr[i]) (void)hipFree(s->pyr[i]);
     if (s->book.mem) (void)hipFree(s->book.mem);
     if (s->eq.mem) (void)hipFree(s->eq.mem);
+    if (s->px.raw) (void)hipFree(s->px.raw);
     mskf_ekf_stream_free(s);
     auto &v = s->home_ctx->streams;
     for (size_t i = 0; i < v.size(); ++i) if (v[i] == s) { v.erase(v.begin() + i); break; }
@@ -572,6 +573,61 @@ struct EqLaunch {
     }
 };
 
+// ---- opt-in input pixel formats (include/mskf_hip.h; arithmetic and job layout: fe_pixfmt.h)
+static inline size_t px_raw_bytes(const mskf_stream *s) { return (size_t)s->w * s->h * s->px.bpp; }      // one camera's raw raster, dense
+
+static int px_validate(const mskf_stream *s, const mskf_fe_input_format *cfg) {
+    if (!s || !cfg) return MSKF_ERR_INVALID;
+    if (px_bpp(cfg->format) == 0) { mskf_set_error("input format: unknown format (MSKF_PIX_GRAY8 .. MSKF_PIX_BAYER_BGGR8)"); return MSKF_ERR_INVALID; }
+    if (cfg->shift < 0 || cfg->shift > PX_MAX_SHIFT) { mskf_set_error("input format: shift must be 0 .. 8"); return MSKF_ERR_INVALID; }
+    if (cfg->shift != 0 && cfg->format != PX_GRAY16) { mskf_set_error("input format: a shift other than 0 goes with MSKF_PIX_GRAY16 only"); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_input_format(mskf_stream *s, const mskf_fe_input_format *cfg) {
+    if (const int rc = px_validate(s, cfg)) return rc;        // no HIP call before this
+    mskf_stream::PixFmt X;                                     // everything is decided here, the stream changes at the end
+    X.cfg = *cfg; X.bpp = px_bpp(cfg->format);
+    MSKF_HIPCHK(hipSetDevice(s->ctx->device));
+    if (cfg->format != PX_GRAY8) MSKF_HIPCHK(hipMalloc((void **)&X.raw, 2 * (size_t)s->w * s->h * X.bpp));
+    if (s->px.raw) {
+        // pushes that still read the old staging finish first (the whole device: mskf_fe_set_equalize has the reason)
+        const hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) { if (X.raw) (void)hipFree(X.raw); mskf_set_error(hipGetErrorString(e)); return MSKF_ERR_HIP; }
+        (void)hipFree(s->px.raw);
+    }
+    s->px = X;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_input_format(mskf_stream *s, mskf_fe_input_format *out) {
+    if (!s || !out) return MSKF_ERR_INVALID;
+    *out = s->px.cfg;
+    return MSKF_OK;
+}
+
+// What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
+// 16-bit pixels on 2-byte boundaries.
+static int px_check_images(const mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, long long pitch) {
+    if (pitch < (long long)s->w * s->px.bpp) { mskf_set_error("image size differs from the calibration"); return MSKF_ERR_INVALID; }
+    if (s->px.cfg.format == PX_GRAY16 && ((((uintptr_t)cam0 | (uintptr_t)cam1) & 1) || (pitch & 1))) {
+        mskf_set_error("input format: MSKF_PIX_GRAY16 images and their pitch must be 2-byte aligned");
+        return MSKF_ERR_INVALID;
+    }
+    return MSKF_OK;
+}
+
+// The converting images of a push: their jobs, and the size of the largest of them.
+struct PxLaunch {
+    int n = 0, max_w = 0, max_h = 0;
+    void add(PxJob *jobs, const mskf_stream *s, const uint8_t *src, uint8_t *dst) {
+        PxJob &j = jobs[n++];
+        j.src = src; j.dst = dst; j.pitch = (long long)s->w * s->px.bpp;
+        j.w = s->w; j.h = s->h; j.format = s->px.cfg.format; j.shift = s->px.cfg.shift;
+        max_w = std::max(max_w, j.w); max_h = std::max(max_h, j.h);
+    }
+};
+
 // A push in the manner of the update batch: plan_push looks at the whole batch and decides everything, touching nothing (no
 // HIP call; every refusal of a push comes from here); push_accepted then waits for the staging, grows the arenas, commits
 // the streams' and the context's fields and enqueues.
@@ -580,6 +636,9 @@ struct PushPlan {
     int max_w = 0, max_h = 0;
     long long px_pyr = 0, px_det = 0; // timing units: output pixels of the levels 1 .. 3 of both cameras, pixels of cam0 level 0
 };
+// (mskf_fe_push_stereo with padded rows enqueues its 2-D copies into the stream's own planes, or its raw staging, BEFORE it comes
+// here: a refusal added to this function must also be looked at there, ahead of those copies, as px_check_images and
+// mskf_refuse_if_owned are for a converting stream.)
 static int plan_push(const mskf_ctx *ctx, int n, const mskf_stream *const *streams, const uint8_t *const *cam0, const uint8_t *const *cam1, int on_device, PushPlan &P) {
     if (!ctx || n <= 0 || !streams || !cam0 || !cam1) return MSKF_ERR_INVALID;
     // the pinned staging of a pending batch (descriptors, pyramid jobs, the cell arena) may still be in flight
@@ -588,7 +647,10 @@ static int plan_push(const mskf_ctx *ctx, int n, const mskf_stream *const *strea
         const mskf_stream *s = streams[i];
         if (!s || s->ctx != ctx || !cam0[i] || !cam1[i]) return MSKF_ERR_INVALID;
         // on_device 3: level 0 already sits in the stream's own planes (mskf_fe_push_stereo with padded rows)
-        if (on_device == 3 && (cam0[i] != s->pyr[s->i_curr0] || cam1[i] != s->pyr[s->i_curr1])) return MSKF_ERR_INVALID;
+        // (a converting stream: the raw rasters already sit in its raw staging)
+        if (on_device == 3 && (s->px.raw ? (cam0[i] != s->px.raw || cam1[i] != s->px.raw + px_raw_bytes(s))
+                                         : (cam0[i] != s->pyr[s->i_curr0] || cam1[i] != s->pyr[s->i_curr1]))) return MSKF_ERR_INVALID;
+        if (s->px.raw) { if (const int rc = px_check_images(s, cam0[i], cam1[i], (long long)s->w * s->px.bpp)) return rc; }
         P.cell_bytes += cell_key_bytes(s);
         P.max_w = std::max(P.max_w, s->w); P.max_h = std::max(P.max_h, s->h);
         for (int l = 1; l < MSKF_LEVELS; ++l) P.px_pyr += 2LL * s->lw[l] * s->lh[l];
@@ -614,6 +676,10 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     int n_eq = 0;
     for (int i = 0; i < n; ++i) n_eq += streams[i]->eq.cfg.mode != EQ_OFF ? 2 : 0;
     if (n_eq && (rc = ctx->eq_jobs.ensure((size_t)n_eq)) != MSKF_OK) return rc;
+    // ... and the streams that convert their raw images (mskf_fe_set_input_format): the same holds
+    int n_px = 0;
+    for (int i = 0; i < n; ++i) n_px += streams[i]->px.raw ? 2 : 0;
+    if (n_px && (rc = ctx->px_jobs.ensure((size_t)n_px)) != MSKF_OK) return rc;
     if (P.cell_bytes > ctx->cell_arena.cap) { if ((rc = ctx->cell_arena.ensure(P.cell_bytes)) != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
     // ---- commit: the streams belong to this push from here on
     ++ctx->push_gen;
@@ -625,7 +691,8 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         // on_device 2: borrowed device images, level 0 is read in place (caller keeps them valid and unchanged until the
         // second-next push of this stream: the previous frame's cam0 is the LK template of the next frame)
         // (an equalising stream writes the equalised image into its own plane: nothing stays borrowed)
-        const bool borrow = on_device == 2 && s->eq.cfg.mode == EQ_OFF;
+        // (nor with a converting stream: the converted image is written into its own plane)
+        const bool borrow = on_device == 2 && s->eq.cfg.mode == EQ_OFF && !s->px.raw;
         s->lvl0[s->i_curr0] = borrow ? cam0[i] : nullptr;
         s->lvl0[s->i_curr1] = borrow ? cam1[i] : nullptr;
         s->has_curr = true;
@@ -635,16 +702,30 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     static_assert(MSKF_LEVELS == 4, "k_pyr_down3 builds exactly the levels 1, 2, 3");
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     EqLaunch eql;
+    PxLaunch pxl;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const uint8_t *const img[2] = {cam0[i], cam1[i]};
         const bool eq = s->eq.cfg.mode != EQ_OFF;
+        // a converting stream reads a device image where the caller has it (on_device 1 and 2 alike), a host image from its raw
+        // staging, and writes its own plane: what follows (the equalisation included) finds level 0 there
+        const bool cv = s->px.raw != nullptr;
         // an equalising stream reads a device image where the caller has it (on_device 1 and 2 alike) and writes its own plane
-        const bool eq_from_caller = eq && (on_device == 1 || on_device == 2);
+        const bool eq_from_caller = eq && !cv && (on_device == 1 || on_device == 2);
         for (int c = 0; c < 2; ++c) {
             const int pi = c == 0 ? s->i_curr0 : s->i_curr1;
             uint8_t *base = s->pyr[pi];
-            if (on_device != 2 && on_device != 3 && !eq_from_caller) MSKF_HIPCHK(hipMemcpyAsync(base, img[c], (size_t)s->w * s->h, kind, st));
+            if (cv) {
+                const uint8_t *raw = img[c];
+                if (on_device == 0 || on_device == 3) {
+                    uint8_t *stage = s->px.raw + c * px_raw_bytes(s);
+                    if (on_device == 0) MSKF_HIPCHK(hipMemcpyAsync(stage, img[c], px_raw_bytes(s), hipMemcpyHostToDevice, st));
+                    raw = stage;
+                }
+                pxl.add(ctx->px_jobs.h, s, raw, base + s->lvl_off[0]);
+            } else if (on_device != 2 && on_device != 3 && !eq_from_caller) {
+                MSKF_HIPCHK(hipMemcpyAsync(base, img[c], (size_t)s->w * s->h, kind, st));
+            }
             if (eq) eql.add(ctx->eq_jobs.h, s, c, eq_from_caller ? img[c] : base, base + s->lvl_off[0]);
             Pyr3Job &j = ctx->jobs.h[2 * (size_t)i + c];
             j.src = s->lvl0[pi] ? s->lvl0[pi] : base + s->lvl_off[0];
@@ -653,9 +734,13 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         }
         fill_fe_desc(s, ctx->desc[0].h[i]);
     }
-    const MskfCopy cp[3] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n},
-                            {ctx->eq_jobs.d, ctx->eq_jobs.h, sizeof(EqJob) * (size_t)eql.n}};
-    if ((rc = mskf_copy_async(ctx, cp, eql.n ? 3 : 2)) != MSKF_OK) return rc;
+    MskfCopy cp[4] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
+    int n_cp = 2;
+    if (eql.n) cp[n_cp++] = {ctx->eq_jobs.d, ctx->eq_jobs.h, sizeof(EqJob) * (size_t)eql.n};
+    if (pxl.n) cp[n_cp++] = {ctx->px_jobs.d, ctx->px_jobs.h, sizeof(PxJob) * (size_t)pxl.n};
+    if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
+    // raw images -> level 0 (fe_pixfmt.h): untimed, there is no MSKF_K_* kind for it
+    if (pxl.n) fe_launch_px_convert(ctx->px_jobs.d, pxl.n, pxl.max_w, pxl.max_h, st);
     // histogram, LUT, apply (fe_equalize.h): untimed, there is no MSKF_K_* kind for them
     if (eql.n) fe_launch_equalize(ctx->eq_jobs.d, eql.n, eql.max_units, eql.any_global, eql.max_regions, eql.splits, st);
     int ts = mskf_t_begin(ctx, MSKF_K_PYR);
@@ -694,11 +779,25 @@ extern "C" int mskf_fe_push_stereo_batch(mskf_ctx *ctx, int n, mskf_stream *cons
 extern "C" int mskf_fe_push_stereo(mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch,
                                    double time_stamp) {
     if (!s || !cam0 || !cam1) return MSKF_ERR_INVALID;
-    if (width != s->w || height != s->h || pitch < width) { mskf_set_error("image size differs from the calibration"); return MSKF_ERR_INVALID; }
-    s->time_stamp = time_stamp;
+    if (width != s->w || height != s->h || pitch < width * s->px.bpp) { mskf_set_error("image size differs from the calibration"); return MSKF_ERR_INVALID; }
     const uint8_t *a[1] = {cam0}, *b[1] = {cam1};
     mskf_stream *ss[1] = {s};
-    if (pitch != width) {
+    if (s->px.raw && pitch != width * s->px.bpp) {
+        // padded rows of a converting stream: the same, into its raw staging; everything a push can be refused for is looked at
+        // before the copies are enqueued
+        int rc;
+        if ((rc = px_check_images(s, cam0, cam1, pitch)) != MSKF_OK || (rc = mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE)) != MSKF_OK) return rc;
+        s->time_stamp = time_stamp;
+        const size_t row = (size_t)width * s->px.bpp;
+        uint8_t *stage[2] = {s->px.raw, s->px.raw + px_raw_bytes(s)};
+        MSKF_HIPCHK(hipSetDevice(s->ctx->device));
+        MSKF_HIPCHK(hipMemcpy2DAsync(stage[0], row, cam0, pitch, row, height, hipMemcpyHostToDevice, s->ctx->stream));
+        MSKF_HIPCHK(hipMemcpy2DAsync(stage[1], row, cam1, pitch, row, height, hipMemcpyHostToDevice, s->ctx->stream));
+        a[0] = stage[0]; b[0] = stage[1];
+        return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, 3);
+    }
+    s->time_stamp = time_stamp;
+    if (pitch != width * s->px.bpp) {
         // padded rows: 2D copies straight into the stream's own level-0 planes (dense, pitch = width), then the batch
         // path with "level 0 already resident" (on_device = 3): no temporary allocation, nothing to free or leak
         MSKF_HIPCHK(hipSetDevice(s->ctx->device));
@@ -706,7 +805,7 @@ extern "C" int mskf_fe_push_stereo(mskf_stream *s, const uint8_t *cam0, const ui
         MSKF_HIPCHK(hipMemcpy2DAsync(s->pyr[s->i_curr1], width, cam1, pitch, width, height, hipMemcpyHostToDevice, s->ctx->stream));
         a[0] = s->pyr[s->i_curr0]; b[0] = s->pyr[s->i_curr1];
     }
-    return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, pitch != width ? 3 : 0);
+    return mskf_fe_push_stereo_batch(s->ctx, 1, ss, a, b, pitch != width * s->px.bpp ? 3 : 0);
 }
 
 extern "C" int mskf_fe_push_stereo_device(mskf_stream *s, const uint8_t *d_cam0, const uint8_t *d_cam1, int width, int height,

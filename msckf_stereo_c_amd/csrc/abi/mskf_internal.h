@@ -7,6 +7,7 @@
 #include "../hip/fe_device.h"
 #include "../hip/fe_book.h"
 #include "../hip/fe_equalize.h"
+#include "../hip/fe_pixfmt.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -22,6 +23,7 @@ void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, 
 void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts, hipStream_t st);
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
+void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);
 }
 
 void mskf_set_error(const std::string &s);
@@ -168,6 +170,7 @@ struct mskf_ctx {
     bool cell_keys_dirty = true;      // the key array holds bytes no generation tag explains (fresh allocation): clear before use
     PinnedDev<Pyr3Job> jobs;
     PinnedDev<EqJob> eq_jobs;         // the equalising streams' images of a push (a front-end arena like jobs; empty until a stream turns it on)
+    PinnedDev<PxJob> px_jobs;         // the converting streams' images of a push (mskf_fe_set_input_format; empty until a stream turns it on)
     PinnedDev<EkfStreamDev> ekf_desc;
     PinnedDev<char> upd_in, upd_out;     // inputs / results of every stream of an update batch (one copy each way)
     PinnedDev<char> pred_arena;          // descriptors + Phi/Q or IMU steps + J of a prediction, clone removal, read-out (fenced)
@@ -231,6 +234,12 @@ struct mskf_stream {
         uint8_t *lut[2] = {nullptr, nullptr};
         int *part[2] = {nullptr, nullptr};
     } eq;
+    // ---- opt-in input pixel format (mskf_fe_set_input_format; fe_pixfmt.h)
+    struct PixFmt {
+        mskf_fe_input_format cfg{0, 0};
+        int bpp = 1;
+        uint8_t *raw = nullptr;                    // raw staging of host pushes: both cameras, w * h * bpp bytes each (null on GRAY8)
+    } px;
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

@@ -1298,6 +1298,123 @@ extern "C" void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_un
     hipLaunchKernelGGL(k_eq_apply, dim3(max_regions * splits, n_jobs), dim3(256), 0, st, jobs_dev, splits);
 }
 
+// ------------------------------------------------------------------------------------------ input pixel formats (fe_pixfmt.h)
+// Opt-in conversion of the raw images of a push (16-bit grey, interleaved colour, 8-bit Bayer) into the streams' 8-bit level
+// 0, ahead of the equalisation, k_pyr_down3 and k_detect_cells: ONE launch for both cameras of every converting stream of
+// the push (blockIdx.y = image).  A bandwidth kernel: a lane owns a 16-byte chunk of the DESTINATION plane, sixteen grey
+// pixels stored as one dword x 4, and loads their 32 / 48 / 64 source bytes as two / three / four dword x 4 (unaligned where
+// the source row starts so); a mosaic loads the sixteen bytes of the three rows around the chunk and one byte either side
+// of each.  The ends of a row, the chunks of a mosaic that touch the left or right border (the only place where a folded
+// column index is formed) and planes whose rows do not start on 16 bytes go pixel by pixel through px_pixel, the function
+// the CPU harness runs.  Consecutive lanes own consecutive chunks of a row.  The format is a field of the job: one switch
+// per workgroup, none per pixel.
+#include "fe_pixfmt.h"
+namespace {
+// The pointers of a job come out of a record in memory, so the compiler knows no address space for them and would issue flat
+// accesses; images live in global memory, and the whole-chunk path says so (global_load / global_store_dwordx4).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PX_GLOBAL __attribute__((address_space(1)))
+#else
+#define PX_GLOBAL          // (the host pass only parses the kernels)
+#endif
+typedef const PX_GLOBAL uint8_t *px_gptr;
+__device__ __forceinline__ px_gptr px_global(const uint8_t *p) { return (px_gptr)(uintptr_t)p; }
+__device__ __forceinline__ uint32_t px_byte(const uint32_t *v, int i) { return (v[i >> 2] >> (8 * (i & 3))) & 255u; }
+template <int NV>
+__device__ __forceinline__ void px_load(uint32_t *v, px_gptr p) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+        const eq_u4 t = *reinterpret_cast<const PX_GLOBAL eq_u4 *>(p + 16 * q);
+        v[4 * q] = t.v[0]; v[4 * q + 1] = t.v[1]; v[4 * q + 2] = t.v[2]; v[4 * q + 3] = t.v[3];
+    }
+}
+// the sixteen pixels x0 .. x0 + 15 of row y (all inside the row), packed
+template <int FMT>
+__device__ __forceinline__ void px_chunk16(const PxJob &j, int x0, int y, uint32_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0u;
+    constexpr int BPP = FMT == PX_GRAY16 ? 2 : (FMT == PX_RGB8 || FMT == PX_BGR8) ? 3 : 4;
+    uint32_t v[4 * BPP];
+    px_load<BPP>(v, px_global(j.src) + (size_t)y * (size_t)j.pitch + (size_t)x0 * BPP);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        int g;
+        if (FMT == PX_GRAY16) g = px_gray16((int)((v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu), j.shift);
+        else {
+            const int c0 = (int)px_byte(v, BPP * k), c1 = (int)px_byte(v, BPP * k + 1), c2 = (int)px_byte(v, BPP * k + 2);
+            g = (FMT == PX_RGB8 || FMT == PX_RGBA8) ? px_luma(c0, c1, c2) : px_luma(c2, c1, c0);
+        }
+        out[k >> 2] |= (uint32_t)g << (8 * (k & 3));
+    }
+}
+// the same for a mosaic; 1 <= x0 and x0 + 16 <= w - 1: every neighbour column is a column of the image
+__device__ __forceinline__ void px_chunk16_bayer(const PxJob &j, int x0, int y, uint32_t out[4]) {
+    out[0] = out[1] = out[2] = out[3] = 0u;
+    const px_gptr src = px_global(j.src);
+    const px_gptr rows[3] = {src + (size_t)px_reflect(y - 1, j.h) * (size_t)j.pitch + x0, src + (size_t)y * (size_t)j.pitch + x0,
+                             src + (size_t)px_reflect(y + 1, j.h) * (size_t)j.pitch + x0};
+    uint32_t v[3][4], lft[3], rgt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { px_load<1>(v[r], rows[r]); lft[r] = rows[r][-1]; rgt[r] = rows[r][16]; }
+    const int site0 = px_bayer_site(j.format, x0, y), site1 = px_bayer_site(j.format, x0 + 1, y);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        int a[3], b[3], c[3];       // columns k - 1, k, k + 1 of the three rows
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            a[r] = (int)(k == 0 ? lft[r] : px_byte(v[r], k - 1));
+            b[r] = (int)px_byte(v[r], k);
+            c[r] = (int)(k == 15 ? rgt[r] : px_byte(v[r], k + 1));
+        }
+        const int g = px_bayer_luma((k & 1) ? site1 : site0, b[1], a[1], c[1], b[0], b[2], a[0], c[0], a[2], c[2]);
+        out[k >> 2] |= (uint32_t)g << (8 * (k & 3));
+    }
+}
+template <int FMT>
+__device__ __forceinline__ void px_rows(const PxJob &j) {
+    const int w = j.w, h = j.h;
+    const int nch = (w + 15) / 16 + 1;                     // aligned chunks that can touch a row of w bytes
+    const long long n_items = (long long)h * nch;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < n_items; idx += (long long)gridDim.x * 256) {
+        const int y = (int)(idx / nch), ch = (int)(idx - (long long)y * nch);
+        const uintptr_t pb = (uintptr_t)j.dst + (size_t)y * w, pe = pb + (size_t)w;
+        const uintptr_t P = (pb & ~(uintptr_t)15) + 16 * (uintptr_t)ch;
+        if (P >= pe) continue;
+        const int lo = pb > P ? (int)(pb - P) : 0, hi = pe - P < 16 ? (int)(pe - P) : 16;
+        const int x0 = (int)((long long)P - (long long)pb);          // column of the chunk's first byte (negative before the row)
+        bool whole = lo == 0 && hi == 16;
+        if (FMT == PX_BAYER_RGGB8) whole = whole && x0 >= 1 && x0 + 16 <= w - 1;
+        if (whole) {
+            uint32_t out[4];
+            if (FMT == PX_BAYER_RGGB8) px_chunk16_bayer(j, x0, y, out); else px_chunk16<FMT>(j, x0, y, out);
+            *reinterpret_cast<PX_GLOBAL uint4 *>(P) = make_uint4(out[0], out[1], out[2], out[3]);
+        } else {
+            for (int k = lo; k < hi; ++k) *reinterpret_cast<PX_GLOBAL uint8_t *>(P + k) = (uint8_t)px_pixel(j.src, (size_t)j.pitch, w, h, j.format, j.shift, x0 + k, y);
+        }
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_px_convert(const PxJob *jobs) {
+    const PxJob j = jobs[blockIdx.y];
+    switch (j.format) {                                    // uniform over the workgroup
+        case PX_GRAY16: px_rows<PX_GRAY16>(j); break;
+        case PX_RGB8: px_rows<PX_RGB8>(j); break;
+        case PX_BGR8: px_rows<PX_BGR8>(j); break;
+        case PX_RGBA8: px_rows<PX_RGBA8>(j); break;
+        case PX_BGRA8: px_rows<PX_BGRA8>(j); break;
+        case PX_BAYER_RGGB8: case PX_BAYER_GRBG8: case PX_BAYER_GBRG8: case PX_BAYER_BGGR8: px_rows<PX_BAYER_RGGB8>(j); break;      // (the pattern is read from the job)
+        default: break;
+    }
+}
+
+// max_w, max_h: the largest image of the jobs (the grid covers its chunks; smaller images leave workgroups idle)
+extern "C" void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st) {
+    if (n_jobs <= 0 || max_w <= 0 || max_h <= 0) return;
+    const long long items = (long long)max_h * ((max_w + 15) / 16 + 1);
+    const long long wgs = (items + 255) / 256;
+    hipLaunchKernelGGL(k_px_convert, dim3((unsigned)(wgs > 65535 ? 65535 : wgs), n_jobs), dim3(256), 0, st, jobs_dev);
+}
+
 // completion mark of the spinning wait (mskf_wait_event): one thread stores a sequence number into pinned host memory
 // once everything enqueued before it on the stream (the D2H copies included) is done
 __global__ void k_mark(volatile unsigned int *flag, unsigned int seq) {

@@ -38,7 +38,9 @@ struct Point3f {
 
 struct Size2 { int width, height; int area() const { return width * height; } };
 
-// 8-bit gray image, dense row-major (cg::YImg8: rows(), cols(), data(), size().area(), empty())
+// 8-bit gray image, dense row-major (cg::YImg8: rows(), cols(), data(), size().area(), empty()).
+// With an input format other than gray8 (ImageProcessor::setInputFormat, key input_format of app_imgproc.yaml) the same class
+// carries the RAW byte raster of the image: rows = h, cols = w * bytes per pixel (16-bit pixels little-endian).
 class YImg8 {
   public:
     YImg8() : rows_(0), cols_(0) {}

@@ -1,6 +1,8 @@
 // host_capi.cpp — C entry points over the host mirror classes (cg::System, MultiRunner) for the Python
 // tests and bench.py.  This is host glue above the C-ABI of include/mskf_hip.h, not part of it.
 #include <cstring>
+#include <string>
+#include <vector>
 #include "batch_runner.h"
 #include "host_prof.h"
 
@@ -198,6 +200,25 @@ int mskfh_runner_set_equalize(void *h, int stream, const mskf_fe_equalize *cfg) 
     if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
     for (int i = 0; i < r->n_streams(); ++i)
         if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setEqualize(*cfg); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
+// ImageProcessor::setInputFormat (mskf_fe_set_input_format) of one stream, or of all (stream < 0); call before the first frame.
+// The images of mskfh_runner_step and the frames of mskfh_runner_set_sequence are then raw byte rasters in that format.
+// All or nothing: a stream that refuses (bad arguments refuse at the first stream; a pending batch or a failed allocation may refuse
+// at a later one) ends the call with its status, and the streams switched before it get their previous setting back.
+int mskfh_runner_set_input_format(void *h, int stream, const mskf_fe_input_format *cfg) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    std::vector<mskf_fe_input_format> before;
+    for (int i = 0; i < r->n_streams(); ++i) before.push_back(r->system(i).imgproc_ptr_->inputFormat());
+    for (int i = 0; i < r->n_streams(); ++i) {
+        if (stream >= 0 && i != stream) continue;
+        const int rc = r->system(i).imgproc_ptr_->setInputFormat(*cfg);
+        if (rc == MSKF_OK) continue;
+        for (int k = 0; k < i; ++k)
+            if (stream < 0 || k == stream) (void)r->system(k).imgproc_ptr_->setInputFormat(before[k]);      // (a success leaves mskf_last_error as it is)
+        return rc;
+    }
     return MSKF_OK;
 }
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame

@@ -2,6 +2,7 @@
 // Reference: msckf_core/src/image_processor.cpp (line numbers cited per function).
 #include "image_processor.h"
 #include "host_prof.h"
+#include "../hip/fe_pixfmt.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -71,6 +72,31 @@ mskf_fe_equalize equalize_from_yaml(const YAML::Node &y) {
     return c;
 }
 
+static const char *const kInputFormatNames[PX_FORMATS] = {"gray8", "gray16", "rgb8", "bgr8", "rgba8", "bgra8",
+                                                         "bayer_rggb8", "bayer_grbg8", "bayer_gbrg8", "bayer_bggr8"};
+const char *input_format_name(int format) { return format >= 0 && format < PX_FORMATS ? kInputFormatNames[format] : nullptr; }
+
+mskf_fe_input_format input_format_from_yaml(const YAML::Node &y) {
+    mskf_fe_input_format c{0, 0};
+    if (y["input_format"].IsDefined()) {
+        const std::string m = y["input_format"].as<std::string>();
+        int f = 0;
+        while (f < PX_FORMATS && m != kInputFormatNames[f]) ++f;
+        if (f == PX_FORMATS) throw YAML::Exception("yaml: input_format must be gray8, gray16, rgb8, bgr8, rgba8, bgra8 or bayer_{rggb,grbg,gbrg,bggr}8, not " + m);
+        c.format = f;
+    }
+    if (y["input_shift"].IsDefined()) c.shift = y["input_shift"].as<int>();
+    return c;
+}
+
+int ImageProcessor::setInputFormat(const mskf_fe_input_format &cfg) {
+    if (!initialized_ || !stream_) { px_cfg_ = cfg; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
+    const int rc = mskf_fe_set_input_format(stream_, &cfg);
+    if (rc != MSKF_OK) { fail("mskf_fe_set_input_format", rc); return rc; }  // refused: inputFormat() keeps reporting what the stream holds
+    px_cfg_ = cfg;
+    return rc;
+}
+
 int ImageProcessor::setEqualize(const mskf_fe_equalize &cfg) {
     if (!initialized_ || !stream_) { eq_cfg_ = cfg; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
     const int rc = mskf_fe_set_equalize(stream_, &cfg);
@@ -109,6 +135,7 @@ bool ImageProcessor::loadParameters() {
         YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");   // Q16
         cfg_ = fe_cfg_from_yaml(cfg_imgproc);
         eq_cfg_ = equalize_from_yaml(cfg_imgproc);
+        px_cfg_ = input_format_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
     processor_config.grid_col = cfg_.grid_col;
@@ -140,6 +167,8 @@ bool ImageProcessor::initialize() {
     initialized_ = true;
     // the opt-in equalisation of the pushed images; a stream that never asked for it is not touched
     if (stream_ && eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return false;
+    // ... and the opt-in input pixel format, likewise
+    if (stream_ && (px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return false;
     return true;
 }
 
@@ -167,7 +196,9 @@ void ImageProcessor::phaseBegin(double time_stamp, int width, int height) {
 
 // :139-203
 void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &cam1_img, bool is_draw) {
-    const int w = cam0_img.image.cols(), h = cam0_img.image.rows();
+    // (with an input format other than gray8 the images are raw byte rasters of w * bpp columns: cg_types.h)
+    const int bpp = std::max(px_bpp(px_cfg_.format), 1);
+    const int w = cam0_img.image.cols() / bpp, h = cam0_img.image.rows();
     if (!stream_) {
         // stand-alone use (no System): own context + stream sized from the first image
         calib_.width = w; calib_.height = h;
@@ -180,8 +211,10 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         own_stream_ = true;
         mskf_fe_set_detect_floor(stream_, cfg_.fast_threshold * 256);
         if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return;
+        if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return;
     }
-    if (w != calib_.width || h != calib_.height) {
+    // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
+    if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {
         error_ = "mskf_fe_push_stereo: image size differs from the calibration";
         std::fprintf(stderr, "ImageProcessor: mskf_fe_push_stereo failed (%d): image size differs from the calibration\n", MSKF_ERR_INVALID);
         return;

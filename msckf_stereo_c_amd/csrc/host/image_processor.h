@@ -24,6 +24,10 @@ mskf_fe_cfg fe_cfg_from_yaml(const YAML::Node &cfg_imgproc);
 // optional keys of the same file (not keys of the reference): equalize: off | hist | clahe, clahe_clip_limit, clahe_tiles_x,
 // clahe_tiles_y (mskf_fe_set_equalize; absent = off, 40.0, 8, 8).  Throws YAML::Exception on an unknown equalize value.
 mskf_fe_equalize equalize_from_yaml(const YAML::Node &cfg_imgproc);
+// ... and input_format: gray8 | gray16 | rgb8 | bgr8 | rgba8 | bgra8 | bayer_rggb8 | bayer_grbg8 | bayer_gbrg8 | bayer_bggr8 with
+// input_shift: 0 .. 8 (mskf_fe_set_input_format; absent = gray8, 0).  Throws YAML::Exception on an unknown name.
+mskf_fe_input_format input_format_from_yaml(const YAML::Node &cfg_imgproc);
+const char *input_format_name(int format);      // nullptr: no such format
 
 // twoPointRansac of image_processor.cpp:911-1135 on points already undistorted to normalised coordinates; `ransac_draws`
 // is the state of the counter-based draw generator (see ImageProcessor::twoPointRansac)
@@ -89,6 +93,10 @@ class ImageProcessor {
     // when a stand-alone processor creates its stream); afterwards, before the first frame: set at once.  Returns the setter's status.
     int setEqualize(const mskf_fe_equalize &cfg);
     const mskf_fe_equalize &equalize() const { return eq_cfg_; }
+    // opt-in pixel format of the images stereoCallback / runFrame are given (mskf_fe_set_input_format): kept and set like setEqualize.
+    // With a format other than gray8 a cg::Image carries the raw byte raster (cg_types.h).
+    int setInputFormat(const mskf_fe_input_format &cfg);
+    const mskf_fe_input_format &inputFormat() const { return px_cfg_; }
     mskf_stream *stream() const { return stream_; }
     void phaseBegin(double time_stamp, int width, int height);      // timestamps, Q2 aliasing, grid size (Q7)
     void phasePrepare1(mskf_fe_track_args &args);                   // first frame: detections; else prev features
@@ -172,6 +180,7 @@ class ImageProcessor {
     YAML::Node cfg_cam_imu_;
     bool have_yaml_ = false;
     mskf_fe_equalize eq_cfg_{0, 8, 8, 0, 40.0};
+    mskf_fe_input_format px_cfg_{0, 0};
     bool initialized_ = false;
     mskf_calib calib_;
     mskf_fe_cfg cfg_;

@@ -11,6 +11,7 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         const YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");
         mskf_fe_cfg fe = fe_cfg_from_yaml(cfg_imgproc);
         equalize_ = equalize_from_yaml(cfg_imgproc);
+        input_format_ = input_format_from_yaml(cfg_imgproc);
         const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);
@@ -38,6 +39,7 @@ void System::setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ek
     imgproc_ptr_.reset(new cg::ImageProcessor(calib, fe));
     imgproc_ptr_->attach(stream_);
     imgproc_ptr_->setEqualize(equalize_);      // (kept until initialize())
+    imgproc_ptr_->setInputFormat(input_format_);
     if (!imgproc_ptr_->initialize()) { std::cerr << "Cannot initialize Image Processor..." << std::endl; return; }
     msckfvio_ptr_.reset(new cg::MsckfVio(calib, ekf));
     msckfvio_ptr_->attach(stream_);

@@ -37,6 +37,7 @@ class System {
   private:
     void setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ekf_cfg &ekf, mskf_ctx *ctx, int device);
     YAML::Node cfg_cam_imu_;
+    mskf_fe_input_format input_format_{0, 0};          // likewise (input_format_from_yaml)
     mskf_fe_equalize equalize_{0, 8, 8, 0, 40.0};      // the YAML constructor reads it from app_imgproc.yaml (equalize_from_yaml)
     std::shared_ptr<CameraMeasurement> feature_msg_ptr_;
     cg::MsckfVioPtr msckfvio_ptr_;

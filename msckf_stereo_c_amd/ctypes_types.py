@@ -76,6 +76,35 @@ assert C.sizeof(FeEqualize) == 24
 EQUALIZE_MODES = {"off": 0, "hist": 1, "clahe": 2}
 
 
+class FeInputFormat(C.Structure):
+    """mskf_fe_input_format (include/mskf_hip.h): the pixel format of the pushed images; shift goes with gray16 only."""
+    _fields_ = [("format", C.c_int32), ("shift", C.c_int32)]
+
+
+assert C.sizeof(FeInputFormat) == 8
+# MSKF_PIX_*: a Bayer name spells the 2 x 2 tile at the image's top-left corner in reading order (not OpenCV's naming)
+INPUT_FORMATS = {"gray8": 0, "gray16": 1, "rgb8": 2, "bgr8": 3, "rgba8": 4, "bgra8": 5,
+                 "bayer_rggb8": 6, "bayer_grbg8": 7, "bayer_gbrg8": 8, "bayer_bggr8": 9}
+INPUT_FORMAT_BPP = [1, 2, 3, 3, 4, 4, 1, 1, 1, 1]
+
+
+def raw_raster(img, fmt):
+    """An image in format number fmt as the contiguous array a push takes: (h, w) uint16 for gray16 (native byte order, which the
+    device reads as little-endian), (h, w, 3 | 4) uint8 for the colour formats, (h, w) uint8 otherwise.  A wrong shape or a
+    dtype that would have to be narrowed raises."""
+    img = np.asarray(img)
+    bpp = INPUT_FORMAT_BPP[fmt]
+    if fmt == 1:
+        if img.dtype != np.uint16 or img.ndim != 2:
+            raise ValueError("gray16 takes (h, w) uint16 images, not %s %s" % (img.shape, img.dtype))
+        return np.ascontiguousarray(img.astype("<u2", copy=False))
+    if bpp > 1 and (img.ndim != 3 or img.shape[2] != bpp or img.dtype != np.uint8):
+        raise ValueError("this colour format takes (h, w, %d) uint8 images, not %s %s" % (bpp, img.shape, img.dtype))
+    if bpp == 1 and fmt != 0 and (img.ndim != 2 or img.dtype != np.uint8):
+        raise ValueError("a Bayer format takes (h, w) uint8 images, not %s %s" % (img.shape, img.dtype))
+    return np.ascontiguousarray(img, dtype=np.uint8)
+
+
 # numpy dtypes of the array records
 POINT2F = np.dtype([("x", "<f4"), ("y", "<f4")])
 CORNER = np.dtype([("x", "<f4"), ("y", "<f4"), ("score", "<i4"), ("cell", "<i4")])

@@ -8,7 +8,8 @@ import os
 import numpy as np
 
 from .capi import MskfError
-from .ctypes_types import EQUALIZE_MODES, FEATURE_MEAS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, ImuSample, TrackingInfo
+from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat,
+                           ImuSample, TrackingInfo, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -39,6 +40,7 @@ def lib():
         L.mskfh_runner_keep_trajectory_stream.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mskfh_runner_publish_covariance.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mskfh_runner_set_equalize.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeEqualize)]
+        L.mskfh_runner_set_input_format.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeInputFormat)]
         L.mskfh_num_odom_covs.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_num_odom_covs.restype = C.c_int
         L.mskfh_get_odom_covs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -103,6 +105,7 @@ class Runner:
         if not self.h:
             raise MskfError("could not create the runner (no GPU / HIP library?): see stderr")
         self._keep = []
+        self._fmt = [0] * self.n          # MSKF_PIX_* of every stream (set_input_format)
 
     def close(self):
         if self.h:
@@ -132,9 +135,10 @@ class Runner:
         self.L.mskfh_runner_imu(self.h, stream, C.byref(sample))
 
     def step(self, cam0_list, cam1_list, times):
-        """One frame for every stream from host images (numpy u8 arrays)."""
-        a = [np.ascontiguousarray(x, dtype=np.uint8) for x in cam0_list]
-        b = [np.ascontiguousarray(x, dtype=np.uint8) for x in cam1_list]
+        """One frame for every stream from host images (numpy u8 arrays; with set_input_format, arrays of the format's dtype and
+        shape: (h, w) uint16, (h, w, 3 | 4) uint8, (h, w) uint8 of the calibration's size)."""
+        a = [np.ascontiguousarray(x, dtype=np.uint8) if f == 0 else self._raw(x, f) for x, f in zip(cam0_list, self._fmt)]
+        b = [np.ascontiguousarray(x, dtype=np.uint8) if f == 0 else self._raw(x, f) for x, f in zip(cam1_list, self._fmt)]
         pa = (C.c_void_p * self.n)(*[x.ctypes.data for x in a])
         pb = (C.c_void_p * self.n)(*[x.ctypes.data for x in b])
         t = np.ascontiguousarray(times, dtype=np.float64)
@@ -205,6 +209,29 @@ class Runner:
         if rc != 0:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
+    def _raw(self, img, fmt):
+        r = raw_raster(img, fmt)
+        if r.shape[:2] != (self.calib.height, self.calib.width):
+            raise ValueError("image of %d x %d for a calibration of %d x %d" % (r.shape[1], r.shape[0], self.calib.width, self.calib.height))
+        return r
+
+    def set_input_format(self, fmt, shift=0, stream=None):
+        """Pixel format of the images of one stream or of all (mskf_fe_set_input_format): "gray8" (default), "gray16" with shift 0 .. 8
+        (g = min(v >> shift, 255)), "rgb8", "bgr8", "rgba8", "bgra8", "bayer_rggb8" / "_grbg8" / "_gbrg8" / "_bggr8" (the name spells
+        the top-left 2 x 2 tile), or the number.  The images are converted to 8-bit grey on the device inside the push.  step() then
+        takes arrays of the format's dtype and shape; a sequence (set_sequence) holds raw frames of frame_bytes = w * h * bytes per
+        pixel.  Call before the first frame."""
+        if isinstance(fmt, str) and fmt not in INPUT_FORMATS:
+            raise MskfError("unknown input format %r" % (fmt,), -1)
+        cfg = FeInputFormat(int(INPUT_FORMATS.get(fmt, fmt)), int(shift))
+        rc = self.L.mskfh_runner_set_input_format(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+        for i in range(self.n):
+            if stream is None or i == int(stream):
+                self._fmt[i] = cfg.format
 
     def publish_covariance(self, on, stream=None):
         """MsckfVio::publishCovariance of one stream or of all: every published pose gets its 6 x 6 pose and 3 x 3 velocity
