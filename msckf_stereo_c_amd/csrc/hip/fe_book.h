@@ -50,10 +50,22 @@
 #define FB_NTH ((int)blockDim.x)
 #define FB_INC(p) atomicAdd((p), 1)
 #else
+// FB_HOST_ORDER (tests only): the order in which the host runs the items of a phase.  0 or undefined: ascending; 1:
+// descending; 2: the odd indices descending, then the even ones ascending.  The items of a phase are independent and
+// nothing read from an FB_INC list depends on its slot order, so every order must leave the same bytes behind.
+#if !defined(FB_HOST_ORDER) || FB_HOST_ORDER == 0
 #define FB_FOR(i, n) for (int i = 0; i < (n); ++i)
+#elif FB_HOST_ORDER == 1
+#define FB_FOR(i, n) for (int i = (n) - 1; i >= 0; --i)
+#elif FB_HOST_ORDER == 2
+inline int fb_host_item(int k, int n) { const int odd = n / 2; return k < odd ? 2 * (odd - 1 - k) + 1 : 2 * (k - odd); }
+#define FB_FOR(i, n) for (int fb_k = 0, fb_n = (n), i = 0; fb_k < fb_n && (i = fb_host_item(fb_k, fb_n)) >= 0; ++fb_k)
+#else
+#error "FB_HOST_ORDER: 0, 1 or 2"
+#endif
 #define FB_SYNC() ((void)0)
 #define FB_NTH 256
-#define FB_INC(p) ((*(p))++)
+#define FB_INC(p) ((*(p))++)          // (a slot counter in every order: the item order alone changes who gets which slot)
 #endif
 
 #define FB_MAXK 16          // grid_min / grid_max above this: the host keeps the books (ImageProcessor falls back)

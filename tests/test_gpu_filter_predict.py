@@ -20,6 +20,7 @@ from msckf_stereo_c_amd.ctypes_types import default_ekf_cfg, default_fe_cfg
 
 import ekf_problems
 import ekf_reference as R
+from hip_runtime import Hip as _Hip
 
 pytestmark = pytest.mark.gpu
 
@@ -548,49 +549,6 @@ def test_shared_context_beside_a_pending_batch_of_its_parent(gpu_ctx, oracle):
 
 
 # ------------------------------------------------------------------------------------------------ f. staging copies
-class _Hip:
-    """hipMalloc / hipHostMalloc / hipMemcpy of the HIP runtime the library itself is linked against."""
-
-    def __init__(self):
-        capi.lib()
-        path = None
-        with open("/proc/self/maps") as f:
-            for line in f:
-                if "libamdhip64.so" in line:
-                    path = line.split()[-1]
-                    break
-        assert path, "the library's HIP runtime is not loaded"
-        L = self.L = C.CDLL(path)
-        L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        L.hipHostMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_uint]
-        L.hipFree.argtypes = [C.c_void_p]
-        L.hipHostFree.argtypes = [C.c_void_p]
-        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.owned = []
-
-    def _ok(self, rc, what):
-        assert rc == 0, "%s failed: %d" % (what, rc)
-
-    def alloc(self, n, pinned):
-        p = C.c_void_p()
-        self._ok(self.L.hipHostMalloc(C.byref(p), n, 0) if pinned else self.L.hipMalloc(C.byref(p), n), "allocation")
-        self.owned.append((p.value, pinned))
-        return p.value
-
-    def put(self, ptr, data):
-        self._ok(self.L.hipMemcpy(ptr, data.ctypes.data, data.nbytes, 4), "hipMemcpy")           # hipMemcpyDefault
-
-    def get(self, ptr, n):
-        out = np.empty(n, np.uint8)
-        self._ok(self.L.hipMemcpy(out.ctypes.data, ptr, n, 4), "hipMemcpy")
-        return out
-
-    def free(self):
-        for p, pinned in self.owned:
-            (self.L.hipHostFree if pinned else self.L.hipFree)(p)
-        self.owned = []
-
-
 CANARY = 64      # bytes after each destination that must survive the copy
 MiB = 1 << 20
 COPY_CASES = [   # segments of one launch: (bytes, direction)
