@@ -409,7 +409,7 @@ struct UpdateBatchPlan {
     bool any_pairs, any_small, any_general;
     bool any_householder, any_gram;      // among the general-route streams: compressed by k_ekf_tsqr / by the Gram factorisation
     bool any_pv_nofeat;                  // a stream without features wants its position variances
-    int max_feat, max_d, max_clones_cfg;
+    int max_feat, max_d, min_d, max_clones_cfg;   // min_d: over the streams with features (those the dense kernels work on)
     int max_frows, max_frows_small;      // block rows (4 n_obs) of the largest feature / of the largest one in the small class's list
     int max_feat_pairs, max_tri;         // over the pair-route streams
     int n_work[3];                       // entries of the three work lists of the feature kernel
@@ -499,6 +499,7 @@ static int plan_stream(const mskf_ctx *ctx, const mskf_stream *s, const mskf_ekf
     B.max_clones_cfg = std::max(B.max_clones_cfg, E.max_clones);
     B.max_feat = std::max(B.max_feat, a.n_feat);
     B.max_d = std::max(B.max_d, E.d);
+    if (a.n_feat > 0) B.min_d = B.min_d ? std::min(B.min_d, E.d) : E.d;
     return MSKF_OK;
 }
 
@@ -619,7 +620,7 @@ static int enqueue_update(mskf_ctx *ctx, int n, const UpdateBatchPlan &B) {
     // (which blocks are stacked - the 1500-row cap of :1002-1010 - is worked out by the first dense kernel of each route
     //  itself: ekf_cap.h; rounds 1-3 ran it as a launch of its own here)
     const double d3 = B.fl_upd / kUpdFlopsPerD3;     // sum of d^3 over the launch
-    const int max_d = B.max_d;
+    const int max_d = B.max_d, min_d = B.min_d ? B.min_d : B.max_d;
     // streams that stack blocks of at most four clones (the pruning update: the two clones being removed):
     // compression, gain and Y in one launch (k_ekf_small_update); the other streams leave it at once
     if (B.any_small) EKF_TIMED(MSKF_K_EKF_SMALL, B.any_general ? 0 : B.fl_qr + B.fl_upd, ekf_launch_small_update(D, n, max_d, st));
@@ -630,11 +631,11 @@ static int enqueue_update(mskf_ctx *ctx, int n, const UpdateBatchPlan &B) {
         if (B.any_gram) EKF_TIMED(MSKF_K_EKF_GEMM, B.fl_qr, ekf_launch_gemm(D, n, GM_GRAM, max_d + 1, st));
         // Householder TSQR of the streams in compression_mode 2 / 3 (a kernel without LDS of its own: ekf_linalg.hip); with no
         // Gram launch before it, it is the first dense kernel and makes the stacking decision itself
-        if (B.any_householder) EKF_TIMED(MSKF_K_EKF_TSQR, B.fl_qr, ekf_launch_tsqr(D, n, max_d, B.any_gram ? 0 : 1, st));
-        if (B.any_gram) EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 0, max_d, st));
+        if (B.any_householder) EKF_TIMED(MSKF_K_EKF_TSQR, B.fl_qr, ekf_launch_tsqr(D, n, min_d, max_d, B.any_gram ? 0 : 1, st));
+        if (B.any_gram) EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 0, min_d, max_d, st));
         EKF_TIMED(MSKF_K_EKF_GEMM, 2.0 * d3, ekf_launch_gemm(D, n, GM_T, max_d, st));
         EKF_TIMED(MSKF_K_EKF_GEMM, 2.0 * d3, ekf_launch_gemm(D, n, GM_S2, max_d, st));
-        EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 1, max_d, st));
+        EKF_TIMED(MSKF_K_EKF_CHOL, d3 / 3.0, ekf_launch_chol(D, n, 1, min_d, max_d, st));
         EKF_TIMED(MSKF_K_EKF_TRSM, 2.0 * d3, ekf_launch_trsm(D, n, max_d, st));
     }
     // P <- P - Y^T Y and delta_x = Y^T w for every stream, whichever route produced Y

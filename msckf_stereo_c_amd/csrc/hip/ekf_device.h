@@ -109,8 +109,8 @@ void ekf_launch_posvar(const EkfStreamDev *d, int n, double *out, hipStream_t st
 void ekf_launch_posvar_upd(const EkfStreamDev *d, int n, hipStream_t st);
 void ekf_launch_odom_cov(const EkfStreamDev *d, int n, double *out, hipStream_t st);      // out: 48 doubles per stream (mskf_odom_cov)
 void ekf_launch_gemm(const EkfStreamDev *d, int n, int mode, int max_mn, hipStream_t st);
-void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int max_d, hipStream_t st);
-void ekf_launch_tsqr(const EkfStreamDev *d, int n, int max_d, int do_cap, hipStream_t st);
+void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int min_d, int max_d, hipStream_t st);
+void ekf_launch_tsqr(const EkfStreamDev *d, int n, int min_d, int max_d, int do_cap, hipStream_t st);
 void ekf_launch_trsm(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
 void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
 }

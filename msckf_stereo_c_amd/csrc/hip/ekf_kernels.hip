@@ -645,6 +645,39 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
         // costs several times a ds_read (the W pass, the rank-6 update and the factorisation all wait on it).
         auto gate_steps = [&](double *Mm) __attribute__((always_inline)) {
         const double *P = S.P;
+        if constexpr (WAVE) {
+            // One wavefront, at most four observations: S_g = H_o P_cc H_o^T from the projected block itself (13 x 24 at most), in the
+            // oracle's order of operations.  Forming H_xj P H_xj^T first and reflecting it (below) costs the digits that
+            // |H_xj P H_xj^T| / |S_g| takes: 1e-8 of gamma for a feature close to the image plane of one camera, whose Jacobian
+            // entries reach thousands.  H_o is formed exactly as step 5 forms the stacked rows.
+            constexpr int NC = 6 * MAXC;
+            static_assert(17 * 18 / 2 + 16 + 2 * (4 * MAXC - 3) * NC <= (int)(sizeof(TriScratchT<2 * TRI_SMALL_CLONES>) / 8), "H_o and H_o P_cc fit the arena behind the gate matrix");
+            double *Ho = Mm + 17 * 18 / 2 + 16, *HP = Ho + (4 * MAXC - 3) * NC;
+            const int nc = 6 * M;
+            for (int e = gt; e < n * nc; e += GS) {
+                const int i = e / nc + 3, cc = e - (i - 3) * nc;
+                const int ob = cc / 6, c6 = cc - 6 * ob;
+                const double base = ((i >> 2) == ob) ? sHx[i][c6] : 0.0;
+                Ho[(i - 3) * NC + cc] = base - sCoef[cc][0] * sV[0][i] - sCoef[cc][1] * sV[1][i] - sCoef[cc][2] * sV[2][i];
+            }
+            GSYNC();
+            for (int e = gt; e < n * nc; e += GS) {
+                const int i = e / nc, v = e - i * nc;
+                const int cv = EKF_IMU_DIM + 6 * sCloneOfObs[v / 6] + v % 6;
+                double t = 0;
+                for (int u = 0; u < nc; ++u) t += Ho[i * NC + u] * P[(size_t)(EKF_IMU_DIM + 6 * sCloneOfObs[u / 6] + u % 6) * ld + cv];
+                HP[i * NC + v] = t;
+            }
+            GSYNC();
+            for (int e = gt; e < n * n; e += GS) {
+                const int i = e / n, k = e - i * n;
+                if (k > i) continue;
+                double t = 0;
+                for (int v = 0; v < nc; ++v) t += HP[i * NC + v] * Ho[k * NC + v];
+                Mm[pk(i + 3, k + 3)] = t;
+            }
+            GSYNC();
+        } else {
         for (int pr = gt; pr < M * M; pr += GS) {
             const int a = pr / M, b = pr - a * M;
             if (b > a) continue;
@@ -729,6 +762,7 @@ __global__ __launch_bounds__(TPB, 2) void k_ekf_feature_blocks(const EkfStreamDe
                 }
             }
             GSYNC();
+        }
         }
         // S = Mm[3:,3:] + sigma^2 I ; in-place right-looking Cholesky (lower) on the sub-matrix view.  The residual
         // r_o rides along as an extra row (sW): after step k it holds y_k = (L^-1 r_o)_k, so gamma = y . y

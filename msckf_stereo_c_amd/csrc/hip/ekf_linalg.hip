@@ -410,6 +410,9 @@ __device__ __forceinline__ void ekf_compress_exit(const EkfStreamDev &S, bool gr
 // (this is a factorisation, not one of the decision-bearing sequences of DESIGN section 3); same skipping rule for annihilated
 // columns as tsqr_wide.
 #define TQ_THREADS 512
+// Which instantiation of k_ekf_tsqr compresses a stream is a property of the stream's own dimension, whatever else is in the
+// batch: 0 = <32, 2, 2> (up to 2 * TQ_THREADS / 4 columns incl. the residual), 1 = <16, 4, 2>.
+__host__ __device__ inline int tsqr_class(int d) { return d - EKF_IMU_DIM + 1 <= 2 * (TQ_THREADS / 4) ? 0 : 1; }
 // sum over the four DPP rows of a wavefront (lanes c, c + 16, c + 32, c + 48): every one of the four gets the same bits
 // (v_permlane16_swap / v_permlane32_swap of gfx950 - a VALU operation each, where a ds_bpermute pays the LDS crossbar's latency
 //  twice per sum on the dependent chain of every reflector step: swapping a value with a copy of itself leaves row pairs (halves)
@@ -614,9 +617,10 @@ __device__ __forceinline__ void tsqr_wave(int n1, int n_blocks, int first, int s
 // do_cap: this is the first dense kernel of the route (no stream of the batch needs a Gram matrix, so k_ekf_gemm<GRAM> was not
 // launched): the stacking decision (ekf_cap.h) is worked out and written down here.
 template <int RL, int NC, int WPE>
-__global__ __launch_bounds__(TQ_THREADS, WPE) void k_ekf_tsqr(const EkfStreamDev *streams, int do_cap) {
+__global__ __launch_bounds__(TQ_THREADS, WPE) void k_ekf_tsqr(const EkfStreamDev *streams, int do_cap, int cls) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
+    if (cls >= 0 && tsqr_class(S.d) != cls) return;               // the other instantiation's stream (ekf_launch_tsqr)
     if (!ekf_mode_householder(S.qr_mode)) return;                 // the Gram route's streams: k_ekf_chol_lds / k_ekf_chol (which = 0)
     if (do_cap) { (void)ekf_cap_local<TQ_THREADS>(S, true); __syncthreads(); }
     __shared__ int s_w[TQ_THREADS / 64];
@@ -644,9 +648,17 @@ __global__ __launch_bounds__(TQ_THREADS, WPE) void k_ekf_tsqr(const EkfStreamDev
 // A row is read up to 15 entries right of its diagonal as filler: those are the mirrored upper triangle and, for the
 // last rows, columns [n, n+16) of the ld-wide row (ld - n >= 21: the IMU columns are not part of the compact block).
 #define CHOLG_THREADS 512
-__global__ __launch_bounds__(CHOLG_THREADS) void k_ekf_chol(const EkfStreamDev *streams, int which, int pan_rs) {
+#define CHOL_LDS_MAX_ROWS 181     // k_ekf_chol_lds: active rows incl. the extra Q^T r row
+#define CHOL_PAN_RS 192           // k_ekf_chol_lds: row stride of the k-major panel (rows padded to a multiple of 16)
+// Which of the two factorisation kernels handles a stream is a property of the stream's own dimension, whatever else is in
+// the batch: 0 = k_ekf_chol_lds (the factor fits LDS), 1 = k_ekf_chol (global memory).
+__host__ __device__ inline int chol_class(int d) { return d - EKF_IMU_DIM + 1 <= CHOL_LDS_MAX_ROWS ? 0 : 1; }
+// dynamic LDS (doubles) of a k_ekf_chol_lds launch for a stream of dimension d alone: the packed factor and the panel
+__host__ __device__ inline int chol_lds_doubles(int d) { const int nt = d - EKF_IMU_DIM + 1; return nt * (nt + 1) / 2 + CHOL_PAN_RS * LNB; }
+__global__ __launch_bounds__(CHOLG_THREADS) void k_ekf_chol(const EkfStreamDev *streams, int which, int pan_rs, int cls) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
+    if (cls >= 0 && chol_class(S.d) != cls) return;               // k_ekf_chol_lds's stream (ekf_launch_chol)
     int entry = 0;
     __shared__ int s_w[CHOLG_THREADS / 64];
     if (which == 0) {
@@ -723,16 +735,16 @@ __global__ __launch_bounds__(CHOLG_THREADS) void k_ekf_chol(const EkfStreamDev *
 //      (sPanT[c][row]) for the MFMA operands;
 //   3. the trailing update A22 -= X X^T runs on v_mfma_f64_16x16x4_f64, one 16x16 tile of the lower triangle at
 //      a time per wave (4 MFMAs per tile), read-modify-write on the packed matrix.
-#define CHOL_LDS_MAX_ROWS 181     // active rows incl. the extra Q^T r row
 #define CHOL_THREADS 512          // 8 waves: 256 VGPRs per lane, the unrolled 16-column eliminations stay in registers
 #define CHOL_WAVES (CHOL_THREADS / 64)
-#define CHOL_PAN_RS 192           // row stride of the k-major panel (rows padded to a multiple of 16)
 
 __device__ __forceinline__ int pk(int i, int j) { return i * (i + 1) / 2 + j; }
 
-__global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDev *streams, int which, int lds_doubles) {
+__global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDev *streams, int which, int cls) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
+    if (cls >= 0 && chol_class(S.d) != cls) return;               // k_ekf_chol's stream (ekf_launch_chol)
+    const int lds_doubles = chol_lds_doubles(S.d);                // what a launch for this stream alone allocates (the batch's is no smaller)
     int entry = 0;
     __shared__ int s_w[CHOL_WAVES];
     if (which == 0) {
@@ -1168,24 +1180,30 @@ void ekf_launch_gemm(const EkfStreamDev *d, int n, int mode, int max_mn, hipStre
     }
 }
 // Householder compression of the streams in compression_mode 2 / 3 (the others leave at once)
-void ekf_launch_tsqr(const EkfStreamDev *d, int n, int max_d, int do_cap, hipStream_t st) {
-    const int n1 = max_d - EKF_IMU_DIM + 1;
+void ekf_launch_tsqr(const EkfStreamDev *d, int n, int min_d, int max_d, int do_cap, hipStream_t st) {
     // (a 64-row block at 128 VGPRs - four waves per SIMD left for others - measured 1270 us alone against 810 and the same bench rate)
-    if (n1 <= 2 * (TQ_THREADS / 4)) hipLaunchKernelGGL((k_ekf_tsqr<32, 2, 2>), dim3(1, n), dim3(TQ_THREADS), 0, st, d, do_cap);
-    else hipLaunchKernelGGL((k_ekf_tsqr<16, 4, 2>), dim3(1, n), dim3(TQ_THREADS), 0, st, d, do_cap);
+    // A batch whose streams fall into both classes gets both launches, each leaving the other's streams alone: a stream's
+    // arithmetic does not depend on its neighbours' windows.
+    const int lo = tsqr_class(min_d), hi = tsqr_class(max_d), cls = lo == hi ? -1 : 0;
+    if (lo == 0) hipLaunchKernelGGL((k_ekf_tsqr<32, 2, 2>), dim3(1, n), dim3(TQ_THREADS), 0, st, d, do_cap, cls);
+    if (hi == 1) hipLaunchKernelGGL((k_ekf_tsqr<16, 4, 2>), dim3(1, n), dim3(TQ_THREADS), 0, st, d, do_cap, lo == hi ? -1 : 1);
 }
-void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int max_d, hipStream_t st) {
-    const int nt = max_d - EKF_IMU_DIM + 1;
-    if (nt <= CHOL_LDS_MAX_ROWS) {
+void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int min_d, int max_d, hipStream_t st) {
+    // A batch whose streams fall into both classes gets both launches, each leaving the other's streams alone.
+    const int lo = chol_class(min_d), hi = chol_class(max_d);
+    if (lo == 0) {
         static std::once_flag attr_once;
-    std::call_once(attr_once, []() { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
+        std::call_once(attr_once, []() { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_ekf_chol_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)(((size_t)CHOL_LDS_MAX_ROWS * (CHOL_LDS_MAX_ROWS + 1) / 2 + (size_t)CHOL_PAN_RS * LNB) * sizeof(double))); });
-        const size_t lds = ((size_t)nt * (nt + 1) / 2 + (size_t)CHOL_PAN_RS * LNB) * sizeof(double);
-        hipLaunchKernelGGL(k_ekf_chol_lds, dim3(1, n), dim3(CHOL_THREADS), lds, st, d, which, (int)(lds / sizeof(double)));
-        return;
+        // (sized for the largest stream of the class in the batch: at most the class limit when the batch is mixed)
+        const size_t lds = (size_t)chol_lds_doubles(hi == 0 ? max_d : EKF_IMU_DIM + CHOL_LDS_MAX_ROWS - 1) * sizeof(double);
+        hipLaunchKernelGGL(k_ekf_chol_lds, dim3(1, n), dim3(CHOL_THREADS), lds, st, d, which, lo == hi ? -1 : 0);
     }
-    const int pan_rs = (nt + 15) / 16 * 16;
-    hipLaunchKernelGGL(k_ekf_chol, dim3(1, n), dim3(CHOLG_THREADS), (size_t)LNB * pan_rs * sizeof(double), st, d, which, pan_rs);
+    if (hi == 1) {
+        const int nt = max_d - EKF_IMU_DIM + 1;
+        const int pan_rs = (nt + 15) / 16 * 16;
+        hipLaunchKernelGGL(k_ekf_chol, dim3(1, n), dim3(CHOLG_THREADS), (size_t)LNB * pan_rs * sizeof(double), st, d, which, pan_rs, lo == hi ? -1 : 1);
+    }
 }
 void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st) {
     const size_t lds = ((size_t)SU_MAX_NA * (max_d + 1) + (SU_MAX_NA + 1) * (SU_MAX_NA + 1) + SU_MAX_NA * SU_MAX_NA + SU_CH * (SU_MAX_NA + 1)) * sizeof(double);
