@@ -42,7 +42,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  pos_var_out, mskf_fe_frame_batch_* (whole front-end frames on the device), mskf_ctx_timing_gate, mskf_ctx_set_wait_mode;
                                  4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter);
                                  added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end;
-                                 mskf_fe_set_equalize, mskf_fe_get_equalize; mskf_fe_set_input_format, mskf_fe_get_input_format */
+                                 mskf_fe_set_equalize, mskf_fe_get_equalize; mskf_fe_set_input_format, mskf_fe_get_input_format;
+                                 mskf_ekf_update_direct, _batch, _batch_begin, _batch_end (with their own mskf_ekf_direct_args) */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -68,7 +69,8 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
  * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
- * stability and counts no launch: the augmentation runs inside k_ekf_propagate (MSKF_K_EKF_PROPAGATE), also for mskf_ekf_augment. */
+ * stability and counts no augmentation: that runs inside k_ekf_propagate (MSKF_K_EKF_PROPAGATE), also for mskf_ekf_augment.  The slot
+ * counts the launches of k_ekf_direct_update instead (mskf_ekf_update_direct*; units: streams with rows), which nothing but those calls makes. */
 enum {
     MSKF_K_PYR = 0, MSKF_K_DETECT, MSKF_K_LK, MSKF_K_EKF_PROPAGATE, MSKF_K_EKF_AUGMENT, MSKF_K_EKF_FEATURES,
     MSKF_K_EKF_TSQR /* k_ekf_tsqr; rounds 1-3: the stacking-decision kernel, which no longer exists */, MSKF_K_EKF_GEMM, MSKF_K_EKF_CHOL, MSKF_K_EKF_TRSM, MSKF_K_EKF_SMALL, MSKF_K_EKF_REMOVE, MSKF_K_PT_GEOM, MSKF_K_FE_BOOK, MSKF_K_COUNT
@@ -359,6 +361,38 @@ int mskf_ekf_update_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, msk
 /* begin / end halves as for mskf_fe_track_batch; `streams` and `args` must stay valid until _end */
 int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_update_args *args);
 int mskf_ekf_update_batch_end(mskf_ctx *ctx);
+/* ---- opt-in direct measurement update: a few caller-supplied rows on the IMU block
+ * A Kalman update of the resident covariance with a measurement that is not a feature track: r = H x~ + noise of covariance R,
+ * H acting on the 21 IMU error states only (0..2 attitude, 3..5 gyro bias, 6..8 velocity, 9..11 acc bias, 12..14 position,
+ * 15..20 extrinsics), 1 .. 6 rows.  A world-frame velocity or position fix is a selector H on columns 6..8 / 12..14 with
+ * r = z - state; a zero-velocity update is the former with z = 0.  The arithmetic is measurementUpdate's (msckf_vio.cpp:831-904)
+ * with R in place of observation_noise * I, every sum in a fixed order: S = H P H^T + R is factored by Cholesky,
+ * gamma = r^T S^-1 r, and when gate > 0 the update is applied only if gamma <= gate (mskf_chi2_table.h has the values);
+ * delta_x = K r is returned for the caller to apply to its state (all 21 + 6 n_clones entries: the clones are corrected through
+ * their correlation), P <- sym((I - K H) P) in place, one launch for the batch and one more read and write of P.
+ * status: 1 applied; 0 gated out; 2 S not positive definite (an indefinite P).  Unless 1, P is untouched and delta_x is zero;
+ * gamma is 0 with status 2.  A stream with m = 0 takes no part: status 0, delta_x zero, gamma 0, pos_var_out -1.
+ * A direct update is a kind of update batch: it stages through the update's arenas and shares its pending slot, so while
+ * either kind is pending the _begin and the _end of the other refuse (MSKF_ERR_INVALID, mskf_last_error names the pending
+ * call); it also refuses while a read-out is pending.  MSKF_ERR_INVALID, with nothing grown, enqueued or written, for m outside
+ * 0..6, null H / r / R / delta_x with m > 0, a non-finite value in H, r or R, a NaN gate, R not exactly symmetric or with
+ * a diagonal entry <= 0, and a stream that appears twice with rows in one batch (the update is in place). */
+typedef struct mskf_ekf_direct_args {
+    int32_t m;                      /* rows, 0 .. 6 (0: the stream takes no part) */
+    int32_t status;                 /* out */
+    const double *H;                /* m x 21, row-major */
+    const double *r;                /* m: residual, measurement minus prediction */
+    const double *R;                /* m x m, row-major, symmetric, positive diagonal */
+    double gate;                    /* > 0: Mahalanobis gate; <= 0: none */
+    double *delta_x;                /* out: 21 + 6 n_clones */
+    double gamma;                   /* out */
+    double *pos_var_out;            /* out, optional (may be NULL), 3 doubles: P(12,12), P(13,13), P(14,14) after the call */
+} mskf_ekf_direct_args;
+int mskf_ekf_update_direct(mskf_stream *s, mskf_ekf_direct_args *args);                          /* batch of one; synchronises */
+int mskf_ekf_update_direct_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_direct_args *args);
+/* `streams` and `args` (and what args point to) must stay valid until _end */
+int mskf_ekf_update_direct_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_direct_args *args);
+int mskf_ekf_update_direct_batch_end(mskf_ctx *ctx);
 int mskf_ekf_remove_clone(mskf_stream *s, int clone_index);
 /* Remove up to two clones per stream in one launch: idx[2*i], idx[2*i+1] are clone indices in the CURRENT
  * state order (distinct; -1 = none).  Equivalent to mskf_ekf_remove_clone calls (msckf_vio.cpp:1161-1181). */

@@ -23,6 +23,7 @@ HIP_SRCS = [
     "hip/fe_kernels.hip",
     "hip/ekf_kernels.hip",
     "hip/ekf_linalg.hip",
+    "hip/ekf_direct.hip",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_ekf.cpp",
 ]

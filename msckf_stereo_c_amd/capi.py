@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import (CORNER, EQUALIZE_MODES, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
+from .ctypes_types import (CORNER, EQUALIZE_MODES, EkfDirectArgs, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
                            FeInputFormat, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +63,7 @@ EXPORTS = [
     "mskf_stream_rebind", "mskf_ctx_record_point", "mskf_ctx_wait_point", "mskf_point_destroy", "mskf_ekf_set_compression_mode",
     "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
+    "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
 ]
 
 
@@ -158,6 +159,7 @@ class Context:
         self.streams = []
         self._trk_pending = None
         self._frame_pending = None
+        self._direct_pending = None
 
     def close(self):
         if self.h:
@@ -319,6 +321,32 @@ class Context:
         self.L.mskf_ekf_get_odom_cov_batch_end.argtypes = [C.c_void_p]
         _chk(self.L.mskf_ekf_get_odom_cov_batch_end(self.h))
         self._oc_pending = None
+
+    def ekf_update_direct_batch(self, streams, problems):
+        """One mskf_ekf_update_direct_batch over several streams of this context; problems[i] = kwargs of Stream.ekf_update_direct,
+        or None for a stream that takes no part (m = 0).  Returns the result dicts."""
+        out = self.ekf_update_direct_batch_begin(streams, problems)
+        self.ekf_update_direct_batch_end()
+        return out
+
+    def ekf_update_direct_batch_begin(self, streams, problems):
+        """mskf_ekf_update_direct_batch_begin: enqueue the batch; the returned result dicts are filled by ekf_update_direct_batch_end."""
+        n = len(streams)
+        built = [Stream._direct_args(s, **(pr or {})) for s, pr in zip(streams, problems)]
+        args = (EkfDirectArgs * n)(*[b[0] for b in built])
+        hs = _handles(streams)
+        self.L.mskf_ekf_update_direct_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(EkfDirectArgs)]
+        _chk(self.L.mskf_ekf_update_direct_batch_begin(self.h, n, hs, args))
+        self._direct_pending = (built, args, hs)          # must stay alive until _end
+        return [b[2] for b in built]
+
+    def ekf_update_direct_batch_end(self):
+        self.L.mskf_ekf_update_direct_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_ekf_update_direct_batch_end(self.h))
+        pending, self._direct_pending = self._direct_pending, None
+        if pending is not None:
+            for a, b in zip(pending[1], pending[0]):
+                b[2]["gamma"], b[2]["status"] = float(a.gamma), int(a.status)
 
     def hip_stream(self):
         return self.L.mskf_ctx_hip_stream(self.h)
@@ -517,6 +545,36 @@ class Stream:
         self.L.mskf_ekf_get_odom_cov.argtypes = [C.c_void_p, C.c_void_p]
         _chk(self.L.mskf_ekf_get_odom_cov(self.h, _p(out)))
         return out[0]
+
+    @staticmethod
+    def _direct_args(stream, H=None, r=None, R=None, gate=0.0, pos_var=True):
+        """(mskf_ekf_direct_args, buffers it points into, result dict the call fills) for one stream; no H: m = 0."""
+        d = stream.ekf_dim()
+        dx = np.zeros(d)
+        pv = np.full(3, np.nan)
+        a = EkfDirectArgs()
+        a.status, a.gamma = -1, float("nan")
+        keep = [dx, pv]
+        if H is not None:
+            r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+            m = len(r)
+            H = np.ascontiguousarray(H, dtype=np.float64).reshape(m, 21)
+            R = np.ascontiguousarray(R, dtype=np.float64).reshape(m, m)
+            a.m, a.H, a.r, a.R = m, H.ctypes.data, r.ctypes.data, R.ctypes.data
+            keep += [H, r, R]
+        a.gate = float(gate)
+        a.delta_x = dx.ctypes.data
+        a.pos_var_out = pv.ctypes.data if pos_var else None
+        return a, keep, dict(delta_x=dx, pos_var=pv, gamma=float("nan"), status=-1)
+
+    def ekf_update_direct(self, H, r, R, gate=0.0, pos_var=True):
+        """mskf_ekf_update_direct: H (m x 21, m <= 6) on the IMU block, residual r, covariance R, gate (> 0: applied only when
+        gamma <= gate).  Returns dict(delta_x, gamma, status (1 applied, 0 gated out, 2 S not positive definite), pos_var)."""
+        a, _keep, res = self._direct_args(self, H, r, R, gate, pos_var)
+        self.L.mskf_ekf_update_direct.argtypes = [C.c_void_p, C.POINTER(EkfDirectArgs)]
+        _chk(self.L.mskf_ekf_update_direct(self.h, C.byref(a)))
+        res["gamma"], res["status"] = float(a.gamma), int(a.status)
+        return res
 
     @staticmethod
     def _update_args(gravity, clones, positions, obs_start, obs_clone, obs_z, dof_offset, apply_row_cap, needs_init=None, init_ranges=None):

@@ -2,6 +2,7 @@
 // the host passes small per-frame descriptors (Phi/Q sequence, J, clone states, observation lists).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include "../../../include/mskf_chi2_table.h"
 #include "mskf_internal.h"
@@ -662,7 +663,7 @@ extern "C" int mskf_ekf_update_batch_begin(mskf_ctx *ctx, int n, mskf_stream *co
     DrainOnError drain{ctx->stream, true};
     if ((rc = grow_stacks(n, streams, U.plan.data(), ctx->stream)) != MSKF_OK) return rc;
     pack_update(ctx, n, streams, args, U.plan.data(), B);
-    U.launched = B.max_feat > 0; U.n = n; U.streams = streams; U.args = args;
+    U.launched = B.max_feat > 0; U.n = n; U.streams = streams; U.args = args; U.direct = false;
     if (!U.launched) U.active = true;            // nothing launched, no mark: _end only fills the outputs
     else if ((rc = enqueue_update(ctx, n, B)) != MSKF_OK || (rc = mskf_batch_arm(ctx, U)) != MSKF_OK) return rc;
     drain.armed = false;
@@ -676,6 +677,7 @@ extern "C" int mskf_ekf_update_batch_end(mskf_ctx *ctx) {
     if (!ctx) return MSKF_ERR_INVALID;
     mskf_ctx::PendingUpdate &U = ctx->pend_upd;
     if (!U.active) return MSKF_OK;
+    if (U.direct) return mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);        // the other kind is pending: names it and its _end
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     if (!U.launched) U.active = false;
     else {
@@ -714,6 +716,139 @@ extern "C" int mskf_ekf_update_batch_end(mskf_ctx *ctx) {
     }
     if (ctx->t_gate) ctx->host_s[1] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h1).count();
     return MSKF_OK;
+}
+
+// ------------------------------------------------------------------------------------------ direct measurement update
+// mskf_ekf_update_direct_batch_begin: plan (validate everything, lay out the arenas; no HIP call), grow, stage, enqueue:
+// one copy in (descriptors + H, r, R of every stream, all in upd_in), k_ekf_direct_update, one copy out.
+static bool finite_all(const double *v, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
+
+static int plan_direct(const mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_ekf_direct_args *args, std::vector<size_t> &in_off,
+                       std::vector<size_t> &out_off, size_t &in_bytes, size_t &out_bytes, int &n_rows) {
+    in_bytes = align_up(sizeof(EkfDirectDev) * (size_t)n, 64);
+    out_bytes = 0; n_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        const mskf_ekf_direct_args &a = args[i];
+        if (!s || s->ctx_ekf != ctx) return MSKF_ERR_INVALID;
+        const int m = a.m;
+        if (m < 0 || m > MSKF_DIRECT_MAX_ROWS) { mskf_set_error("mskf_ekf_direct_args.m must be in [0, " + std::to_string(MSKF_DIRECT_MAX_ROWS) + "]"); return MSKF_ERR_INVALID; }
+        // (the update is in place: two entries with rows for one stream would be two workgroups writing one P)
+        if (m > 0) for (int k = 0; k < i; ++k) if (streams[k] == s && args[k].m > 0) { mskf_set_error("a stream appears twice with rows in one direct update batch"); return MSKF_ERR_INVALID; }
+        if (m > 0) {
+            if (!a.H || !a.r || !a.R || !a.delta_x) { mskf_set_error("a direct update with rows needs H, r, R and delta_x"); return MSKF_ERR_INVALID; }
+            if (!finite_all(a.H, m * EKF_IMU_DIM) || !finite_all(a.r, m) || !finite_all(a.R, m * m) || std::isnan(a.gate)) {
+                mskf_set_error("a direct update takes finite H, r and R (and a gate that is a number)");
+                return MSKF_ERR_INVALID;
+            }
+            for (int p = 0; p < m; ++p) {
+                if (!(a.R[p * m + p] > 0.0)) { mskf_set_error("R of a direct update needs a positive diagonal"); return MSKF_ERR_INVALID; }
+                for (int q = 0; q < p; ++q)
+                    if (a.R[p * m + q] != a.R[q * m + p]) { mskf_set_error("R of a direct update must be symmetric"); return MSKF_ERR_INVALID; }
+            }
+        }
+        in_off[i] = in_bytes;
+        in_bytes = align_up(in_bytes + sizeof(double) * (size_t)(m * EKF_IMU_DIM + m + m * m), 64);
+        out_off[i] = out_bytes;           // delta_x (ld), gamma, 3 position variances, status
+        out_bytes = align_up(out_bytes + sizeof(double) * (size_t)(s->ekf_state.ld + 4) + sizeof(int), 64);
+        n_rows += m > 0;
+    }
+    return MSKF_OK;
+}
+
+extern "C" int mskf_ekf_update_direct_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_direct_args *args) {
+    if (!ctx || n <= 0 || !streams || !args) return MSKF_ERR_INVALID;
+    int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);
+    if (rc != MSKF_OK || (rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED)) != MSKF_OK) return rc;
+    mskf_ctx::PendingUpdate &U = ctx->pend_upd;
+    std::vector<size_t> in_off((size_t)n), out_off((size_t)n);
+    size_t in_bytes, out_bytes;
+    int n_rows;
+    if ((rc = plan_direct(ctx, n, streams, args, in_off, out_off, in_bytes, out_bytes, n_rows)) != MSKF_OK) return rc;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ctx->upd_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->upd_out.ensure(out_bytes)) != MSKF_OK) return rc;
+    // the batch is accepted
+    char *hin = ctx->upd_in.h, *din = ctx->upd_in.d, *dout = ctx->upd_out.d;
+    EkfDirectDev *D = (EkfDirectDev *)hin;
+    for (int i = 0; i < n; ++i) {
+        const mskf_ekf_direct_args &a = args[i];
+        const EkfStreamState &E = streams[i]->ekf_state;
+        const int m = a.m;
+        double *in = (double *)(hin + in_off[i]);
+        const double *din_i = (const double *)(din + in_off[i]);
+        double *o = (double *)(dout + out_off[i]);
+        if (m > 0) {
+            std::memcpy(in, a.H, sizeof(double) * (size_t)(m * EKF_IMU_DIM));
+            std::memcpy(in + m * EKF_IMU_DIM, a.r, sizeof(double) * (size_t)m);
+            std::memcpy(in + m * EKF_IMU_DIM + m, a.R, sizeof(double) * (size_t)(m * m));
+        }
+        EkfDirectDev &d = D[i];
+        d.P = E.P; d.d = E.d; d.ld = E.ld; d.m = m;
+        d.H = din_i; d.r = din_i + m * EKF_IMU_DIM; d.R = din_i + m * EKF_IMU_DIM + m;
+        d.gate = a.gate;
+        d.delta_x = o; d.gamma = o + E.ld; d.pos_var_out = a.pos_var_out ? o + E.ld + 1 : nullptr;
+        d.status = (int *)(o + E.ld + 4);
+    }
+    // the slot's fields describe a direct batch only once it is pending: `direct` is set together with `active`
+    U.launched = n_rows > 0; U.n = n; U.streams = streams; U.args = nullptr; U.dargs = args;
+    U.d_out.swap(out_off);
+    if (!U.launched) { U.direct = true; U.active = true; return MSKF_OK; }      // nothing launched, no mark: _end only fills the outputs
+    DrainOnError drain{ctx->stream, true};
+    { const MskfCopy cp = {din, hin, in_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
+    {
+        const int ts = mskf_t_begin(ctx, MSKF_K_EKF_AUGMENT);     // (the slot the direct update is accounted in: mskf_hip.h)
+        ekf_launch_direct_update((const EkfDirectDev *)din, n, ctx->stream);
+        mskf_t_end(ctx, ts, n_rows);
+    }
+    MSKF_HIPCHK(hipGetLastError());
+    { const MskfCopy cp = {ctx->upd_out.h, dout, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
+    if ((rc = mskf_batch_arm(ctx, U)) != MSKF_OK) return rc;
+    U.direct = true;
+    drain.armed = false;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_ekf_update_direct_batch_end(mskf_ctx *ctx) {
+    if (!ctx) return MSKF_ERR_INVALID;
+    mskf_ctx::PendingUpdate &U = ctx->pend_upd;
+    if (!U.active) return MSKF_OK;
+    if (!U.direct) return mskf_refuse_if_owned(ctx, MSKF_ARENAS_UPDATE);       // the other kind is pending: names it and its _end
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    if (!U.launched) U.active = false;
+    else {
+        const int rc = mskf_batch_finish(ctx, U);
+        if (rc != MSKF_OK) return rc;
+        mskf_t_collect(ctx);
+    }
+    const char *hout = ctx->upd_out.h;
+    for (int i = 0; i < U.n; ++i) {
+        mskf_ekf_direct_args &a = U.dargs[i];
+        const EkfStreamState &E = U.streams[i]->ekf_state;
+        if (a.m <= 0) {
+            a.status = 0; a.gamma = 0.0;
+            if (a.delta_x) std::memset(a.delta_x, 0, sizeof(double) * (size_t)E.d);
+            if (a.pos_var_out) a.pos_var_out[0] = a.pos_var_out[1] = a.pos_var_out[2] = -1.0;      // nothing ran for it: no value
+            continue;
+        }
+        const double *o = (const double *)(hout + U.d_out[i]);
+        std::memcpy(a.delta_x, o, sizeof(double) * (size_t)E.d);
+        a.gamma = o[E.ld];
+        if (a.pos_var_out) std::memcpy(a.pos_var_out, o + E.ld + 1, sizeof(double) * 3);
+        a.status = *(const int *)(o + E.ld + 4);
+    }
+    U.direct = false;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_ekf_update_direct_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_ekf_direct_args *args) {
+    const int rc = mskf_ekf_update_direct_batch_begin(ctx, n, streams, args);
+    return rc != MSKF_OK ? rc : mskf_ekf_update_direct_batch_end(ctx);
+}
+
+extern "C" int mskf_ekf_update_direct(mskf_stream *s, mskf_ekf_direct_args *args) {
+    if (!s || !args) return MSKF_ERR_INVALID;
+    mskf_stream *ss[1] = {s};
+    return mskf_ekf_update_direct_batch(s->ctx_ekf, 1, ss, args);
 }
 
 // Test / diagnostic access to the work buffers of the last update of a stream (not used by the product path):

@@ -188,7 +188,9 @@ int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which) {
             else if (c->pend_frame.active) owner = "a device frame of this context is still pending (call mskf_fe_frame_batch_end)";
             break;
         case MSKF_ARENAS_UPDATE:
-            if (c->pend_upd.active) owner = "an update batch of this context is still pending (call mskf_ekf_update_batch_end)";
+            if (c->pend_upd.active)
+                owner = c->pend_upd.direct ? "a direct update batch of this context is still pending (call mskf_ekf_update_direct_batch_end)"
+                                           : "an update batch of this context is still pending (call mskf_ekf_update_batch_end)";
             break;
         case MSKF_ARENAS_PRED:
             if (c->pend_ro.active)

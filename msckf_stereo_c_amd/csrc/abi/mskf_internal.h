@@ -102,7 +102,7 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 
 // Which pending batch owns which arenas of the context:
 //   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
-//   a pending update owns ekf_desc, upd_in and upd_out;
+//   a pending update (a feature update or a direct update: one slot for both kinds) owns ekf_desc, upd_in and upd_out;
 //   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
 //   descriptors from and writes results into the host side).
 // Every _begin and every batch call that writes an arena refuses while the owner is pending: MSKF_ERR_INVALID, and the
@@ -183,6 +183,9 @@ struct mskf_ctx {
     struct PendingUpdate : PendingBatch {
         bool launched = false; int n = 0; mskf_stream *const *streams = nullptr; mskf_ekf_update_args *args = nullptr;
         std::vector<EkfUpdatePlan> plan;       // per stream, written by _begin's planning step; storage reused from call to call
+        // the same slot holds a pending DIRECT update (mskf_ekf_update_direct_batch_begin): the two kinds share the arenas
+        bool direct = false; struct mskf_ekf_direct_args *dargs = nullptr;
+        std::vector<size_t> d_out;             // direct: byte offset of each stream's results in upd_out
     } pend_upd;
     // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
     struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;

@@ -14,6 +14,7 @@
 #define FEAT_SMALL_CLONES 16      // one-wavefront class: max(observations, triangulation clones) at most; above it the big class
 #define TRI_SMALL_CLONES 32       // the wave-per-feature variant triangulates over at most this many clones
 #define SU_MAX_NA 24              // k_ekf_small_update: active columns at most (four clones)
+#define MSKF_DIRECT_MAX_ROWS 6    // k_ekf_direct_update: rows of a caller-supplied measurement at most (mskf_ekf_direct_args.m)
 static_assert(FEAT_WAVE_CLONES <= FEAT_SMALL_CLONES && FEAT_SMALL_CLONES <= TRI_SMALL_CLONES && TRI_SMALL_CLONES <= MAX_CLONES_DEV, "size classes nest");
 static_assert(MAX_CLONES_DEV <= 64, "clone sets are 64-bit masks (EkfFeatDev::colmask, rowmask)");
 
@@ -98,7 +99,22 @@ struct EkfStreamDev {
     double *P_dst;            // destination of the out-of-place clone removal
 };
 
-// ---- launchers (ekf_kernels.hip, ekf_linalg.hip): d = n descriptors in device-addressable memory, one per stream
+// One stream of a direct-update batch (k_ekf_direct_update, ekf_direct.hip): m rows H r R on the IMU block, P updated in place.
+struct EkfDirectDev {
+    double *P;                // ld x ld, row-major, [0,d) x [0,d) live
+    int d, ld;
+    int m;                    // 0: the stream takes no part
+    int *status;              // out: 1 applied, 0 gated out, 2 S not positive definite (P untouched unless 1)
+    const double *H;          // m x 21
+    const double *r;          // m
+    const double *R;          // m x m, symmetric
+    double gate;              // > 0: the update is applied only when gamma <= gate
+    double *delta_x;          // out: d (zero unless applied)
+    double *gamma;            // out: r^T S^-1 r (0 when S is not positive definite)
+    double *pos_var_out;      // out, 3: P(12,12), P(13,13), P(14,14) after the call, or null
+};
+
+// ---- launchers (ekf_kernels.hip, ekf_linalg.hip, ekf_direct.hip): d = n descriptors in device-addressable memory, one per stream
 extern "C" {
 void ekf_launch_propagate(const EkfStreamDev *d, int n, hipStream_t st);
 void ekf_launch_remove_clone(const EkfStreamDev *d, int n, hipStream_t st);
@@ -113,6 +129,7 @@ void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int min_d, int max
 void ekf_launch_tsqr(const EkfStreamDev *d, int n, int min_d, int max_d, int do_cap, hipStream_t st);
 void ekf_launch_trsm(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
 void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st);
+void ekf_launch_direct_update(const EkfDirectDev *d, int n, hipStream_t st);
 }
 
 struct EkfStreamState {       // host-side bookkeeping of the device buffers of one stream

@@ -331,7 +331,7 @@ int MultiRunner::run_balanced(int first, int warmup, int steps, int max_extra, d
     static const int fe_phases[] = {PH_PUSH, PH_PREP1, PH_TRACK1, PH_AFTER1, PH_TRACK2,
                                     PH_AFTER2, PH_IMU, PH_HANDOFF, PH_FE_QWAIT};
     static const int ekf_phases[] = {PH_EKF_A, PH_UPD1, PH_EKF_B, PH_UPD2, PH_EKF_C,
-                                     PH_POSVAR, PH_EKF_QWAIT, PH_IMU_EKF};
+                                     PH_POSVAR, PH_EKF_QWAIT, PH_IMU_EKF, PH_DIRECT};
     std::vector<mskf_ctx *> fe_ctx(nb), ekf_ctx(nb);      // worker w = the two contexts group w created (captured before any batch moves)
     for (int w = 0; w < nb; ++w) { fe_ctx[w] = groups_[w]->ctx(); ekf_ctx[w] = groups_[w]->ekf_ctx(); }
     auto gate = [&](int w, bool fe, bool on) {

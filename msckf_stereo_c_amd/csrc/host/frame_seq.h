@@ -6,9 +6,9 @@
 
 namespace cg {
 
-// phases of the front-end thread: PH_IMU .. PH_FE_QWAIT (without PH_EKF_*); of the filter thread: PH_EKF_QWAIT, PH_IMU_EKF, PH_EKF_A .. PH_POSVAR
+// phases of the front-end thread: PH_IMU .. PH_FE_QWAIT (without PH_EKF_*); of the filter thread: PH_EKF_QWAIT, PH_IMU_EKF, PH_EKF_A .. PH_POSVAR, PH_DIRECT (the direct updates' batches and their waits)
 enum { PH_PUSH = 0, PH_PREP1, PH_TRACK1, PH_AFTER1, PH_TRACK2, PH_AFTER2, PH_EKF_A, PH_UPD1, PH_EKF_B, PH_UPD2, PH_EKF_C, PH_POSVAR, PH_IMU,
-       PH_HANDOFF, PH_FE_QWAIT, PH_EKF_QWAIT, PH_IMU_EKF, PH_COUNT };
+       PH_HANDOFF, PH_FE_QWAIT, PH_EKF_QWAIT, PH_IMU_EKF, PH_DIRECT, PH_COUNT };
 
 // runs fn(i) for i in [0, n) and returns when all are done (a BatchGroup passes its ForkJoin); empty: a plain loop
 typedef std::function<void(int, const std::function<void(int)> &)> ParFor;

@@ -34,6 +34,18 @@ int mskfh_load_configs(const char *config_dir, mskf_calib *calib, mskf_fe_cfg *f
     }
 }
 
+// the optional zupt keys of an app_msckfvio.yaml (zupt_cfg_from_yaml); 0 on success
+int mskfh_load_zupt_config(const char *yaml_path, int *on, double *max_disparity, int *min_features, double *noise_std) {
+    try {
+        const zupt::Config c = zupt_cfg_from_yaml(YAML::LoadFile(yaml_path));
+        *on = c.on ? 1 : 0; *max_disparity = c.max_disparity; *min_features = c.min_features; *noise_std = c.noise_std;
+        return 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "mskfh_load_zupt_config: %s\n", e.what());
+        return -1;
+    }
+}
+
 // where the front-end's bookkeeping runs (ImageProcessor::setFeBooksOnHost): tests compare the two paths
 void mskfh_set_fe_books_on_host(int on) { ImageProcessor::setFeBooksOnHost(on); }
 void mskfh_runner_destroy(void *h) { delete (MultiRunner *)h; }
@@ -226,6 +238,24 @@ void mskfh_runner_publish_covariance(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;
     for (int i = 0; i < r->n_streams(); ++i) if (stream < 0 || i == stream) r->system(i).msckfvio_ptr()->publishCovariance = on != 0;
 }
+// MsckfVio::setZupt of one stream, or of all (stream < 0); between runs
+int mskfh_runner_set_zupt(void *h, int stream, int on, double max_disparity, int min_features, double noise_std) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream >= r->n_streams() || !(max_disparity > 0) || !(noise_std > 0) || min_features < 0 || max_disparity > 1e300 || noise_std > 1e300) return MSKF_ERR_INVALID;
+    zupt::Config c;
+    c.on = on != 0; c.max_disparity = max_disparity; c.min_features = min_features; c.noise_std = noise_std;
+    for (int i = 0; i < r->n_streams(); ++i) if (stream < 0 || i == stream) r->system(i).msckfvio_ptr()->setZupt(c);
+    return MSKF_OK;
+}
+// MsckfVio::queueVelocity (kind 0) / queuePosition (kind 1) of one stream; between runs
+int mskfh_runner_fuse(void *h, int stream, int kind, double t, const double *z, const double *R, int gated) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream < 0 || stream >= r->n_streams() || !z || !R || (kind != 0 && kind != 1)) return MSKF_ERR_INVALID;
+    MsckfVio &v = *r->system(stream).msckfvio_ptr();
+    return (kind == 0 ? v.queueVelocity(t, z, R, gated != 0) : v.queuePosition(t, z, R, gated != 0)) ? MSKF_OK : MSKF_ERR_INVALID;
+}
+int mskfh_num_direct_updates(void *h, int stream) { return ((MultiRunner *)h)->system(stream).msckfvio_ptr()->numDirectUpdates(); }
+int mskfh_num_zupt(void *h, int stream) { return ((MultiRunner *)h)->system(stream).msckfvio_ptr()->numZupt(); }
 int mskfh_num_odom_covs(void *h, int stream) { return (int)((MultiRunner *)h)->system(stream).msckfvio_ptr()->odomCovs().size(); }
 void mskfh_get_odom_covs(void *h, int stream, mskf_odom_cov *out) {
     const auto &c = ((MultiRunner *)h)->system(stream).msckfvio_ptr()->odomCovs();

@@ -9,6 +9,7 @@
 #include "image_processor.h"
 #include "kinematics.h"
 #include "../hip/ekf_meas.h"
+#include "../../../include/mskf_chi2_table.h"
 
 namespace cg {
 
@@ -43,6 +44,21 @@ mskf_ekf_cfg ekf_cfg_from_yaml(const YAML::Node &y) {
     return c;
 }
 
+zupt::Config zupt_cfg_from_yaml(const YAML::Node &y) {
+    zupt::Config c;
+    if (y["zupt"].IsDefined()) {
+        const std::string v = y["zupt"].as<std::string>();
+        if (v == "on") c.on = true;
+        else if (v != "off") throw YAML::Exception("yaml: zupt must be on or off, not '" + v + "'");
+    }
+    if (y["zupt_max_disparity"].IsDefined()) c.max_disparity = y["zupt_max_disparity"].as<double>();
+    if (y["zupt_min_features"].IsDefined()) c.min_features = y["zupt_min_features"].as<int>();
+    if (y["zupt_noise_std"].IsDefined()) c.noise_std = y["zupt_noise_std"].as<double>();
+    if (!(c.max_disparity > 0) || c.min_features < 0 || !(c.noise_std > 0) || !std::isfinite(c.max_disparity) || !std::isfinite(c.noise_std))
+        throw YAML::Exception("yaml: zupt_max_disparity and zupt_noise_std must be positive, zupt_min_features not negative");
+    return c;
+}
+
 MsckfVio::MsckfVio(YAML::Node cfg_cam_imu) : cfg_cam_imu_(cfg_cam_imu), have_yaml_(true) {
     std::memset(&calib_, 0, sizeof(calib_));
     std::memset(&cfg_, 0, sizeof(cfg_));
@@ -67,6 +83,7 @@ bool MsckfVio::loadParameters() {
         calib_ = calib_from_yaml(cfg_cam_imu_);
         YAML::Node y = YAML::LoadFile("../config/app_msckfvio.yaml");   // Q16
         cfg_ = ekf_cfg_from_yaml(y);
+        zupt_ = zupt_cfg_from_yaml(y);
     }
     feat_translation_threshold_ = cfg_.feature_translation_threshold;
     gyro_noise_ = cfg_.noise_gyro * cfg_.noise_gyro;            // :77-81 variance, not std
@@ -142,6 +159,11 @@ bool MsckfVio::resetCallback() {
     imu_msg_buffer.clear();
     is_gravity_set = false;
     is_first_img = true;
+    // what was queued for, or observed by, the filter before the reset does not reach the filter after it
+    direct_queue_.clear();
+    publish_deferred_ = false;
+    zupt_prev_.clear();
+    zupt_have_prev_ = false;
     return true;
 }
 
@@ -196,6 +218,25 @@ int MsckfVio::runFrame(mskf_ctx *ekf_ctx, int n, MsckfVio *const *vio, mskf_stre
     for (int i = 0; i < n; ++i) any_rm |= s.rm[2 * i] >= 0;
     if (any_rm) FRAME_CHK(mskf_ekf_remove_clones_batch, (ekf_ctx, n, streams, s.rm.data()));
     lap(PH_EKF_C);
+    // direct measurements (queueVelocity / queuePosition / a zero-velocity update) of the streams that have one due: one update
+    // batch per round over those streams, behind the clone removal, each against the state the round before left; then the
+    // publish these streams postponed in phaseC.  No stream has one: nothing here runs.
+    bool any_direct = false;
+    for (int i = 0; i < n; ++i) any_direct |= vio[i]->directDue();
+    if (any_direct) {
+        for (;;) {
+            s.dir_i.clear(); s.dir_s.clear();
+            for (int i = 0; i < n; ++i) if (vio[i]->directDue()) { s.dir_i.push_back(i); s.dir_s.push_back(streams[i]); }
+            if (s.dir_i.empty()) break;
+            s.dir_a.resize(s.dir_i.size());
+            for (size_t k = 0; k < s.dir_i.size(); ++k) vio[s.dir_i[k]]->buildDirect(s.dir_a[k]);
+            FRAME_CHK(mskf_ekf_update_direct_batch_begin, (ekf_ctx, (int)s.dir_s.size(), s.dir_s.data(), s.dir_a.data()));
+            FRAME_CHK(mskf_ekf_update_direct_batch_end, (ekf_ctx));
+            for (size_t k = 0; k < s.dir_i.size(); ++k) vio[s.dir_i[k]]->finishDirect(s.dir_a[k]);
+        }
+        for (int i = 0; i < n; ++i) vio[i]->publishDeferred();
+        lap(PH_DIRECT);
+    }
     // publishCovariance on any stream: one read-out of all the streams' odometry covariances (msckf_vio.cpp:1262-1293) behind the
     // clone removal, before onlineReset (:356, :359); its pos_var is what onlineReset tests, so it takes the place of the
     // fallback below (and costs a host wait of its own)
@@ -233,6 +274,7 @@ bool MsckfVio::phaseA(const CameraMeasurementConstPtr &msg, mskf_ekf_update_args
     pos_var_valid_ = false;
     have_J_ = false;
     imu_steps_.clear();
+    if (zupt_.on) zuptObserve(msg);
     if (!is_gravity_set) return false;
     if (is_first_img) { is_first_img = false; state_server.imu_state.time = msg->time_stamp; }
     frame_active_ = true;
@@ -498,8 +540,90 @@ void MsckfVio::buildLostFeatureUpdate(mskf_ekf_update_args &upd) {
     finishArgs(upd, -1, 1);   // Q12 dof = #obs - 1, Q13 row cap
 }
 
+// ---- direct measurements
+bool MsckfVio::queueDirect(int first_col, double t, const double z[3], const double R[9], bool gated, bool is_zupt) {
+    DirectMeas m;
+    m.first_col = first_col; m.t = t; m.gated = gated; m.is_zupt = is_zupt;
+    if (!std::isfinite(t)) return false;
+    for (int i = 0; i < 3; ++i) { if (!std::isfinite(z[i])) return false; m.z[i] = z[i]; }
+    for (int i = 0; i < 9; ++i) { if (!std::isfinite(R[i])) return false; m.R[i] = R[i]; }
+    for (int i = 0; i < 3; ++i) {            // what mskf_ekf_update_direct would refuse, refused here: a bad R must not fail a frame
+        if (!(R[4 * i] > 0.0)) return false;
+        for (int j = 0; j < i; ++j) if (R[3 * i + j] != R[3 * j + i]) return false;
+    }
+    direct_queue_.push_back(m);
+    return true;
+}
+
+// the cam0 points of this message against the previous message's (zupt.h); a stationary pair queues the zero-velocity measurement
+void MsckfVio::zuptObserve(const CameraMeasurementConstPtr &msg) {
+    size_t cnt = msg->features.size();
+    if (zero_tail_msg_ == msg.get() && zero_tail_start_ < cnt) cnt = zero_tail_start_;      // (the never-written tail records are no points)
+    zupt_curr_.resize(cnt);
+    for (size_t k = 0; k < cnt; ++k) { const FeatureMeasurement &f = msg->features[k]; zupt_curr_[k] = zupt::Point{f.id, f.u0, f.v0}; }
+    // (is_gravity_set: phaseA runs this frame's filter, so a measurement queued here is applied in this very frame, never later)
+    if (zupt_have_prev_ && is_gravity_set) {
+        const zupt::Disparity d = zupt::disparity(zupt_prev_.data(), zupt_prev_.size(), zupt_curr_.data(), zupt_curr_.size(),
+                                                   calib_.cam0_intrinsics[0], calib_.cam0_intrinsics[1], &zupt_scratch_);
+        if (zupt::stationary(d, zupt_)) {
+            const double z[3] = {0, 0, 0}, v = zupt_.noise_std * zupt_.noise_std, R[9] = {v, 0, 0, 0, v, 0, 0, 0, v};
+            queueDirect(6, msg->time_stamp, z, R, true, true);
+        }
+    }
+    zupt_prev_.swap(zupt_curr_);
+    zupt_have_prev_ = true;
+}
+
+bool MsckfVio::directDue() const {
+    if (!frame_active_) return false;
+    for (const DirectMeas &m : direct_queue_) if (m.t <= frame_time_) return true;
+    return false;
+}
+
+void MsckfVio::buildDirect(mskf_ekf_direct_args &a) {
+    size_t k = 0;
+    while (k < direct_queue_.size() && !(direct_queue_[k].t <= frame_time_)) ++k;
+    direct_cur_ = direct_queue_[k];
+    direct_queue_.erase(direct_queue_.begin() + (std::ptrdiff_t)k);
+    const IMUState &s = state_server.imu_state;
+    const Vector3 &x = direct_cur_.first_col == 6 ? s.velocity : s.position;
+    std::memset(dH_, 0, sizeof(dH_));
+    for (int i = 0; i < 3; ++i) { dH_[i * 21 + direct_cur_.first_col + i] = 1.0; dr_[i] = direct_cur_.z[i] - x[i]; }
+    ddx_.assign(21 + 6 * state_server.cam_states.size(), 0.0);
+    std::memset(&a, 0, sizeof(a));
+    a.m = 3; a.H = dH_; a.r = dr_; a.R = direct_cur_.R;
+    a.gate = direct_cur_.gated ? mskf_chi2_ppf95[3 - 1] : 0.0;      // 95 % of chi-square with 3 degrees of freedom
+    a.delta_x = ddx_.data();
+    a.pos_var_out = pos_var_buf_;
+    pos_var_buf_[0] = pos_var_buf_[1] = pos_var_buf_[2] = -1.0;
+}
+
+void MsckfVio::finishDirect(const mskf_ekf_direct_args &a) {
+    takePosVar();                               // the variances after this call, applied or not: what onlineReset tests
+    if (a.status != 1) return;                  // gated out, or S not positive definite: no correction
+    applyStateCorrection(ddx_);
+    ++n_direct_updates_;
+    if (direct_cur_.is_zupt) ++n_zupt_;
+}
+
+void MsckfVio::publishDeferred() {
+    if (!publish_deferred_) return;
+    publish_deferred_ = false;
+    hostprof::Scope hp_pub(hostprof::EKF_PUBLISH);
+    publish(frame_time_);
+    ++n_pub_;
+}
+
 // measurementUpdate, state part (:862-894)
 void MsckfVio::applyCorrection(const std::vector<double> &dx) {
+    applyStateCorrection(dx);
+    n_tsqr_ += diag_out_[0] == 1 ? 1 : 0;
+    n_direct_ += diag_out_[0] == 2 ? 1 : 0;
+    rows_sum_ += rows_out_;
+    ++n_update_;
+}
+
+void MsckfVio::applyStateCorrection(const std::vector<double> &dx) {
     IMUState &s = state_server.imu_state;
     double dq[4];
     kin::small_angle(Vector3(dx[0], dx[1], dx[2]), dq);
@@ -513,9 +637,6 @@ void MsckfVio::applyCorrection(const std::vector<double> &dx) {
     kin::small_angle(Vector3(dx[15], dx[16], dx[17]), dq);
     s.R_imu_cam0 = kin::rotation_of(dq) * s.R_imu_cam0;
     for (int i = 0; i < 3; ++i) s.t_cam0_imu[i] += dx[18 + i];
-    n_tsqr_ += diag_out_[0] == 1 ? 1 : 0;
-    n_direct_ += diag_out_[0] == 2 ? 1 : 0;
-    rows_sum_ += rows_out_;
     int ci = 0;
     for (auto &kv : state_server.cam_states) {
         const double *d = &dx[21 + 6 * ci];
@@ -524,7 +645,6 @@ void MsckfVio::applyCorrection(const std::vector<double> &dx) {
         for (int i = 0; i < 3; ++i) kv.second.position[i] += d[3 + i];
         ++ci;
     }
-    ++n_update_;
 }
 
 // featureJacobian's debug output (msckf_vio.cpp:719-723): in the frame with n_pub == 9 the reference writes the
@@ -688,6 +808,7 @@ void MsckfVio::phaseC() {
         }
         prune_pending_ = false;
     }
+    if (directDue()) { publish_deferred_ = true; return; }      // a direct update follows the clone removal: publish behind its correction (publishDeferred)
     hostprof::Scope hp_pub(hostprof::EKF_PUBLISH);
     publish(frame_time_);
     ++n_pub_;                                    // :356
@@ -703,6 +824,7 @@ void MsckfVio::phaseD(const double pos_var[3]) {
     resetCloneSlots();
     map_server.clear();
     resetCov();
+    direct_queue_.clear();          // measurements queued against the state that has just been given up (the messages go on: zupt_prev_ stays)
 }
 
 // :1238-1305

@@ -6,7 +6,7 @@
 // augmentation, triangulation, Jacobians, gating, QR and the Kalman update run behind the C-ABI
 // (include/mskf_hip.h); this class integrates the 16-dim nominal state, keeps the clone / feature maps
 // and applies the returned correction vector.  The order of a frame (phaseA -> predict -> update -> phaseB -> update ->
-// phaseC -> clone removal -> read-out -> phaseD) is written once, over n streams, in runFrame(): featureCallback() is
+// phaseC -> clone removal -> [direct updates of the streams that have one due -> correction -> publish] -> read-out -> phaseD) is written once, over n streams, in runFrame(): featureCallback() is
 // runFrame() with n = 1, BatchGroup calls it with its group.  The phases themselves never touch the device.
 #pragma once
 #include <array>
@@ -20,10 +20,14 @@
 #include "feature_store.h"
 #include "frame_seq.h"
 #include "yaml_lite.h"
+#include "zupt.h"
 
 namespace cg {
 
 mskf_ekf_cfg ekf_cfg_from_yaml(const YAML::Node &cfg_msckfvio);
+// optional keys of app_msckfvio.yaml (not keys of the reference's file): zupt: on | off, zupt_max_disparity, zupt_min_features,
+// zupt_noise_std; absent means off (zupt.h)
+zupt::Config zupt_cfg_from_yaml(const YAML::Node &cfg_msckfvio);
 
 struct Quat { double q[4] = {0, 0, 0, 1}; };   // JPL [x y z w]
 
@@ -79,6 +83,7 @@ class MsckfVio {
         std::vector<int32_t> pred_ns, rm;                     // prediction steps and clone removals per stream
         std::vector<const mskf_imu_step *> pred_sp; std::vector<const double *> pred_jp;
         std::vector<double> pv; std::vector<mskf_odom_cov> oc;   // position variances fetched on their own (3 per stream); odometry covariances
+        std::vector<mskf_ekf_direct_args> dir_a; std::vector<mskf_stream *> dir_s; std::vector<int> dir_i;   // the streams with a direct update due (valid until *_end)
     };
     static int runFrame(mskf_ctx *ekf_ctx, int n, MsckfVio *const *vio, mskf_stream *const *streams, const CameraMeasurementConstPtr *msgs,
                         FrameScratch &scratch, const ParFor &par, double *acc, std::string &err);
@@ -96,6 +101,24 @@ class MsckfVio {
     // phase C: apply the pruning update, delete clones (the device's copies: pendingRemovals()), publish
     void phaseC();
     const int32_t *pendingRemovals() const { return pending_rm_; }   // two clone indices (current state order) or -1
+    // ---- opt-in direct measurements (mskf_ekf_update_direct*): world-frame measurements z of the IMU's velocity (error states 6..8)
+    // or position (12..14) with covariance R (3 x 3 row-major, symmetric, positive diagonal), applied in the first filter frame whose
+    // time stamp is >= t: r = z - state, H the selector, gated at the 95 % chi-square value of 3 degrees of freedom when `gated`.
+    // A frame applies everything that is due, oldest first, one update batch per round, behind the clone removal; the published
+    // pose of such a frame carries the corrections (publish moves from phaseC behind them).  false: R refused, nothing queued.
+    // resetCallback and an online reset (phaseD) empty the queue: what was measured against the old state is not applied to the new.
+    bool queueVelocity(double t, const double z[3], const double R[9], bool gated) { return queueDirect(6, t, z, R, gated, false); }
+    bool queuePosition(double t, const double z[3], const double R[9], bool gated) { return queueDirect(12, t, z, R, gated, false); }
+    // zero-velocity update: with c.on every frame compares the cam0 points of its message with the previous message's (zupt.h) and a
+    // stationary pair queues z = 0 on the velocity with R = noise_std^2 I, gated
+    void setZupt(const zupt::Config &c) { zupt_ = c; zupt_prev_.clear(); zupt_have_prev_ = false; }
+    const zupt::Config &zuptConfig() const { return zupt_; }
+    bool directDue() const;                                  // a queued measurement applies in this frame
+    void buildDirect(mskf_ekf_direct_args &a);               // the oldest due measurement, against the state as it is now
+    void finishDirect(const mskf_ekf_direct_args &a);        // its correction, counters, position variances
+    void publishDeferred();                                  // the publish a frame with a direct update postponed in phaseC
+    int numDirectUpdates() const { return n_direct_updates_; }   // direct updates applied (status 1), zero-velocity updates included
+    int numZupt() const { return n_zupt_; }                      // ... of which zero-velocity updates
     // phase D: online reset decision from the position variances (msckf_vio.cpp:1186-1236)
     void phaseD(const double pos_var[3]);
     // the position variances the last update of this frame brought back (mskf_ekf_update_args.pos_var_out), if any
@@ -152,6 +175,9 @@ class MsckfVio {
     void findRedundantCamStates(std::vector<StateIDType> &rm);
     void buildPruneUpdate(mskf_ekf_update_args &upd);
     void applyCorrection(const std::vector<double> &delta_x);
+    void applyStateCorrection(const std::vector<double> &delta_x);   // the state part alone (a direct update counts as no feature update)
+    bool queueDirect(int first_col, double t, const double z[3], const double R[9], bool gated, bool is_zupt);
+    void zuptObserve(const CameraMeasurementConstPtr &msg);
     void publish(double time_stamp);
     bool checkMotion(int slot, uint64_t mask) const;
     void packClones();
@@ -214,6 +240,18 @@ class MsckfVio {
     double J_[6 * 21];
     int32_t pending_rm_[2] = {-1, -1};
     int rm_order_[2] = {-1, -1};                           // window positions of the two clones being pruned
+    // direct measurements: the queue (insertion order), the one in flight and its argument arrays
+    struct DirectMeas { int first_col; double t, z[3], R[9]; bool gated, is_zupt; };
+    std::vector<DirectMeas> direct_queue_;
+    DirectMeas direct_cur_{};
+    double dH_[3 * 21], dr_[3];
+    std::vector<double> ddx_;
+    int n_direct_updates_ = 0, n_zupt_ = 0;
+    bool publish_deferred_ = false;
+    zupt::Config zupt_;
+    std::vector<zupt::Point> zupt_prev_, zupt_curr_;
+    zupt::Scratch zupt_scratch_;
+    bool zupt_have_prev_ = false;
     const CameraMeasurement *zero_tail_msg_ = nullptr;
     size_t zero_tail_start_ = 0, zero_tail_total_ = 0;
     std::ofstream pose_outfile_, debug_, cov_outfile_;

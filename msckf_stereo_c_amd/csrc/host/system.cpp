@@ -16,6 +16,7 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);
         if (ok_) { imgproc_ptr_->enableFileOutputs(); msckfvio_ptr_->enableFileOutputs(); }   // pose_out.txt, debug_imageprocessor.txt
+        if (ok_) msckfvio_ptr_->setZupt(zupt_cfg_from_yaml(cfg_msckfvio));        // optional keys zupt*: absent means off
         // optional (not a key of the reference's file): "covariance_out: <file>" writes publish()'s covariances, one line per pose
         if (ok_ && cfg_msckfvio["covariance_out"].IsDefined()) msckfvio_ptr_->enableCovarianceOutput(cfg_msckfvio["covariance_out"].as<std::string>());
     } catch (const std::exception &e) {   // the reference swallows init errors and only prints (system.cpp:17-33)

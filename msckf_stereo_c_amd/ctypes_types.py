@@ -67,6 +67,16 @@ class OdomCov(C.Structure):
     _fields_ = [("pose", C.c_double * 36), ("twist", C.c_double * 9), ("pos_var", C.c_double * 3)]
 
 
+class EkfDirectArgs(C.Structure):
+    """mskf_ekf_direct_args (include/mskf_hip.h): a direct measurement update of up to DIRECT_MAX_ROWS rows on the IMU block."""
+    _fields_ = [("m", C.c_int32), ("status", C.c_int32), ("H", C.c_void_p), ("r", C.c_void_p), ("R", C.c_void_p), ("gate", C.c_double),
+                ("delta_x", C.c_void_p), ("gamma", C.c_double), ("pos_var_out", C.c_void_p)]
+
+
+assert C.sizeof(EkfDirectArgs) == 64
+DIRECT_MAX_ROWS = 6          # MSKF_DIRECT_MAX_ROWS (csrc/hip/ekf_device.h)
+
+
 class FeEqualize(C.Structure):
     """mskf_fe_equalize (include/mskf_hip.h): opt-in equalisation of the pushed images; mode 0 off, 1 global, 2 CLAHE."""
     _fields_ = [("mode", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("_pad", C.c_int32), ("clip_limit", C.c_double)]

@@ -41,6 +41,8 @@ def lib():
         L.mskfh_runner_publish_covariance.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mskfh_runner_set_equalize.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeEqualize)]
         L.mskfh_runner_set_input_format.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeInputFormat)]
+        L.mskfh_runner_set_zupt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double]
+        L.mskfh_runner_fuse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
         L.mskfh_num_odom_covs.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_num_odom_covs.restype = C.c_int
         L.mskfh_get_odom_covs.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -54,7 +56,7 @@ def lib():
         L.mskfh_runner_group_offset.argtypes = [C.c_void_p, C.c_int]
         L.mskfh_runner_group_offset.restype = C.c_int
         for name in ("mskfh_num_features", "mskfh_msg_size", "mskfh_num_poses", "mskfh_state_dim", "mskfh_num_updates",
-                     "mskfh_num_clones"):
+                     "mskfh_num_clones", "mskfh_num_direct_updates", "mskfh_num_zupt"):
             getattr(L, name).argtypes = [C.c_void_p, C.c_int]
             getattr(L, name).restype = C.c_int
         L.mskfh_num_tsqr_updates.argtypes = [C.c_void_p, C.c_int]
@@ -238,7 +240,40 @@ class Runner:
         covariance (one device read-out per filter frame).  Off by default; set it before the first frame."""
         self.L.mskfh_runner_publish_covariance(self.h, -1 if stream is None else int(stream), int(on))
 
-    # indexed like the MSKF_K_* kinds of mskf_hip.h; "k_ekf_augment" keeps its place and stays empty (augmentation is fused into k_ekf_propagate)
+    def set_zupt(self, on, max_disparity=0.5, min_features=20, noise_std=0.05, stream=None):
+        """Opt-in zero-velocity update of one stream or of all: a frame whose message has at least min_features cam0 points in common
+        with the previous message, moved by less than max_disparity pixels on average, fuses velocity = 0 with standard deviation
+        noise_std (m/s), gated.  The defaults are starting values nobody has tuned.  Call between runs."""
+        rc = self.L.mskfh_runner_set_zupt(self.h, -1 if stream is None else int(stream), int(bool(on)), float(max_disparity), int(min_features), float(noise_std))
+        if rc != 0:
+            raise MskfError("set_zupt: max_disparity and noise_std must be positive, min_features not negative, the stream one of the runner's", rc)
+
+    def _fuse(self, kind, stream, t, z, cov, gated):
+        z = np.ascontiguousarray(z, dtype=np.float64).reshape(3)
+        cov = np.ascontiguousarray(cov, dtype=np.float64).reshape(3, 3)
+        rc = self.L.mskfh_runner_fuse(self.h, int(stream), kind, float(t), _p(z), _p(cov), int(bool(gated)))
+        if rc != 0:
+            raise MskfError("a fused measurement takes finite values and a symmetric covariance with a positive diagonal", rc)
+
+    def fuse_velocity(self, stream, t, v, cov, gated=True):
+        """Queue a world-frame measurement v (3) of the IMU's velocity with covariance cov (3 x 3) for the first filter frame of the
+        stream whose time stamp is >= t; gated: applied only inside the 95 % chi-square gate of 3 degrees of freedom."""
+        self._fuse(0, stream, t, v, cov, gated)
+
+    def fuse_position(self, stream, t, p, cov, gated=True):
+        """The same for a world-frame measurement p of the IMU's position."""
+        self._fuse(1, stream, t, p, cov, gated)
+
+    def num_direct_updates(self, stream=0):
+        """Direct measurement updates applied to the stream (fused velocities and positions, zero-velocity updates)."""
+        return self.L.mskfh_num_direct_updates(self.h, stream)
+
+    def num_zupt(self, stream=0):
+        """... of which zero-velocity updates."""
+        return self.L.mskfh_num_zupt(self.h, stream)
+
+    # indexed like the MSKF_K_* kinds of mskf_hip.h; "k_ekf_augment" keeps its place: the augmentation is fused into k_ekf_propagate, and
+    # the slot counts the launches of k_ekf_direct_update (mskf_hip.h)
     KERNELS = ["k_pyr_down", "k_detect_cells", "k_track4", "k_ekf_propagate", "k_ekf_augment", "k_ekf_feature_blocks",
                "k_ekf_tsqr", "k_ekf_gemm", "k_ekf_chol_lds", "k_ekf_trsm", "k_ekf_small", "k_ekf_remove_clone", "k_pt_geom", "k_fe_book"]
 
@@ -246,7 +281,9 @@ class Runner:
         self.L.mskfh_runner_set_timing(self.h, int(enable))
 
     def get_timing(self, reset=True):
-        """Per-kernel HIP-event timing accumulated on the groups' own streams: {kernel: (ms, launches, units)}."""
+        """Per-kernel HIP-event timing accumulated on the groups' own streams: {kernel: (ms, launches, units)}.  The key
+        "k_ekf_augment" carries the launches of k_ekf_direct_update (fused measurements, zero-velocity updates; units: streams with
+        rows) and nothing else: the augmentation itself runs inside k_ekf_propagate, and the slot keeps its name for the ABI."""
         k = len(self.KERNELS)
         ms = np.zeros(k)
         launches = np.zeros(k, np.int64)
@@ -255,9 +292,9 @@ class Runner:
         return {n: (float(ms[i]), int(launches[i]), int(units[i])) for i, n in enumerate(self.KERNELS)}
 
     PHASES = ["push", "fe_prepare1", "track1", "fe_after1", "track2", "fe_after2", "ekf_A", "update1", "ekf_B", "update2",
-              "ekf_C", "posvar", "imu_feed", "handoff", "fe_queue_wait", "ekf_queue_wait", "imu_feed_ekf"]
+              "ekf_C", "posvar", "imu_feed", "handoff", "fe_queue_wait", "ekf_queue_wait", "imu_feed_ekf", "direct"]
     FE_THREAD_PHASES = ["imu_feed", "push", "fe_prepare1", "track1", "fe_after1", "track2", "fe_after2", "handoff", "fe_queue_wait"]
-    EKF_THREAD_PHASES = ["ekf_queue_wait", "imu_feed_ekf", "ekf_A", "update1", "ekf_B", "update2", "ekf_C", "posvar"]
+    EKF_THREAD_PHASES = ["ekf_queue_wait", "imu_feed_ekf", "ekf_A", "update1", "ekf_B", "update2", "ekf_C", "posvar", "direct"]
 
     def get_window_phases_group(self, g):
         """The same for one group."""
