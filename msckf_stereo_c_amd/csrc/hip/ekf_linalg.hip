@@ -716,7 +716,11 @@ __global__ __launch_bounds__(CHOLG_THREADS) void k_ekf_chol(const EkfStreamDev *
         for (int k = tid; k < n; k += CHOLG_THREADS) S.T[(size_t)k * lda + S.d] = A[(size_t)n * lda + k];
         __syncthreads();
         double *Rg = S.W;
-        ekf_compress_exit(S, true, s_diag, [=](int k, int j) -> double & { return Rg[(size_t)k * lda + j]; }, sPanT, LNB * pan_rs);
+        // the TSQR's row block: the panel a launch for this stream alone allocates (the batch's is no smaller).  Sized from the
+        // launch's pan_rs, a 31-clone stream beside a 64-clone one took 32-row blocks instead of 16-row ones and its results
+        // differed in the last bits from the same update alone (tests/test_gpu_update_routes.py).
+        const int own_rs = (S.d - EKF_IMU_DIM + 1 + 15) / 16 * 16;
+        ekf_compress_exit(S, true, s_diag, [=](int k, int j) -> double & { return Rg[(size_t)k * lda + j]; }, sPanT, LNB * min(own_rs, pan_rs));
     }
 }
 

@@ -237,6 +237,10 @@ def test_ekf_propagate_augment_remove(gpu_ctx, oracle):
 
 @pytest.mark.parametrize("n_clones,n_feat,seed,dof_offset", [(6, 5, 1, -1), (20, 30, 2, -1), (30, 60, 3, -1), (12, 20, 4, 0)])
 def test_ekf_update_matches_oracle(gpu_ctx, oracle, n_clones, n_feat, seed, dof_offset):
+    """The whole update against the oracle in the default configuration.  Since compression_mode 3 became the default of
+    default_ekf_cfg() this is the Householder route (k_ekf_tsqr, then T, S, the factorisation of S, the solve and the
+    downdate), not Gram + regularised Cholesky: the bars below were set for the Gram route and still carry its lambda prior.
+    The Gram route, the fallback TSQR and the kernels' size limits are checked in value by tests/test_gpu_update_routes.py."""
     s, calib = _stream(gpu_ctx, oracle, 376, 240, max_cam_state_size=max(n_clones, 4))
     cfg = default_ekf_cfg(max_cam_state_size=max(n_clones, 4))
     pr = ekf_problems.make_problem(calib, seed=seed, n_clones=n_clones, n_feat=n_feat)
@@ -253,7 +257,7 @@ def test_ekf_update_matches_oracle(gpu_ctx, oracle, n_clones, n_feat, seed, dof_
     scale = np.abs(ref["delta_x"]).max()
     assert np.allclose(got["delta_x"], ref["delta_x"], rtol=1e-6, atol=1e-9 * max(scale, 1e-3))
     Pg = s.ekf_get_cov()
-    assert np.allclose(Pg, ref["P"], rtol=1e-7, atol=1e-8 * np.abs(ref["P"]).max())   # incl. the lambda-prior bias (~1e-10)
+    assert np.allclose(Pg, ref["P"], rtol=1e-7, atol=1e-8 * np.abs(ref["P"]).max())   # (wide enough for the Gram route's lambda-prior bias, ~1e-10)
     assert np.array_equal(Pg, Pg.T)
     s.close()
 
@@ -346,8 +350,11 @@ def test_detector_small_and_odd_geometries(gpu_ctx, oracle, w, h):
 @pytest.mark.parametrize("n_clones,n_feat", [(29, 4), (13, 4), (24, 4), (30, 4), (10, 2), (19, 3)])
 def test_ekf_update_ill_conditioned(gpu_ctx, oracle, n_clones, n_feat):
     """Few features over many clones: the stacked Jacobian is rank deficient beyond the gauge and cond(H) ~ 1e6-1e7.
-    An unpivoted semidefinite Cholesky of H^T H loses up to 7e-5 here (tools/dev/update_truth.py); the regularised
-    factorisation has to stay at the 1e-9 level against the oracle's Householder path."""
+    An unpivoted semidefinite Cholesky of H^T H loses up to 7e-5 here (tools/dev/update_truth.py), which is why the Gram route
+    factors G + lambda I.  Since compression_mode 3 became the default of default_ekf_cfg() these stacks do NOT reach that
+    factorisation any more: they run k_ekf_tsqr (rows > active columns) or the uncompressed route, Householder against the
+    oracle's Householder, at the 1e-9 level asserted here.  The regularised factorisation on such stacks is checked in value in
+    compression modes 0 and 1 by test_ekf_compression_condition_sweep and tests/test_gpu_update_routes.py."""
     s, calib = _stream(gpu_ctx, oracle, 376, 240, max_cam_state_size=max(n_clones, 4))
     cfg = default_ekf_cfg(max_cam_state_size=max(n_clones, 4))
     pr = ekf_problems.make_problem(calib, seed=100 + n_clones, n_clones=n_clones, n_feat=n_feat, min_obs=3)
@@ -463,8 +470,11 @@ def test_ekf_compression_condition_sweep(gpu_ctx, oracle):
 
 @pytest.mark.parametrize("n_clones,n_feat,seed", [(50, 40, 21), (60, 30, 22), (64, 30, 23)])
 def test_ekf_update_many_clones(gpu_ctx, oracle, n_clones, n_feat, seed):
-    """d = 321 / 381 / 405 (the largest window mskf_stream_create accepts): global-memory Cholesky fallback, gating
-    matrix outside LDS, > 1500 stacked rows (cap), the triangular solve's strip at its LDS limit."""
+    """d = 321 / 381 / 405 (the largest window mskf_stream_create accepts): gating matrix outside LDS, > 1500 stacked rows
+    (cap), the triangular solve's strip at its LDS limit.  Since compression_mode 3 became the default of default_ekf_cfg() the
+    stack is compressed by k_ekf_tsqr<16,4,2> with R in the W buffer; the global-memory Cholesky k_ekf_chol runs here on the
+    innovation covariance only (which == 1).  Its Gram variant (which == 0) at these windows is checked by
+    tests/test_gpu_update_routes.py (31, 32, 34, 35 and 64 clones in mode 1)."""
     s, calib = _stream(gpu_ctx, oracle, 376, 240, max_cam_state_size=n_clones)
     cfg = default_ekf_cfg(max_cam_state_size=n_clones)
     pr = ekf_problems.make_problem(calib, seed=seed, n_clones=n_clones, n_feat=n_feat, min_obs=20)
