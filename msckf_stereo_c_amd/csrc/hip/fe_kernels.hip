@@ -9,9 +9,9 @@
 // Arithmetic contract: every decision-bearing quantity is integer or a fixed
 // sequence of IEEE-754 double operations; this file must be compiled with -ffp-contract=off.
 // Work shapes: one 16-lane DPP row per tracked point (four points per wavefront, a lane owns one row of the 15x15
-// window), one workgroup per 32x32 detector tile, one workgroup per 64x16 pyramid output tile; the
-// stream index of the batch is blockIdx.y / blockIdx.z, so a launch covers every VIO stream of a
-// context and fills the chip only when many streams are batched.
+// window); the detector and the pyramid pass march 16-lane strips down segments of rows, four (strip, segment) jobs per
+// one-wave workgroup, in registers and DPP only.  A launch covers every VIO stream of a context and fills the chip only
+// when many streams are batched.
 #include <stdlib.h>
 #include <mutex>
 #include "fe_device.h"
@@ -23,239 +23,204 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     return i;
 }
 
-// ---- levels 1, 2 and 3 of one image in ONE launch.
-// Round 3 ran cg::pyr_down as one launch per level: level k was written to HBM and read back by the level k + 1 launch
-// (1.46 x the algorithmic traffic), two of the three launches were tiny, and in the busy device each of the three dependent
-// launches queued for compute units on its own (200 us per launch in situ against 55 alone).  Here a workgroup owns a
-// 16 x 8 tile of LEVEL 3 and everything above it: it reads the level-0 footprint once (156 x 92 pixels for the 128 x 64 it
-// owns; the halo is shared with the neighbouring tiles through the XCD's L2: the tiles of one image get block ids that are
-// congruent modulo 8), keeps its level-1 region (76 x 44) and its level-2 region (36 x 20) in LDS, and writes the parts of
-// the three levels it owns.  Every level is the separable [1 4 6 4 1] / 256 filter with BORDER_REFLECT_101 of the level
-// BELOW it, so the values are those of three separate passes bit for bit: a region holds in-image pixels of its level, the
-// two reflected columns / rows on either side of the image that the next level's taps can reach are filled in by copying
-// (pd_fill_halo), and the level-0 taps are reflected at the loads.
-// Planes: columns are shifted so that the columns a tile OWNS start on a group of four (stores and LDS rows stay dword
-// aligned): a level-1 plane column pc is x1 = 4 * x3_0 - 8 + pc (80 columns, 76 used), a level-2 plane column qc is
-// x2 = 2 * x3_0 - 4 + qc (40 columns, 36 used); byte planes carry 4 bytes of padding in front of every row because the
-// next level's window of a group starts two pixels before a dword boundary.
-#define P3_TW 16
-#define P3_TH 8
+// ---- levels 1, 2 and 3 of one image in ONE launch, as a register / DPP row march (no LDS, no barrier, one-wave workgroups).
+// Every level is the separable [1 4 6 4 1] / 256 filter with BORDER_REFLECT_101 of the level BELOW it, so the values are those
+// of three separate passes bit for bit (reflecting level 0 alone does NOT give them: level k + 1 reflects the pixels of level k).
+// A 16-lane DPP row is one JOB: a STRIP of 16 level-3 columns (a lane owns eight consecutive level-0 columns = four level-1,
+// two level-2, one level-3 column) marched down the level-0 rows of a SEGMENT of level-3 rows; a wavefront carries four jobs.
+// Per level-0 row a lane loads its eight bytes, takes the two pixels to its left and the one to its right from the neighbouring
+// lanes (row_shr / row_shl) and forms four horizontal sums with 8-bit dot products.  The vertical pass of a level is a ring of
+// the last five rows of that level's horizontal sums in registers (2 + 1 + 1 dwords per row, two sums per dword): a level-1 row
+// comes out every second level-0 row, a level-2 row every fourth, a level-3 row every eighth, and each is passed on to the next
+// level's horizontal sums straight from the registers.  A level-3 column needs the level-0 columns 8 x3 - 14 .. 8 x3 + 14: the
+// two lanes at either end of a strip are halo, the twelve between them own outputs; a segment warms up on the 16 level-0 rows
+// above the first level-0 row it owns and runs 8 rows past the last: 8 (rows + 3) level-0 rows for `rows` level-3 rows.
+// Borders.  Columns: a lane at an image edge permutes the bytes of its extended row (v_perm with selectors computed once per
+// lane: the out-of-image positions read the reflected column of THAT level, identity everywhere else).  Rows: level 0 is
+// reflected at the loads; the rings of the levels 1 and 2 substitute the reflected rows of their level when the first / last
+// row of the next level is formed (pd_vfix).
+// Block -> (image, four jobs): the jobs of ONE image get block ids that are congruent modulo 8 (blocks b and b + 8 share an
+// XCD: the halo rows and columns that neighbouring jobs read twice come from that XCD's L2).
+#define P3_HALO 2              // halo lanes at either end of a strip
+#define P3_OWN 12              // lanes of a 16-lane strip that own outputs
+#define P3_SEG_ROWS 8          // level-3 rows of a segment in a launch that fills the device (measured: DESIGN.md section 6)
 struct Pyr3Job { const uint8_t *src; uint8_t *d1, *d2, *d3; int w0, h0; };
 
 namespace {
-constexpr int P3_R2H = 2 * P3_TH + 4, P3_R1H = 2 * P3_R2H + 4, P3_R0H = 2 * P3_R1H + 4;      // 20, 44, 92 rows
-constexpr int P3_P2W = 2 * P3_TW + 8, P3_P1W = 2 * (2 * P3_TW + 4) + 8;                        // 40, 80 plane columns
-constexpr int P3_P1S = P3_P1W + 8, P3_P2S = P3_P2W + 8;                                        // byte-plane row strides (4 B pad in front, 4 behind)
 typedef uint32_t __attribute__((aligned(1))) pd_u32u;
+typedef uint16_t __attribute__((aligned(1))) pd_u16u;
+typedef unsigned long long __attribute__((aligned(1))) pd_u64u;
+// the images live in global memory: typed so, a uniform base and a 32-bit lane offset make one global_load / global_store
+typedef const __attribute__((address_space(1))) pd_u64u *pd_gld64;
+typedef __attribute__((address_space(1))) pd_u32u *pd_gst32;
+typedef __attribute__((address_space(1))) pd_u16u *pd_gst16;
+typedef __attribute__((address_space(1))) uint8_t *pd_gst8;
 
-// four neighbouring horizontal [1 4 6 4 1] sums from eleven consecutive pixels b0 .. b10 (three dwords): outputs at b2, b4, b6, b8
-__device__ __forceinline__ uint2 pd_h4(uint32_t w0, uint32_t w1, uint32_t w2) {
-    const int b0 = w0 & 255u, b1 = (w0 >> 8) & 255u, b2 = (w0 >> 16) & 255u, b3 = w0 >> 24, b4 = w1 & 255u, b5 = (w1 >> 8) & 255u,
-              b6 = (w1 >> 16) & 255u, b7 = w1 >> 24, b8 = w2 & 255u, b9 = (w2 >> 8) & 255u, b10 = (w2 >> 16) & 255u;
-    const uint32_t h0 = (uint32_t)(b0 + 4 * b1 + 6 * b2 + 4 * b3 + b4), h1 = (uint32_t)(b2 + 4 * b3 + 6 * b4 + 4 * b5 + b6);
-    const uint32_t h2 = (uint32_t)(b4 + 4 * b5 + 6 * b6 + 4 * b7 + b8), h3 = (uint32_t)(b6 + 4 * b7 + 6 * b8 + 4 * b9 + b10);
+template <int CTRL> __device__ __forceinline__ uint32_t pd_dpp0(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true); }
+__device__ __forceinline__ uint32_t pd_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
+
+// four neighbouring horizontal [1 4 6 4 1] sums of the extended row e[-2 .. 8] (dwords e0 = e[-2 .. 1], e1 = e[2 .. 5],
+// e2 = e[6 .. 8]): outputs centred on e[0], e[2], e[4], e[6], two per register in 16-bit lanes (a sum is below 2^12)
+__device__ __forceinline__ uint2 pd_h4(uint32_t e0, uint32_t e1, uint32_t e2) {
+    const uint32_t h0 = pd_dot4(e0, 0x04060401u, e1 & 255u), h1 = pd_dot4(e0, 0x04010000u, pd_dot4(e1, 0x00010406u, 0u));
+    const uint32_t h2 = pd_dot4(e1, 0x04060401u, e2 & 255u), h3 = pd_dot4(e1, 0x04010000u, pd_dot4(e2, 0x00010406u, 0u));
     uint2 o; o.x = h0 | (h1 << 16); o.y = h2 | (h3 << 16);
     return o;
 }
-// four neighbouring output pixels from five rows of horizontal sums (two columns per register in 16-bit lanes:
-// s + 128 <= 16 * 16 * 255 + 128 < 2^16, so the lanes never carry into each other)
-__device__ __forceinline__ uint32_t pd_v4(uint2 r0, uint2 r1, uint2 r2, uint2 r3, uint2 r4) {
-    const uint32_t lo = (r0.x + r4.x) + 4u * (r1.x + r3.x) + 6u * r2.x + 0x00800080u;
-    const uint32_t hi = (r0.y + r4.y) + 4u * (r1.y + r3.y) + 6u * r2.y + 0x00800080u;
-    return ((lo >> 8) & 255u) | ((lo >> 24) << 8) | (((hi >> 8) & 255u) << 16) | ((hi >> 24) << 24);
+// vertical [1 4 6 4 1] of five rows of horizontal sums, both 16-bit lanes at once, rounded: the two output pixels are the bytes
+// 1 and 3 of the result (s + 128 <= 16 * 16 * 255 + 128 < 2^16, so the lanes never carry into each other)
+__device__ __forceinline__ uint32_t pd_v2(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t r4) {
+    return (r0 + r4 + 0x00800080u) + ((r1 + r2 + r3) << 2) + (r2 << 1);
 }
-// store the (up to four) pixels of a group that lie inside the image row of width w
-__device__ __forceinline__ void pd_store4(uint8_t *row, int x, int w, uint32_t px) {
-    if (x + 3 < w) *reinterpret_cast<pd_u32u *>(row + x) = px;
-    else for (int k = 0; x + k < w; ++k) row[x + k] = (uint8_t)(px >> (8 * k));
+// store the n (1 .. 4) pixels of a group that lie inside the image row; the offset is that of the first pixel in its level
+__device__ __forceinline__ void pd_store4(uint8_t *lvl, uint32_t off, int n, uint32_t px) {
+    if (n >= 4) { *(pd_gst32)(lvl + off) = px; return; }
+    *(pd_gst8)(lvl + off) = (uint8_t)px;
+    if (n >= 2) *(pd_gst8)(lvl + off + 1u) = (uint8_t)(px >> 8);
+    if (n >= 3) *(pd_gst8)(lvl + off + 2u) = (uint8_t)(px >> 16);
 }
-// BORDER_REFLECT_101 of the next level: the pixels at -2, -1, n, n + 1 of a level are copies of those at 2, 1, n - 2, n - 3.
-// plane(row, col) addresses a byte plane whose (0, 0) is the pixel (y_base, x_base); rows x cols plane positions.
-__device__ __forceinline__ void pd_fill_halo(uint8_t *plane, int stride, int rows, int cols, int y_base, int x_base, int w, int h, int tid) {
-    // (a) the four out-of-image columns, every row the next level can reach; (b) the four out-of-image rows over the in-image columns
-    for (int i = tid; i < 4 * rows; i += 256) {
-        const int r = i >> 2, q = i & 3;
-        const int x = q < 2 ? q - 2 : w + q - 2, y = y_base + r;
-        const int c = x - x_base;
-        if (c < 0 || c >= cols || y < -2 || y > h + 1) continue;
-        const int ys = reflect101(y, h) - y_base, xs = reflect101(x, w) - x_base;
-        if (ys < 0 || ys >= rows || xs < 0 || xs >= cols) continue;
-        plane[r * stride + 4 + c] = plane[ys * stride + 4 + xs];
+// v_perm selector of one dword of a lane's extended row (positions p0 .. p0 + 3; position p is the column cb - 2 + p of a level
+// of width w): a position outside the image reads the position of its BORDER_REFLECT_101 column when that lies in the two
+// source dwords (positions base .. base + 7; always, for a position a valid output needs), every other one keeps `ident`
+__device__ uint32_t pd_fix_sel(int cb, int w, int p0, int base, uint32_t ident) {
+    uint32_t sel = 0u;
+    for (int b = 0; b < 4; ++b) {
+        const int col = cb - 2 + p0 + b;
+        uint32_t s = (ident >> (8 * b)) & 255u;
+        if (col < 0 || col >= w) {
+            const int sp = reflect101(col, w) - cb + 2 - base;
+            if (sp >= 0 && sp < 8) s = (uint32_t)sp;
+        }
+        sel |= s << (8 * b);
     }
-    for (int i = tid; i < 4 * cols; i += 256) {
-        const int q = i / cols, c = i - q * cols;
-        const int y = q < 2 ? q - 2 : h + q - 2, x = x_base + c;
-        const int r = y - y_base;
-        if (r < 0 || r >= rows || x < 0 || x >= w) continue;
-        const int ys = reflect101(y, h) - y_base;
-        if (ys < 0 || ys >= rows) continue;
-        plane[r * stride + 4 + c] = plane[ys * stride + 4 + c];
-    }
+    return sel;
+}
+// the five ring rows a .. e = rows 2 yd - 2 .. 2 yd + 2 of a level of height hs, for the row yd of the next level: rows outside
+// the image are replaced by their BORDER_REFLECT_101 rows (only the first and the last row of the next level reach outside)
+__device__ __forceinline__ void pd_vfix(uint32_t &a, uint32_t &b, uint32_t c, uint32_t &d, uint32_t &e, int yd, int hs) {
+    if (2 * yd + 1 == hs) { e = hs == 1 ? c : a; d = hs == 1 ? c : b; }       // rows hs, hs + 1 -> hs - 2, hs - 3
+    else if (2 * yd + 2 == hs) e = c;                                          // row hs -> hs - 2
+    if (yd == 0) { a = e; b = d; }                                             // rows -2, -1 -> 2, 1
 }
 }  // namespace
 
-__global__ __launch_bounds__(256) void k_pyr_down3(const Pyr3Job *jobs, int n_jobs, int tiles_x, int tiles_y) {
-    // block -> (image, tile): the tiles of ONE image get ids congruent modulo 8 (blocks b and b + 8 share an XCD, speed only)
-    const int tiles = tiles_x * tiles_y;
-    const int bx = blockIdx.x & 7, bq = blockIdx.x >> 3;
-    const int ji = bx + 8 * (bq / tiles), tile = bq - (bq / tiles) * tiles;
+__global__ __launch_bounds__(64) void k_pyr_down3(const Pyr3Job *jobs, int n_jobs, int strips, int seg3, int waves) {
+    const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
+    const int ji = xcd + 8 * (qb / waves), wi = qb - (qb / waves) * waves;
     if (ji >= n_jobs) return;
     const Pyr3Job job = jobs[ji];
     const int w0 = job.w0, h0 = job.h0, w1 = (w0 + 1) >> 1, h1 = (h0 + 1) >> 1, w2 = (w1 + 1) >> 1, h2 = (h1 + 1) >> 1, w3 = (w2 + 1) >> 1, h3 = (h2 + 1) >> 1;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int x3_0 = tx * P3_TW, y3_0 = ty * P3_TH;
-    if (x3_0 >= w3 || y3_0 >= h3) return;
-    __shared__ __attribute__((aligned(16))) uint16_t s_h0[P3_R0H][P3_P1W];     // horizontal sums of level 0 (rows: level-0 rows, columns: level-1 plane columns)
-    __shared__ __attribute__((aligned(16))) uint8_t s_p1[P3_R1H][P3_P1S];      // level-1 region
-    __shared__ __attribute__((aligned(16))) uint16_t s_h1[P3_R1H][P3_P2W];
-    __shared__ __attribute__((aligned(16))) uint8_t s_p2[P3_R2H][P3_P2S];      // level-2 region
-    __shared__ __attribute__((aligned(16))) uint16_t s_h2[P3_R2H][P3_TW];
-    const int tid = threadIdx.x;
-    const int x1b = 4 * x3_0 - 8, y1b = 4 * y3_0 - 6, y0b = 8 * y3_0 - 14;       // pixel of plane column / row 0
-    const int x2b = 2 * x3_0 - 4, y2b = 2 * y3_0 - 2;
-    // ---- A: horizontal pass over the level-0 rows this tile needs.  A group is four level-1 columns = eleven source pixels.
-    //      Groups whose pixels all lie inside the image row take whole (unaligned) dwords; the groups at the left / right image
-    //      border reflect every tap and run in a loop of their own (a wavefront does not pay both paths).
-    {
-        const int pa = max(0, -y0b), pb = min(P3_R0H, h0 - y0b);                 // plane rows inside the image
-        constexpr int NG = P3_P1W / 4;
-        // fast groups: x1f >= 1 (first tap 2 x1f - 2 >= 0), x1f + 3 < w1, last byte read 2 x1f + 9 < w0
-        int ga = (1 - x1b + 3) >> 2; ga = ga < 0 ? 0 : ga;
-        int gb = min(min((w1 - 4 - x1b) >> 2, (w0 - 10 - 2 * x1b) >> 3) + 1, NG);
-        if (w1 - 4 - x1b < 0 || w0 - 10 - 2 * x1b < 0) gb = 0;
-        if (gb < ga) gb = ga;
-        const int ng = gb - ga, n_fast = (pb - pa) * ng;
-        const unsigned inv = ng > 0 ? (65536u + (unsigned)ng - 1u) / (unsigned)ng : 0u;      // idx / ng for idx * ng < 2^16
-        // every load of the tile is issued before the first sum is formed (a thread has at most MAXIT groups: 24 dwords in
-        // flight per lane; with the loads inside the loop a workgroup paid the memory latency once per iteration: 145 us per
-        // 192-stream launch alone against ... with them hoisted)
-        constexpr int MAXIT = (P3_R0H * NG + 255) / 256;
-        uint32_t la[MAXIT], lb[MAXIT], lc[MAXIT];
+    const int lane = threadIdx.x, r = lane & 15;
+    const int sj = 4 * wi + (lane >> 4);
+    const int seg = sj / strips, strip = sj - seg * strips;
+    const int x3 = P3_OWN * strip - P3_HALO + r;                 // the lane's level-3 column
+    const int y3a = seg3 * seg, y3b = min(y3a + seg3, h3);       // the segment's level-3 rows
+    const bool job_on = P3_OWN * strip < w3 && y3a < h3;
+    if (!__any(job_on)) return;
+    const bool own = job_on && r >= P3_HALO && r < P3_HALO + P3_OWN && x3 < w3;
+    // ---- byte selectors of the extended rows (identity except in the lanes at the left / right image edge of a level)
+    uint32_t sa0 = 0x03020100u, sa1 = 0x07060504u, sa2 = 0x07060504u, sb0 = 0x03020100u, sb1 = 0x07060504u, sc0 = 0x03020100u, sc1 = 0x07060504u;
+    if (x3 >= 0 && 8 * x3 < w0 && (x3 == 0 || 8 * x3 + 8 >= w0 || 4 * x3 + 4 >= w1 || 2 * x3 + 2 >= w2)) {
+        sa0 = pd_fix_sel(8 * x3, w0, 0, 0, sa0); sa1 = pd_fix_sel(8 * x3, w0, 4, 0, sa1); sa2 = pd_fix_sel(8 * x3, w0, 8, 4, sa2);
+        sb0 = pd_fix_sel(4 * x3, w1, 0, 0, sb0); sb1 = pd_fix_sel(4 * x3, w1, 4, 0, sb1);
+        sc0 = pd_fix_sel(2 * x3, w2, 0, 0, sc0); sc1 = pd_fix_sel(2 * x3, w2, 4, 0, sc1);
+    }
+    // ---- level-0 loads: eight bytes at the lane's first column.  A lane whose eight columns reach past the row loads the last
+    // eight bytes of the row and shifts (the bytes past the edge are replaced through sa*); lanes outside the image read
+    // clamped addresses, their values reach no valid output.  Images narrower than eight pixels load the eight bytes that end
+    // with the image at the latest (an image holds at least eight bytes).
+    const int c0 = min(max(8 * x3, 0), w0 - 1), cl = max(min(c0, w0 - 8), 0);
+    const int sh0 = 8 * (c0 - cl), k0 = 2 * (h0 - 1);
+    const uint32_t last8 = (uint32_t)max(w0 * h0 - 8, 0);
+    auto load = [&](int s) -> uint2 {
+        int y = max(s, -s);
+        y = max(min(y, k0 - y), 0);                              // BORDER_REFLECT_101 of the rows a valid output needs, clamped
+        const uint32_t a = (uint32_t)y * (uint32_t)w0 + (uint32_t)cl, ac = min(a, last8);     // (a <= last8 unless w0 < 8)
+        const int sh = sh0 + 8 * (int)(a - ac);
+        const unsigned long long q = *(pd_gld64)(job.src + ac) >> sh;
+        uint2 o; o.x = (uint32_t)q; o.y = (uint32_t)(q >> 32);
+        return o;
+    };
+    // ---- the march: step p of iteration `it` takes the level-0 row 8 t + p, t = y3a - 2 + it
+    uint2 R0[5];
+    uint32_t R1[5], R2[5];
 #pragma unroll
-        for (int it = 0; it < MAXIT; ++it) {
-            const int idx = tid + 256 * it;
-            la[it] = lb[it] = lc[it] = 0u;
-            if (idx < n_fast) {
-                const int pr = (int)(((unsigned)idx * inv) >> 16), g = ga + idx - pr * ng, p = pa + pr;
-                const uint8_t *q = job.src + (size_t)(y0b + p) * w0 + (2 * (x1b + 4 * g) - 2);
-                la[it] = *reinterpret_cast<const pd_u32u *>(q); lb[it] = *reinterpret_cast<const pd_u32u *>(q + 4); lc[it] = *reinterpret_cast<const pd_u32u *>(q + 8);
+    for (int k = 0; k < 5; ++k) { R0[k].x = R0[k].y = 0u; R1[k] = R2[k] = 0u; }
+    int t = y3a - 2;
+    uint2 q[4];                                                  // rows are loaded four steps before they are used
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = load(8 * t + k);
+    const int y1a = 4 * y3a, y1b = min(4 * (y3a + seg3), h1), y2a = 2 * y3a, y2b = min(2 * (y3a + seg3), h2);
+    const int n1 = own ? min(w1 - 4 * x3, 4) : 0, n2 = own ? min(w2 - 2 * x3, 2) : 0;      // pixels of the lane inside a level-1 / level-2 row
+#pragma unroll 1
+    for (int it = 0; it < seg3 + 3; ++it, ++t) {
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+            const uint2 px = q[p & 3];
+            q[p & 3] = load(8 * t + p + 4);
+            // extended row e[-2 .. 8] of level 0 and its four horizontal sums
+            const uint32_t lf = pd_dpp0<0x111>(px.y), rt = pd_dpp0<0x101>(px.x);
+            const uint32_t e0 = __builtin_amdgcn_alignbyte(px.x, lf, 2), e1 = __builtin_amdgcn_alignbyte(px.y, px.x, 2), e2 = __builtin_amdgcn_alignbyte(rt, px.y, 2);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) R0[k] = R0[k + 1];
+            R0[4] = pd_h4(__builtin_amdgcn_perm(e1, e0, sa0), __builtin_amdgcn_perm(e1, e0, sa1), __builtin_amdgcn_perm(e2, e1, sa2));
+            if (p & 1) continue;
+            // ---- level-1 row y1 = (8 t + p) / 2 - 1: four pixels per lane
+            const int y1 = 4 * t + p / 2 - 1;
+            const uint32_t p1 = __builtin_amdgcn_perm(pd_v2(R0[0].y, R0[1].y, R0[2].y, R0[3].y, R0[4].y), pd_v2(R0[0].x, R0[1].x, R0[2].x, R0[3].x, R0[4].x), 0x07050301u);
+            if (n1 > 0 && y1 >= y1a && y1 < y1b) pd_store4(job.d1, (uint32_t)(y1 * w1 + 4 * x3), n1, p1);
+            {
+                const uint32_t l1 = pd_dpp0<0x111>(p1), r1 = pd_dpp0<0x101>(p1);
+                const uint32_t u0 = __builtin_amdgcn_alignbyte(p1, l1, 2), u1 = __builtin_amdgcn_alignbyte(r1, p1, 2);
+                const uint32_t g0 = __builtin_amdgcn_perm(u1, u0, sb0), g1 = __builtin_amdgcn_perm(u1, u0, sb1);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) R1[k] = R1[k + 1];
+                R1[4] = pd_dot4(g0, 0x04060401u, g1 & 255u) | (pd_dot4(g0, 0x04010000u, pd_dot4(g1, 0x00010406u, 0u)) << 16);
             }
-        }
-#pragma unroll
-        for (int it = 0; it < MAXIT; ++it) {
-            const int idx = tid + 256 * it;
-            if (idx < n_fast) {
-                const int pr = (int)(((unsigned)idx * inv) >> 16), g = ga + idx - pr * ng, p = pa + pr;
-                *reinterpret_cast<uint2 *>(&s_h0[p][4 * g]) = pd_h4(la[it], lb[it], lc[it]);
+            if (p != 2 && p != 6) continue;
+            // ---- level-2 row y2 = y1 / 2 - 1: two pixels per lane (the low half of p2)
+            const int y2 = 2 * t - 1 + (p == 6);
+            uint32_t p2;
+            {
+                uint32_t a = R1[0], b = R1[1], d = R1[3], e = R1[4];
+                pd_vfix(a, b, R1[2], d, e, y2, h1);
+                p2 = __builtin_amdgcn_perm(0u, pd_v2(a, b, R1[2], d, e), 0x0c0c0301u);
             }
-        }
-        const int n_edge = NG - ng, n_slow = (pb - pa) * n_edge;
-        for (int idx = tid; idx < n_slow; idx += 256) {
-            const int pr = idx / n_edge, e = idx - pr * n_edge, g = e < ga ? e : gb + (e - ga), p = pa + pr;
-            const uint8_t *row = job.src + (size_t)(y0b + p) * w0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int x1 = x1b + 4 * g + j;
-                if (x1 < 0 || x1 >= w1) continue;
-                const int c = 2 * x1;
-                s_h0[p][4 * g + j] = (uint16_t)(row[reflect101(c - 2, w0)] + 4 * row[reflect101(c - 1, w0)] + 6 * row[reflect101(c, w0)] +
-                                                4 * row[reflect101(c + 1, w0)] + row[reflect101(c + 2, w0)]);
+            if (n2 > 0 && y2 >= y2a && y2 < y2b) {
+                const uint32_t o = (uint32_t)(y2 * w2 + 2 * x3);
+                if (n2 == 2) *(pd_gst16)(job.d2 + o) = (uint16_t)p2; else *(pd_gst8)(job.d2 + o) = (uint8_t)p2;
             }
-        }
-    }
-    __syncthreads();
-    // ---- B: vertical pass -> level 1 (in-image rows of the region), into the plane and, for the pixels this tile owns, to HBM
-    {
-        const int ra = max(0, -y1b), rb = min(P3_R1H, h1 - y1b);
-        constexpr int NG = P3_P1W / 4;
-        const int n = (rb - ra) * NG;
-        for (int idx = tid; idx < n; idx += 256) {
-            const int rr = idx / NG, g = idx - rr * NG, r = ra + rr;
-            const int y1 = y1b + r, x1 = x1b + 4 * g;
-            if (x1 + 3 < 0 || x1 >= w1) continue;
-            uint2 v[5];
+            {
+                const uint32_t l2 = pd_dpp0<0x111>(p2), r2 = pd_dpp0<0x101>(p2);
+                const uint32_t u0 = __builtin_amdgcn_perm(p2, l2, 0x05040100u);              // e[-2 .. 1]; r2 = e[2] in its byte 0
+                const uint32_t g0 = __builtin_amdgcn_perm(r2, u0, sc0), g1 = __builtin_amdgcn_perm(r2, u0, sc1);
 #pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int p = min(max(reflect101(2 * y1 - 2 + k, h0) - y0b, 0), P3_R0H - 1);
-                v[k] = *reinterpret_cast<const uint2 *>(&s_h0[p][4 * g]);
+                for (int k = 0; k < 4; ++k) R2[k] = R2[k + 1];
+                R2[4] = pd_dot4(g0, 0x04060401u, g1 & 255u);
             }
-            const uint32_t px = pd_v4(v[0], v[1], v[2], v[3], v[4]);
-            *reinterpret_cast<uint32_t *>(&s_p1[r][4 + 4 * g]) = px;
-            if (r >= 6 && r < 6 + 4 * P3_TH && g >= 2 && g < 2 + P3_TW && x1 >= 0) pd_store4(job.d1 + (size_t)y1 * w1, x1, w1, px);
-        }
-    }
-    __syncthreads();
-    const bool edge1 = x1b < 0 || y1b < 0 || x1b + P3_P1W > w1 || y1b + P3_R1H > h1;      // the region reaches past the level-1 image
-    if (edge1) { pd_fill_halo(&s_p1[0][0], P3_P1S, P3_R1H, P3_P1W, y1b, x1b, w1, h1, tid); __syncthreads(); }
-    // ---- C: horizontal pass over the level-1 region (rows -2 .. h1 + 1 of the image that the plane holds)
-    {
-        constexpr int NG = P3_P2W / 4;
-        const int ra = max(0, -2 - y1b), rb = min(P3_R1H, h1 + 2 - y1b);
-        const int n = (rb - ra) * NG;
-        for (int idx = tid; idx < n; idx += 256) {
-            const int rr = idx / NG, g = idx - rr * NG, r = ra + rr;
-            // the group's eleven pixels start at plane column 8 g - 2: bytes 8 g + 2 .. of the padded row
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(&s_p1[r][8 * g]);
-            const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-            *reinterpret_cast<uint2 *>(&s_h1[r][4 * g]) = pd_h4(__builtin_amdgcn_alignbyte(d1, d0, 2), __builtin_amdgcn_alignbyte(d2, d1, 2), __builtin_amdgcn_alignbyte(d3, d2, 2));
-        }
-    }
-    __syncthreads();
-    // ---- D: vertical pass -> level 2
-    {
-        constexpr int NG = P3_P2W / 4;
-        const int ra = max(0, -y2b), rb = min(P3_R2H, h2 - y2b);
-        const int n = (rb - ra) * NG;
-        for (int idx = tid; idx < n; idx += 256) {
-            const int rr = idx / NG, g = idx - rr * NG, r = ra + rr;
-            const int y2 = y2b + r, x2 = x2b + 4 * g;
-            if (x2 + 3 < 0 || x2 >= w2) continue;
-            uint2 v[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) v[k] = *reinterpret_cast<const uint2 *>(&s_h1[2 * r + k][4 * g]);      // level-1 row 2 y2 - 2 + k = plane row 2 r + k
-            const uint32_t px = pd_v4(v[0], v[1], v[2], v[3], v[4]);
-            *reinterpret_cast<uint32_t *>(&s_p2[r][4 + 4 * g]) = px;
-            if (r >= 2 && r < 2 + 2 * P3_TH && g >= 1 && g < 1 + P3_TW / 2 && x2 >= 0) pd_store4(job.d2 + (size_t)y2 * w2, x2, w2, px);
-        }
-    }
-    __syncthreads();
-    const bool edge2 = x2b < 0 || y2b < 0 || x2b + P3_P2W > w2 || y2b + P3_R2H > h2;
-    if (edge2) { pd_fill_halo(&s_p2[0][0], P3_P2S, P3_R2H, P3_P2W, y2b, x2b, w2, h2, tid); __syncthreads(); }
-    // ---- E: horizontal pass over the level-2 region
-    {
-        constexpr int NG = P3_TW / 4;
-        const int ra = max(0, -2 - y2b), rb = min(P3_R2H, h2 + 2 - y2b);
-        const int n = (rb - ra) * NG;
-        for (int idx = tid; idx < n; idx += 256) {
-            const int rr = idx / NG, g = idx - rr * NG, r = ra + rr;
-            // level-3 column x3_0 + 4 g: first tap at level-2 pixel 2 x3_0 + 8 g - 2 = plane column 8 g + 2
-            const uint32_t *q = reinterpret_cast<const uint32_t *>(&s_p2[r][4 + 8 * g]);
-            const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3];
-            *reinterpret_cast<uint2 *>(&s_h2[r][4 * g]) = pd_h4(__builtin_amdgcn_alignbyte(d1, d0, 2), __builtin_amdgcn_alignbyte(d2, d1, 2), __builtin_amdgcn_alignbyte(d3, d2, 2));
-        }
-    }
-    __syncthreads();
-    // ---- F: vertical pass -> level 3 (every pixel of the tile is owned)
-    {
-        constexpr int NG = P3_TW / 4;
-        const int rb = min(P3_TH, h3 - y3_0);
-        const int n = rb * NG;
-        for (int idx = tid; idx < n; idx += 256) {
-            const int r = idx / NG, g = idx - r * NG;
-            const int x3 = x3_0 + 4 * g;
-            if (x3 >= w3) continue;
-            uint2 v[5];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) v[k] = *reinterpret_cast<const uint2 *>(&s_h2[2 * r + k][4 * g]);
-            pd_store4(job.d3 + (size_t)(y3_0 + r) * w3, x3, w3, pd_v4(v[0], v[1], v[2], v[3], v[4]));
+            if (p != 6) continue;
+            // ---- level-3 row y3 = y2 / 2 - 1: one pixel per lane
+            const int y3 = t - 1;
+            uint32_t a = R2[0], b = R2[1], d = R2[3], e = R2[4];
+            pd_vfix(a, b, R2[2], d, e, y3, h2);
+            const uint32_t p3 = (((a + e) + 4u * (b + d) + 6u * R2[2] + 128u) >> 8) & 255u;
+            if (own && y3 >= y3a && y3 < y3b) *(pd_gst8)(job.d3 + (uint32_t)(y3 * w3 + x3)) = (uint8_t)p3;
         }
     }
 }
 
 extern "C" void fe_launch_pyr_down3(const Pyr3Job *jobs_dev, int n_jobs, int max_w0, int max_h0, hipStream_t st) {
     const int w3 = (((max_w0 + 1) / 2 + 1) / 2 + 1) / 2, h3 = (((max_h0 + 1) / 2 + 1) / 2 + 1) / 2;
-    const int tiles_x = (w3 + P3_TW - 1) / P3_TW, tiles_y = (h3 + P3_TH - 1) / P3_TH;
-    hipLaunchKernelGGL(k_pyr_down3, dim3(8 * ((n_jobs + 7) / 8) * tiles_x * tiles_y), dim3(256), 0, st, jobs_dev, n_jobs, tiles_x, tiles_y);
+    if (n_jobs <= 0 || w3 <= 0 || h3 <= 0) return;
+    const int strips = (w3 + P3_OWN - 1) / P3_OWN;
+    // level-3 rows per segment: long segments pay the 24 warm-up and run-out rows of level 0 less often, short ones give more
+    // wavefronts (the 192-stream launch: 67-70 us with 8 rows = 6 k wavefronts, 79-80 us with 16); the segments of a launch are
+    // made equally long
+    int target = P3_SEG_ROWS;
+    while (target > 4 && (long long)n_jobs * strips * ((h3 + target - 1) / target) / 4 < 2048) target /= 2;
+    const int segs = (h3 + target - 1) / target, seg3 = (h3 + segs - 1) / segs;
+    const int waves = (strips * segs + 3) / 4;
+    hipLaunchKernelGGL(k_pyr_down3, dim3(8 * ((n_jobs + 7) / 8) * waves), dim3(64), 0, st, jobs_dev, n_jobs, strips, seg3, waves);
 }
 
 // ------------------------------------------------------------------------------------------ detector
@@ -305,10 +270,10 @@ __device__ __forceinline__ void det_hsum(int P01, int P23, int p0, int p2, int H
 
 struct DetPix { uint32_t lo, hi; };     // eight pixels of an image row: columns c - 4 .. c - 1 and c .. c + 3 of the lane's first column c
 
-// Gradient products dx*dx, dx*dy, dy*dy (central differences) of the lane's four columns in the row `mid`, and their
-// horizontal 8-sums.  The differences are formed two at a time in 16-bit lanes (byte permutes + packed subtract), the
-// products and their pair sums are 16-bit dot products: 64 instructions per row instead of 90 with 32-bit arithmetic.
-__device__ __forceinline__ void det_hrow(uint32_t up, DetPix mid, uint32_t dn, int Ha[4], int Hb[4], int Hc[4]) {
+// Gradient products dx*dx, dx*dy, dy*dy (central differences) of the lane's four columns in the row `mid`, in the form
+// det_hsum takes: P[4 i .. 4 i + 3] = P01, P23, p0, p2 of the product i.  The differences are formed two at a time in 16-bit
+// lanes (byte permutes + packed subtract), the products and their pair sums are 16-bit dot products.
+__device__ __forceinline__ void det_prod(uint32_t up, DetPix mid, uint32_t dn, int P[12]) {
     const uint32_t rn = (uint32_t)det_dpp0<0x101>((int)mid.hi);          // the pixels of lane r + 1 (its first one is needed)
     // pixels m0 .. m5 = columns c - 1 .. c + 4 as pairs of 16-bit lanes
     const uint32_t m01 = __builtin_amdgcn_perm(mid.hi, mid.lo, 0x0c040c03u);   // (lo.b3, hi.b0)
@@ -318,9 +283,17 @@ __device__ __forceinline__ void det_hrow(uint32_t up, DetPix mid, uint32_t dn, i
     const int E01 = det_pksub(__builtin_amdgcn_perm(0u, dn, 0x0c010c00u), __builtin_amdgcn_perm(0u, up, 0x0c010c00u));
     const int E23 = det_pksub(__builtin_amdgcn_perm(0u, dn, 0x0c030c02u), __builtin_amdgcn_perm(0u, up, 0x0c030c02u));
     const int D0 = D01 & 0xffff, D2 = D23 & 0xffff, E0 = E01 & 0xffff, E2 = E23 & 0xffff;   // (d, 0): picks the product of the even column
-    det_hsum(det_dot2(D01, D01), det_dot2(D23, D23), det_dot2(D0, D01), det_dot2(D2, D23), Ha);
-    det_hsum(det_dot2(D01, E01), det_dot2(D23, E23), det_dot2(D0, E01), det_dot2(D2, E23), Hb);
-    det_hsum(det_dot2(E01, E01), det_dot2(E23, E23), det_dot2(E0, E01), det_dot2(E2, E23), Hc);
+    P[0] = det_dot2(D01, D01); P[1] = det_dot2(D23, D23); P[2] = det_dot2(D0, D01); P[3] = det_dot2(D2, D23);
+    P[4] = det_dot2(D01, E01); P[5] = det_dot2(D23, E23); P[6] = det_dot2(D0, E01); P[7] = det_dot2(D2, E23);
+    P[8] = det_dot2(E01, E01); P[9] = det_dot2(E23, E23); P[10] = det_dot2(E0, E01); P[11] = det_dot2(E2, E23);
+}
+// V += the horizontal 8-sums of the twelve values P (the products of a row, or the difference of the products of two rows:
+// the sums are linear and every term is an integer far below 2^31)
+__device__ __forceinline__ void det_vadd(const int P[12], int Va[4], int Vb[4], int Vc[4]) {
+    int Ha[4], Hb[4], Hc[4];
+    det_hsum(P[0], P[1], P[2], P[3], Ha); det_hsum(P[4], P[5], P[6], P[7], Hb); det_hsum(P[8], P[9], P[10], P[11], Hc);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { Va[j] += Ha[j]; Vb[j] += Hb[j]; Vc[j] += Hc[j]; }
 }
 
 // cg::CornerDetector per-cell maxima of cam0 level 0 (image_processor.cpp:259, :657): integer Shi-Tomasi score
@@ -330,9 +303,10 @@ __device__ __forceinline__ void det_hrow(uint32_t up, DetPix mid, uint32_t dn, i
 // per pixel, 124 VALU instructions per pixel, 304 us alone for 192 streams).  This version keeps everything in registers:
 // a 16-lane DPP row is a STRIP of 64 columns (four per lane, 56 outputs) marched down a SEGMENT of rows.  Per row a lane
 // loads eight bytes, forms its twelve products, the horizontal 8-sums come from the two lanes to the right (row_shl), and
-// the vertical 8-sums are running sums: the row entering the window is added, the row leaving it is RECOMPUTED from its
-// pixels (re-read through L1/L2) and subtracted - cheaper than a ring of eight rows of twelve sums in registers, and there
-// is no LDS, no barrier and no inter-wave traffic at all.  The exact score test needs the square root only for a pixel
+// the vertical 8-sums are running sums: the products of the row leaving the window are RECOMPUTED from its pixels (re-read
+// through L1/L2) and subtracted from those of the row entering it, and the horizontal sums of that one difference are
+// added (the sums are linear: one set of them per step, not two) - cheaper than a ring of eight rows of twelve sums in
+// registers, and there is no LDS, no barrier and no inter-wave traffic at all.  The exact score test needs the square root only for a pixel
 // that beats the best score its own column has seen in the current cell (disc < (a + c - best)^2 is decided first), so
 // after the first rows of a cell almost no pixel takes the expensive path.  At the bottom of a cell row the lanes of a
 // strip merge their keys with a segmented DPP max (runs of lanes in the same cell) and the first lane of each run issues
@@ -374,21 +348,21 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
         col_ok[j] = job_on && r < DS_LANES && x < W - DET_BORDER;
     }
     int Va[4] = {0, 0, 0, 0}, Vb[4] = {0, 0, 0, 0}, Vc[4] = {0, 0, 0, 0};
-    // ---- fill the window: product rows ys - 4 .. ys + 2
+    // ---- fill the window of the first output row: product rows ys - 4 .. ys + 3
     int pr = ys - 4;
     // (the rows are loaded two steps before they are used: e_nx / l_nx are in flight while a step computes)
     DetPix e_mid = load(pr), e_dn = load(pr + 1), e_nx = load(pr + 2);
     uint32_t e_up = load(pr - 1).hi;
 #pragma unroll 1
-    for (int k = 0; k < 7; ++k) {
+    for (int k = 0; k < 8; ++k) {
         const DetPix nx = load(pr + 3);
-        int Ha[4], Hb[4], Hc[4];
-        det_hrow(e_up, e_mid, e_dn.hi, Ha, Hb, Hc);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { Va[j] += Ha[j]; Vb[j] += Hb[j]; Vc[j] += Hc[j]; }
+        int P[12];
+        det_prod(e_up, e_mid, e_dn.hi, P);
+        det_vadd(P, Va, Vb, Vc);
         e_up = e_mid.hi; e_mid = e_dn; e_dn = e_nx; e_nx = nx; ++pr;
     }
-    // ---- steady state: the row pr enters, output row y = pr - 3, the row y - 4 leaves
+    // ---- steady state: output row y sees the rows y - 4 .. y + 3; then the row pr = y + 4 enters and the row y - 4 leaves in
+    // ONE set of horizontal sums, those of the difference of their products: V(y + 1) = V(y) + H(enter(y + 1) - leave(y))
     uint32_t l_up = load(ys - 5).hi;
     DetPix l_mid = load(ys - 4), l_dn = load(ys - 3), l_nx = load(ys - 2);
     int cy = ys / ch, yin = ys - cy * ch;
@@ -400,13 +374,6 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
         const int y = ys + k;
         const bool row_ok = y < y_end;
         const DetPix enx = load(pr + 3), lnx = load(y - 1);
-        {
-            int Ha[4], Hb[4], Hc[4];
-            det_hrow(e_up, e_mid, e_dn.hi, Ha, Hb, Hc);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { Va[j] += Ha[j]; Vb[j] += Hb[j]; Vc[j] += Hc[j]; }
-            e_up = e_mid.hi; e_mid = e_dn; e_dn = e_nx; e_nx = enx; ++pr;
-        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!(col_ok[j] && row_ok)) continue;
@@ -426,10 +393,13 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
             bk[j] = det_key(gen, score, (unsigned int)(yin * cw + xin[j]));
         }
         {
-            int Ha[4], Hb[4], Hc[4];
-            det_hrow(l_up, l_mid, l_dn.hi, Ha, Hb, Hc);
+            int Pe[12], Pl[12];
+            det_prod(e_up, e_mid, e_dn.hi, Pe);
+            det_prod(l_up, l_mid, l_dn.hi, Pl);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { Va[j] -= Ha[j]; Vb[j] -= Hb[j]; Vc[j] -= Hc[j]; }
+            for (int j = 0; j < 12; ++j) Pe[j] -= Pl[j];
+            det_vadd(Pe, Va, Vb, Vc);
+            e_up = e_mid.hi; e_mid = e_dn; e_dn = e_nx; e_nx = enx; ++pr;
             l_up = l_mid.hi; l_mid = l_dn; l_dn = l_nx; l_nx = lnx;
         }
         // ---- bottom of a cell row (or of the segment): merge the strip's keys per cell, one atomicMax per cell
