@@ -475,7 +475,8 @@ static int plan_stream(const mskf_ctx *ctx, const mskf_stream *s, const mskf_ekf
     L.o_gamma = align_up(L.o_dx + sizeof(double) * (size_t)E.ld, 16);
     L.o_pos = align_up(L.o_gamma + sizeof(double) * (size_t)a.n_feat, 16);
     L.o_rows = align_up(L.o_pos + sizeof(double) * 3 * (size_t)a.n_feat, 16);
-    L.o_status = L.o_rows + 32 + 32;           // rows_out (5 ints, padded to 32 bytes) + 3 position variances
+    static_assert(EKF_ROWS_COUNT * sizeof(int) <= 32, "rows_out fits its 32 bytes");
+    L.o_status = L.o_rows + 32 + 32;           // rows_out (EKF_ROWS_COUNT ints, padded to 32 bytes) + 3 position variances
     B.out_bytes = align_up(L.o_status + (size_t)a.n_feat, 64);
     B.any_pv_nofeat |= a.pos_var_out != nullptr && a.n_feat == 0;
     // (the first block is sized for what a stream of this configuration can stack, mskf_ekf_stream_init: growth is rare)
@@ -707,8 +708,8 @@ extern "C" int mskf_ekf_update_batch_end(mskf_ctx *ctx) {
         }
         std::memcpy(a.delta_x, hout + L.o_dx, sizeof(double) * (size_t)d);
         if (a.gamma) std::memcpy(a.gamma, hout + L.o_gamma, sizeof(double) * (size_t)a.n_feat);
-        *a.rows_out = ((const int *)(hout + L.o_rows))[0];
-        if (a.diag_out) { const int dg = ((const int *)(hout + L.o_rows))[3]; a.diag_out[0] = (dg & 4) ? 2 : (dg & 1); a.diag_out[1] = dg >> 8; }
+        *a.rows_out = ((const int *)(hout + L.o_rows))[EKF_ROWS_STACKED];
+        if (a.diag_out) ekf_diag_decode(((const int *)(hout + L.o_rows))[EKF_ROWS_DIAG], &a.diag_out[0], &a.diag_out[1]);
         std::memcpy(a.feat_status, hout + L.o_status, (size_t)a.n_feat);
         const double *po = (const double *)(hout + L.o_pos);
         for (int j = 0; j < a.n_feat; ++j)

@@ -12,15 +12,15 @@
 //     stacked row count, the end of the last stacked block (the K range of the Gram pass), the clones the stack touches
 //     (active columns) and the first feature behind the cap.  Integer work on a few hundred features: every workgroup gets
 //     the same answer, no workgroup waits for another.  ONE workgroup per stream (publish = true) also writes it down for
-//     the kernels that follow: rows_out[0..4], the active column list, and the gate bits / masks of the capped features.
+//     the kernels that follow: rows_out (EKF_ROWS_*), the active column list, and the gate bits / masks of the capped features.
 // All NT threads of the workgroup call it (256; 512 in k_ekf_tsqr).
 #pragma once
 #include "ekf_device.h"
 
 struct EkfCapResult {
-    int stacked;                  // rows_out[0]: rows of the stacked blocks
-    int end;                      // rows_out[1]: end of the last stacked block (rows beyond it carry nothing)
-    int na;                       // rows_out[2]: active columns = 6 x clones the stack touches
+    int stacked;                  // EKF_ROWS_STACKED: rows of the stacked blocks
+    int end;                      // EKF_ROWS_END: end of the last stacked block (rows beyond it carry nothing)
+    int na;                       // EKF_ROWS_NA: active columns = 6 x clones the stack touches
     unsigned long long clones;    // those clones (bit c)
 };
 
@@ -101,11 +101,11 @@ __device__ __forceinline__ EkfCapResult ekf_cap_local(const EkfStreamDev &S, boo
     if (publish) {
         for (int i = tid; i < R.na; i += NT) S.act[i] = ekf_act_column(R.clones, i);
         if (tid == 0) {
-            S.rows_out[0] = R.stacked;
-            S.rows_out[1] = R.end;       // rows beyond the last stacked block carry nothing: the Gram pass stops there
-            S.rows_out[2] = R.na;
-            S.rows_out[3] = 0;
-            S.rows_out[4] = R.na;        // rows of the compressed measurement (the factorisation kernel lowers it when nothing is compressed)
+            S.rows_out[EKF_ROWS_STACKED] = R.stacked;
+            S.rows_out[EKF_ROWS_END] = R.end;       // rows beyond the last stacked block carry nothing: the Gram pass stops there
+            S.rows_out[EKF_ROWS_NA] = R.na;
+            S.rows_out[EKF_ROWS_DIAG] = 0;
+            S.rows_out[EKF_ROWS_NK] = R.na;         // rows of the compressed measurement (the factorisation kernel lowers it when nothing is compressed)
         }
     }
     return R;

@@ -1,22 +1,13 @@
-// ekf_device.h — device-side descriptors of the MSCKF measurement-update kernels and, defined here and nowhere else, what the
-// host (mskf_capi_ekf.cpp) and the kernels must agree on: the limits a stream is routed by, the route bits, the mode predicates, the launchers.
+// ekf_device.h — device-side descriptors of the MSCKF measurement-update kernels and, defined here (the plain numbers: ekf_limits.h) and
+// nowhere else, what the host (mskf_capi_ekf.cpp) and the kernels must agree on: the limits a stream is routed by, the route bits, the
+// mode predicates, the rows_out record, the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../../include/mskf_hip.h"
+#include "ekf_limits.h"      // the limits, the compression modes and the rows_out record: plain C++, tested on the CPU
 
-#define EKF_IMU_DIM 21
 #define EKF_SLOTS 64          // feature workgroups per stream and launch (each loops over its features)
-
-// ---- kernel limits the host routes by
-#define MAX_CLONES_DEV 64         // largest clone window (mskf_ekf_cfg.max_cam_state_size): 4*64 = 256 block rows max per feature
-#define FEAT_WAVE_CLONES 4        // wave-per-feature class of the feature kernel: Jacobian observations per feature at most
-#define FEAT_SMALL_CLONES 16      // one-wavefront class: max(observations, triangulation clones) at most; above it the big class
-#define TRI_SMALL_CLONES 32       // the wave-per-feature variant triangulates over at most this many clones
-#define SU_MAX_NA 24              // k_ekf_small_update: active columns at most (four clones)
-#define MSKF_DIRECT_MAX_ROWS 6    // k_ekf_direct_update: rows of a caller-supplied measurement at most (mskf_ekf_direct_args.m)
-static_assert(FEAT_WAVE_CLONES <= FEAT_SMALL_CLONES && FEAT_SMALL_CLONES <= TRI_SMALL_CLONES && TRI_SMALL_CLONES <= MAX_CLONES_DEV, "size classes nest");
-static_assert(MAX_CLONES_DEV <= 64, "clone sets are 64-bit masks (EkfFeatDev::colmask, rowmask)");
 
 // ---- EkfStreamDev::route: which kernels handle a stream's update, decided per STREAM from its own features (never from
 // the rest of the batch, so a stream's arithmetic does not depend on its neighbours)
@@ -24,12 +15,6 @@ static_assert(MAX_CLONES_DEV <= 64, "clone sets are 64-bit masks (EkfFeatDev::co
 #define EKF_ROUTE_WAVE 2          // wave-per-feature class: every feature <= FEAT_WAVE_CLONES observations, triangulation <= TRI_SMALL_CLONES clones
 #define EKF_ROUTE_SMALL 4         // whole update in k_ekf_small_update (<= SU_MAX_NA active columns possible); the general kernels leave it alone
 enum { GM_GRAM = 0, GM_T = 1, GM_S2 = 2, GM_PUPD = 3 };      // ekf_launch_gemm's mode
-
-// ---- qr_mode (mskf_ekf_cfg.compression_mode): auto, Gram only, Householder always, the reference literally
-// (msckf_vio.cpp:795-821): Householder QR when the stack has more rows than columns, nothing otherwise.
-enum { EKF_QR_AUTO = 0, EKF_QR_GRAM = 1, EKF_QR_HOUSEHOLDER = 2, EKF_QR_REFERENCE = 3 };
-__host__ __device__ __forceinline__ bool ekf_mode_direct(int qr_mode, int stacked, int na) { return (qr_mode == EKF_QR_AUTO || qr_mode == EKF_QR_REFERENCE) && stacked <= na; }
-__host__ __device__ __forceinline__ bool ekf_mode_householder(int qr_mode) { return qr_mode == EKF_QR_HOUSEHOLDER || qr_mode == EKF_QR_REFERENCE; }
 
 // Per feature of one update (device copy of mskf_ekf_feature + row offset of its block)
 struct EkfFeatDev {
@@ -67,7 +52,7 @@ struct EkfStreamDev {
     double *T;                // na x (d+1) work: T = R P[act, :], then Y = L^-1 [T | Q^T r]
     double *S;                // (na+1)^2 work (compact): Gram matrix [H_act|r]^T [H_act|r], then its Cholesky factor L = R^T (+ the Q^T r row)
     double *W;                // na x na work (compact): S = T[:, act] R^T + sigma^2 I, then its Cholesky factor
-    int *act;                 // active columns of this update (the 6 columns of every clone a stacked feature observed), ascending; count in rows_out[2];
+    int *act;                 // active columns of this update (the 6 columns of every clone a stacked feature observed), ascending; count in rows_out[EKF_ROWS_NA];
                               // act + ld: indices of the stacked rows, in order, when the update is not compressed (2 ld ints in all)
     double *gate_S;           // EKF_SLOTS x (nmax x nmax)
     int nmax;                 // 4 * max_clones
@@ -82,12 +67,7 @@ struct EkfStreamDev {
                               // 3 the reference's own rule (Householder when rows > columns, uncompressed otherwise)
     const int *tri_idx;       // features that need triangulation (pair path: k_ekf_triangulate), n_tri of them
     int n_tri;
-    int *rows_out;            // [0] stacked rows, [1] last stacked row + 1 (K range of the Gram pass), [2] number of active columns,
-                              // [3] compression diagnostics: bit 0 = Householder TSQR used, bit 1 = the lambda prior of the Gram path
-                              //     would bias P by more than QR_BIAS_LIMIT (auto mode then re-does the compression as TSQR), bit 2 = no
-                              //     compression (stacked rows <= active columns: the stacked rows themselves are the measurement),
-                              //     bits 8.. = pivots of the Gram factor below 100 lambda (reported only)
-                              // [4] nk = rows of the compressed measurement = dimension of S: na, or rows_out[0] without compression
+    int *rows_out;            // EKF_ROWS_COUNT ints, slots EKF_ROWS_* (ekf_limits.h)
     // propagation / augmentation
     const double *PhiQ;       // n_steps x (2 x 21 x 21): Phi then Q   (generic form)
     const mskf_imu_step *imu_steps;   // or: n_steps compact IMU records, Phi/Q formed on the device

@@ -3,25 +3,34 @@
 //
 //  k_ekf_gemm   : 32x32 output tile per workgroup, v_mfma_f64_16x16x4_f64 (one 16x16 sub-tile per wave,
 //                 K staged through LDS 32 at a time, next stage prefetched into registers).  Modes:
-//                   GRAM  G  = [Hs|rs]^T [Hs|rs]          ((d+1)x(d+1), replaces the QR: G = R^T R, last row = (Q^T r)^T R)
+//                   GRAM  G  = [Hs|rs]^T [Hs|rs]          ((d+1)x(d+1): G = R^T R, last row = (Q^T r)^T R; Gram route only)
 //                   T     T  = R P,  R = L^T upper        (skips the zero half of R)
 //                   S2    S  = T R^T + sigma^2 I          (symmetric, lower computed and mirrored)
 //                   PUPD  P <- P - Y^T Y                  (symmetric)
-//  k_ekf_chol   : blocked (NB = 16) right-looking Cholesky in place, one workgroup per stream; the Gram
-//                 variant factors G + lambda I (lambda = 1e-14 d max diag: G is rank deficient and an unpivoted
-//                 factorisation of it is unstable) and carries the extra Q^T r row through the panel solves.
+//  k_ekf_tsqr   : Householder TSQR of the stacked rows, the row block in registers: the compression of compression_mode 2 and 3.
+//  k_ekf_chol_lds, k_ekf_chol : blocked (NB = 16) right-looking Cholesky, one workgroup per stream, of S (every route) and of the
+//                 Gram matrix (modes 0 and 1), on the packed copy in LDS or, beyond CHOL_LDS_MAX_ROWS rows, in place in global
+//                 memory; prologue, regularisation, diagnostics and epilogue are shared routines.  The Gram variant factors
+//                 G + lambda I and carries the extra Q^T r row along; in auto mode it re-does the compression as Householder
+//                 TSQR (tsqr_wide) when lambda would bias P.
 //  k_ekf_trsm   : Y = L^-1 [T | Q^T r] in place, one workgroup per 32-column strip and stream.
+//  k_ekf_small_update : the whole update of a stream with at most SU_MAX_NA active columns in one workgroup.
 //  (delta_x = Y^T w, w = column d of Y, is computed by extra workgroups of the PUPD GEMM launch)
 //
-//  All of them work on the ACTIVE columns of the update only (compact index i <-> column act[i], count rows_out[2],
-//  built by k_ekf_cap): the stacked Jacobian is zero in the 21 IMU columns and in the columns of clones that no
-//  stacked feature observed, and those columns add nothing to S, K or the downdate.  The pruning update (hundreds of
-//  features, but only the two clones being removed) thus factors 12 x 12 systems instead of 180 x 180.
+//  All of them work on the ACTIVE columns of the update only (compact index i <-> column act[i], count rows_out[EKF_ROWS_NA]):
+//  the stacked Jacobian is zero in the 21 IMU columns and in the columns of clones that no stacked feature observed, and those
+//  columns add nothing to S, K or the downdate.  The pruning update (hundreds of features, but only the two clones being
+//  removed) thus factors 12 x 12 systems instead of 180 x 180.  Which blocks are stacked, and with them the active columns, is
+//  worked out by the FIRST dense kernel of a stream's route (ekf_cap.h): k_ekf_gemm<GRAM>, k_ekf_tsqr when no stream of the
+//  batch needs a Gram matrix, or k_ekf_small_update.
 //
-// Why Gram + Cholesky instead of Householder QR: the update only needs R^T R = H^T H and R^T (Q^T r) =
-// H^T r; forming them is one GEMM-shaped pass over the stacked Jacobian (MFMA-friendly, fully parallel
-// over output tiles) instead of d sequential reflector applications.  H^T H is rank deficient (the 21
-// IMU columns of H are zero, unobserved clones, the gauge): the factorisation is regularised, see k_ekf_chol_lds.
+// How the stack is compressed (compression_mode, ekf_limits.h).  The default is mode 3, the reference's own rule
+// (msckf_vio.cpp:795-821): Householder QR when the stack has more rows than active columns (k_ekf_tsqr), nothing otherwise (the
+// stacked rows are the measurement).  Mode 2 is Householder always.  Modes 0 and 1 form the Gram matrix instead: the update
+// only needs R^T R = H^T H and R^T (Q^T r) = H^T r, one GEMM-shaped pass over the stack (MFMA-friendly, parallel over output
+// tiles) instead of d sequential reflector applications.  H^T H is rank deficient (unobserved directions, the gauge) and its
+// condition is the square of H's, so the factorisation is regularised (gram_regularise); mode 0 falls back to Householder where
+// that would show in P, mode 1 never does.
 #include <mutex>
 #include <type_traits>
 #include "ekf_device.h"
@@ -30,23 +39,24 @@
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
-// Gram + regularised Cholesky adds a prior lambda I to the stacked information H^T H / sigma^2: the posterior covariance
-// moves by about lambda max(P_aa) / sigma^2 relative.  Above this limit (or when the stack has no more rows than active
-// columns) the compression runs as Householder TSQR instead (tsqr_wide), which has no such term.
-#define QR_BIAS_LIMIT 1e-6
 // How a stream's stack is compressed is decided from ONE pair of numbers everywhere (the GRAM pass, the factorisation
-// kernels, the fused small update): st = rows_out[0], the rows actually stacked, and na = rows_out[2], the active columns.
-//   * st <= na (auto mode): the reference compresses nothing there (msckf_vio.cpp:818-821) and H^T H would be singular by
+// kernels, the fused small update): st = rows_out[EKF_ROWS_STACKED], the rows actually stacked, and na = rows_out[EKF_ROWS_NA],
+// the active columns.
+//   * st <= na (modes 0 and 3): the reference compresses nothing there (msckf_vio.cpp:818-821) and H^T H would be singular by
 //     construction, so neither the Gram pass nor any factorisation of the stack runs: the st stacked rows themselves are the
 //     measurement ("direct": R = H_act, st x na).  Blocks that were gated out leave gaps between the stacked rows (the last
-//     stacked row, rows_out[1], may lie far beyond na), so the rows are addressed through a compact list of their indices
-//     (rowidx, built by ekf_compress_entry behind the active-column list).
-//   * otherwise Gram + regularised Cholesky, re-done as Householder TSQR when the factorisation raises the bias flag (bit 1).
-// (the qr_mode predicates ekf_mode_direct / ekf_mode_householder: ekf_device.h)
-__device__ __forceinline__ bool ekf_direct_wanted(const EkfStreamDev &S) { return ekf_mode_direct(S.qr_mode, S.rows_out[0], S.rows_out[2]); }
+//     stacked row, rows_out[EKF_ROWS_END], may lie far beyond na), so the rows are addressed through a compact list of their
+//     indices (rowidx, built by ekf_compress_entry behind the active-column list).
+//   * otherwise Householder TSQR (modes 2 and 3), or Gram + regularised Cholesky, re-done as Householder TSQR in mode 0 when
+//     the factorisation raises the bias flag (ekf_mode_redo_householder).
+// (the qr_mode predicates: ekf_limits.h)
+__device__ __forceinline__ bool ekf_direct_wanted(const EkfStreamDev &S) { return ekf_mode_direct(S.qr_mode, S.rows_out[EKF_ROWS_STACKED], S.rows_out[EKF_ROWS_NA]); }
 __device__ __forceinline__ bool ekf_skip_gram(const EkfStreamDev &S) { return ekf_mode_householder(S.qr_mode) || ekf_direct_wanted(S); }
-// the stream's stacked rows are used uncompressed (set by the factorisation kernel): R = H_act (rows_out[1] x na, dense, rowmask-gathered)
-__device__ __forceinline__ bool ekf_direct(const EkfStreamDev &S) { return (S.rows_out[3] & 4) != 0; }
+// the stream's stacked rows are used uncompressed (set by the factorisation kernel): R = H_act (st x na, dense, rowmask-gathered)
+__device__ __forceinline__ bool ekf_direct(const EkfStreamDev &S) { return (S.rows_out[EKF_ROWS_DIAG] & EKF_DIAG_DIRECT) != 0; }
+// Does a stacked row of rowmask rm carry the compact column that belongs to `clone` (bit c = the six columns of clone c;
+// clone < 0: the residual column, which every stacked row carries)?  Nothing else of a row was ever written, and it is not read.
+__device__ __forceinline__ bool ekf_row_has(unsigned long long rm, int clone) { return clone < 0 ? rm != 0ULL : ((rm >> clone) & 1ULL) != 0ULL; }
 
 // Per-mode compile-time shape of op(A) op(B): TA: op(A)(i,k) = A[k*ld+i] (else A[i*ld+k]); B is always B[k*ld+j].
 // KMIN_I: op(A)(i,k) == 0 for k < i (R = L^T is upper triangular); KMIN_J: op(B)(k,j) == 0 for k < j.
@@ -56,7 +66,7 @@ template <> struct GemmTraits<GM_T>    { static constexpr bool TA = true,  SYM =
 template <> struct GemmTraits<GM_S2>   { static constexpr bool TA = false, SYM = true,  KMIN_I = false, KMIN_J = true;  };
 template <> struct GemmTraits<GM_PUPD> { static constexpr bool TA = true,  SYM = true,  KMIN_I = false, KMIN_J = false; };
 
-#define GT 32      // output tile edge
+#define GT EKF_GEMM_TILE      // output tile edge
 #ifndef GK
 #define GK 32      // K per LDS stage (64 measured slower: 49 vs 41 us per launch, the LDS footprint halves the workgroups per CU)
 #endif
@@ -93,13 +103,13 @@ __global__ __launch_bounds__(256) void k_ekf_gemm(const EkfStreamDev *streams) {
         cap = ekf_cap_local(S, blockIdx.x == 0);
         if (ekf_mode_householder(S.qr_mode) || ekf_mode_direct(S.qr_mode, cap.stacked, cap.na)) return;       // ekf_skip_gram, on this update's own numbers
     }
-    const int na = MODE == GM_GRAM ? cap.na : S.rows_out[2];                  // active columns (compact index i <-> column act[i])
+    const int na = MODE == GM_GRAM ? cap.na : S.rows_out[EKF_ROWS_NA];                  // active columns (compact index i <-> column act[i])
     const int *__restrict__ act = S.act;
     const double *__restrict__ A; const double *__restrict__ B; double *C;
     int M, N, K;
     double alpha = 1.0, beta = 0.0, diag_add = 0.0;
     if (MODE == GM_GRAM)      { A = S.Hs; B = S.Hs; C = S.S; M = N = na + 1; K = cap.end; }       // G_c = [H_act|r]^T [H_act|r]
-    const int nk = MODE == GM_GRAM ? 0 : S.rows_out[4];                                               // rows of the compressed measurement
+    const int nk = MODE == GM_GRAM ? 0 : S.rows_out[EKF_ROWS_NK];                                               // rows of the compressed measurement
     const bool direct = MODE != GM_GRAM && MODE != GM_PUPD && ekf_direct(S);                          // R = H_act itself (no compression)
     if (MODE == GM_T)         { A = direct ? S.Hs : S.S;  B = S.P;  C = S.T; M = nk; N = d; K = na; }   // T = R P[act, :]
     else if (MODE == GM_S2)   { A = S.T;  B = direct ? S.Hs : S.S;  C = S.W; M = N = nk; K = na; diag_add = S.sigma2; } // S = T[:, act] R^T + sigma^2 I
@@ -164,8 +174,7 @@ __global__ __launch_bounds__(256) void k_ekf_gemm(const EkfStreamDev *streams) {
                 double v = 0.0, w = 0.0;
                 if (gk < K) {
                     const unsigned long long rm = rowmask[gk];
-                    const bool onA = cloneA < 0 ? rm != 0ULL : ((rm >> cloneA) & 1ULL) != 0ULL;
-                    const bool onB = cloneB < 0 ? rm != 0ULL : ((rm >> cloneB) & 1ULL) != 0ULL;
+                    const bool onA = ekf_row_has(rm, cloneA), onB = ekf_row_has(rm, cloneB);
                     if (onA && i0 + lo < M) v = A[(size_t)gk * ld + colA];
                     if (onB && j0 + lo < N) w = B[(size_t)gk * ld + colB];
                 }
@@ -236,13 +245,13 @@ __global__ __launch_bounds__(256) void k_ekf_gemm(const EkfStreamDev *streams) {
 }
 
 // ------------------------------------------------------------------------------------ Householder TSQR
-// The reference compresses the stacked Jacobian with a Householder QR (SPQR / Eigen HouseholderQR, msckf_vio.cpp:795-817).
-// The default here is the Gram matrix + a regularised Cholesky (one MFMA pass, fully parallel), which squares the
-// condition number of H and adds the prior lambda I.  The Kalman update itself is regularised by P, so what that costs is
-// bounded by lambda max(P_aa) / sigma^2 whatever cond(H) is (measured: tests/test_gpu_kernels.py, condition sweep); the
-// factorisation evaluates that bound and this path takes over when it exceeds QR_BIAS_LIMIT, when the stack has no more
-// rows than active columns (the reference's m <= d case: nothing is compressed there, :818-821; H^T H would be singular
-// by construction), or always with compression_mode = 2.
+// The reference compresses the stacked Jacobian with a Householder QR (SPQR / Eigen HouseholderQR, msckf_vio.cpp:795-817) when
+// it has more rows than columns, and so does the default here (compression_mode 3): k_ekf_tsqr below, the row block in
+// registers.  This first variant, tsqr_wide, is the fallback INSIDE the Gram factorisation kernels (ekf_compress_exit) for
+// compression_mode 0: the Gram matrix + a regularised Cholesky squares the condition number of H and adds the prior lambda I.
+// The Kalman update itself is regularised by P, so what that costs is bounded by lambda max(P_aa) / sigma^2 whatever cond(H) is
+// (measured: tests/test_gpu_kernels.py, condition sweep); the factorisation evaluates that bound (gram_diagnostics) and this
+// path takes over when it exceeds QR_BIAS_LIMIT.
 // Row-block TSQR: the upper-triangular R of [H_act | r] (n1 = na + 1 columns, the residual rides along as the last one)
 // stays resident (LDS, packed by rows, when it fits; the stream's W buffer otherwise); the stacked rows are
 // streamed through LDS sixteen at a time and annihilated column by column against R's diagonal with Householder
@@ -284,9 +293,7 @@ __device__ __forceinline__ void tsqr_wide(const EkfStreamDev &S, int n1, int K, 
             if (gk < K) {
                 int col, clone;
                 colOf(c, col, clone);
-                const unsigned long long rm = S.rowmask[gk];
-                const bool on = clone < 0 ? rm != 0ULL : ((rm >> clone) & 1ULL) != 0ULL;
-                if (on) v = S.Hs[(size_t)gk * ld + col];
+                if (ekf_row_has(S.rowmask[gk], clone)) v = S.Hs[(size_t)gk * ld + col];
             }
             sB[e] = v;
         }
@@ -337,8 +344,8 @@ __device__ __forceinline__ void tsqr_quads(const EkfStreamDev &S, int n1, int K,
 // matrix; 1: the stack is used uncompressed and everything is set up (the kernel returns); 2: no Gram matrix was formed,
 // go straight to the TSQR.
 __device__ __forceinline__ int ekf_compress_entry(const EkfStreamDev &S, int *s_w /* shared, >= blockDim / 64 ints */) {
-    const int na = S.rows_out[2], me = S.rows_out[1], d = S.d, ld = S.ld;
-    if (na <= 0) { if (threadIdx.x == 0) S.rows_out[3] = 0; return 1; }
+    const int na = S.rows_out[EKF_ROWS_NA], me = S.rows_out[EKF_ROWS_END], d = S.d, ld = S.ld;
+    if (na <= 0) { if (threadIdx.x == 0) S.rows_out[EKF_ROWS_DIAG] = 0; return 1; }
     if (ekf_direct_wanted(S)) {
         // The reference's m <= d case (msckf_vio.cpp:818-821): no more stacked rows than active columns, nothing to
         // compress.  The stacked rows themselves are the measurement: R = H_act (st x na, read through rowidx and the
@@ -359,34 +366,40 @@ __device__ __forceinline__ int ekf_compress_entry(const EkfStreamDev &S, int *s_
             base += tot;
             __syncthreads();
         }
-        // (base == rows_out[0] <= na <= ld - 21: the list fits the ld ints behind act)
+        // (base == rows_out[EKF_ROWS_STACKED] <= na <= ld - 21: the list fits the ld ints behind act)
         __threadfence_block();
         __syncthreads();
         for (int i = tid; i < base; i += (int)blockDim.x) S.T[(size_t)i * ld + d] = S.Hs[(size_t)rowidx[i] * ld + d];
-        if (tid == 0) { S.rows_out[3] = 4; S.rows_out[4] = base; }
+        if (tid == 0) { S.rows_out[EKF_ROWS_DIAG] = EKF_DIAG_DIRECT; S.rows_out[EKF_ROWS_NK] = base; }
         return 1;
     }
     return ekf_skip_gram(S) ? 2 : 0;
 }
-// ... and AFTER it: Householder TSQR instead, for the streams that need it (forced, no Gram matrix formed, or the bias flag
-// of the factorisation just done), handed over in the layout the update expects: S.S = L = R^T (lower, ld-wide rows),
-// column d of T = Q^T r.  Rat(k, j): the resident R (zeroed here); sB: the row block, `room` doubles (>= 16 x n1).
+// The hand-over of a finished R (na + 1 columns, the last one Q^T r) in the layout the update expects: S.S = L = R^T (lower,
+// ld-wide rows), column d of T = Q^T r, and the diagnostics word.  Every thread of the workgroup calls it.
 template <class RAt>
-__device__ __forceinline__ void ekf_compress_exit(const EkfStreamDev &S, bool gram_done, int diag, RAt Rat, double *sB, int room) {
-    const int na = S.rows_out[2], n1 = na + 1, K = S.rows_out[1], d = S.d, ld = S.ld;
-    const int tid = threadIdx.x, nth = blockDim.x;
-    const bool need = ekf_mode_householder(S.qr_mode) || (S.qr_mode == 0 && (!gram_done || (diag & 2)));
-    if (!need) { if (tid == 0) S.rows_out[3] = diag; return; }
-    __syncthreads();
-    for (int e = tid; e < n1 * n1; e += nth) { const int k = e / n1, j = e - k * n1; if (j >= k) Rat(k, j) = 0.0; }
-    const int *act = S.act;
-    tsqr_quads(S, n1, K, [=](int c, int &col, int &clone) { col = c < na ? act[c] : d; clone = c < na ? (col - EKF_IMU_DIM) / 6 : -1; }, Rat, sB, room);
+__device__ __forceinline__ void ekf_hand_over_r(const EkfStreamDev &S, int na, RAt Rat, int diag) {
+    const int tid = threadIdx.x, nth = blockDim.x, d = S.d, ld = S.ld;
     for (int e = tid; e < na * na; e += nth) {
         const int i = e / na, j = e - i * na;
         if (j <= i) S.S[(size_t)i * ld + j] = Rat(j, i);
     }
     for (int k = tid; k < na; k += nth) S.T[(size_t)k * ld + d] = Rat(k, na);
-    if (tid == 0) S.rows_out[3] = diag | 1;
+    if (tid == 0) S.rows_out[EKF_ROWS_DIAG] = diag | EKF_DIAG_HOUSEHOLDER;
+}
+// ... and AFTER it: Householder TSQR instead, for the streams that need it (ekf_mode_redo_householder: forced, no Gram matrix
+// formed, or the bias flag of the factorisation just done).  Rat(k, j): the resident R (zeroed here); sB: the row block, `room`
+// doubles (>= 16 x n1).
+template <class RAt>
+__device__ __forceinline__ void ekf_compress_exit(const EkfStreamDev &S, bool gram_done, int diag, RAt Rat, double *sB, int room) {
+    const int na = S.rows_out[EKF_ROWS_NA], n1 = na + 1, K = S.rows_out[EKF_ROWS_END], d = S.d;
+    const int tid = threadIdx.x, nth = blockDim.x;
+    if (!ekf_mode_redo_householder(S.qr_mode, gram_done, (diag & EKF_DIAG_BIAS) != 0)) { if (tid == 0) S.rows_out[EKF_ROWS_DIAG] = diag; return; }
+    __syncthreads();
+    for (int e = tid; e < n1 * n1; e += nth) { const int k = e / n1, j = e - k * n1; if (j >= k) Rat(k, j) = 0.0; }
+    const int *act = S.act;
+    tsqr_quads(S, n1, K, [=](int c, int &col, int &clone) { col = c < na ? act[c] : d; clone = c < na ? (col - EKF_IMU_DIM) / 6 : -1; }, Rat, sB, room);
+    ekf_hand_over_r(S, na, Rat, diag);
 }
 
 // ------------------------------------------------------------------------------------ Householder TSQR, row block in registers
@@ -409,10 +422,7 @@ __device__ __forceinline__ void ekf_compress_exit(const EkfStreamDev &S, bool gr
 // No LDS to speak of, so the launch shares its CUs with whatever else is running.  Arithmetic: explicit fused multiply-adds
 // (this is a factorisation, not one of the decision-bearing sequences of DESIGN section 3); same skipping rule for annihilated
 // columns as tsqr_wide.
-#define TQ_THREADS 512
-// Which instantiation of k_ekf_tsqr compresses a stream is a property of the stream's own dimension, whatever else is in the
-// batch: 0 = <32, 2, 2> (up to 2 * TQ_THREADS / 4 columns incl. the residual), 1 = <16, 4, 2>.
-__host__ __device__ inline int tsqr_class(int d) { return d - EKF_IMU_DIM + 1 <= 2 * (TQ_THREADS / 4) ? 0 : 1; }
+
 // sum over the four DPP rows of a wavefront (lanes c, c + 16, c + 32, c + 48): every one of the four gets the same bits
 // (v_permlane16_swap / v_permlane32_swap of gfx950 - a VALU operation each, where a ds_bpermute pays the LDS crossbar's latency
 //  twice per sum on the dependent chain of every reflector step: swapping a value with a copy of itself leaves row pairs (halves)
@@ -458,6 +468,18 @@ template <int RL, int I = 0> struct TqAxpy {
     }
 };
 template <int RL> struct TqAxpy<RL, RL> { static __device__ __forceinline__ void run(double (&)[RL], const double (&)[RL / 16], double) {} };
+// Reflector (vr, v0, beta) onto the 16 columns of one slab, column bc of the block in this lane's registers: returns the new R[k][j]
+// of the lane's column (rkj before), meaningful where `on`; a lane with on == false keeps its column.  All 64 lanes of the
+// wavefront call it: the DPP broadcasts need their source lanes.
+template <int RL>
+__device__ __forceinline__ double tq_apply_reflector(double (&bc)[RL], const double (&vr)[RL / 16], double v0, double beta, double rkj, bool on) {
+    double p[4] = {0.0, 0.0, 0.0, 0.0};
+    TqDot<RL>::run(p, vr, bc);
+    const double dot = tq_rows_sum((p[0] + p[1]) + (p[2] + p[3]));
+    const double tt = on ? beta * __builtin_fma(v0, rkj, dot) : 0.0;
+    TqAxpy<RL>::run(bc, vr, -tt);
+    return __builtin_fma(-tt, v0, rkj);
+}
 // the four lanes that hold column k (one per DPP row, rows [r RL, (r + 1) RL) of the block each) form reflector k and publish it
 template <int RL>
 __device__ __forceinline__ void tq_form_reflector(const double (&bc)[RL], double x0, double *sVs, int *sFlag_s, double *Rkk, int r) {
@@ -506,7 +528,7 @@ __device__ __forceinline__ void tsqr_regs(const EkfStreamDev &S, int na, int K, 
             const unsigned long long rm = gk < K ? S.rowmask[gk] : 0ULL;
 #pragma unroll
             for (int t = 0; t < NC; ++t) {
-                const bool on = has[t] && (clone[t] < 0 ? rm != 0ULL : ((rm >> clone[t]) & 1ULL) != 0ULL);
+                const bool on = has[t] && ekf_row_has(rm, clone[t]);
                 b[t][i] = on ? S.Hs[(size_t)gk * ld + col[t]] : 0.0;
             }
         }
@@ -534,12 +556,8 @@ __device__ __forceinline__ void tsqr_regs(const EkfStreamDev &S, int na, int K, 
             for (int t = 0; t < NC; ++t) { const int j = 16 * wave + c + SLAB * t; rc[t] = (has[t] && k + 2 < n1) ? Rg[(size_t)(k + 2) * ld + j] : 0.0; }
             // reflector k onto the 16 columns of slab t of this wavefront (all 64 lanes: the DPP broadcasts need their source lanes)
             auto apply = [&](double (&bc)[RL], double rkj, int j, bool on) {
-                double p[4] = {0.0, 0.0, 0.0, 0.0};
-                TqDot<RL>::run(p, vr, bc);
-                const double dot = tq_rows_sum((p[0] + p[1]) + (p[2] + p[3]));
-                const double tt = on ? beta * __builtin_fma(v0, rkj, dot) : 0.0;
-                TqAxpy<RL>::run(bc, vr, -tt);
-                if (on && r == 0) Rg[(size_t)k * ld + j] = __builtin_fma(-tt, v0, rkj);
+                const double rnew = tq_apply_reflector<RL>(bc, vr, v0, beta, rkj, on);
+                if (on && r == 0) Rg[(size_t)k * ld + j] = rnew;
             };
             // the wavefront that holds column k + 1 takes that slab first, forms reflector k + 1 at once and publishes it in the
             // other copy while the rest of the workgroup is still applying reflector k
@@ -601,12 +619,8 @@ __device__ __forceinline__ void tsqr_wave(int n1, int n_blocks, int first, int s
                         const int j = c + 16 * t;
                         const bool on = j < n1 && j > k;
                         const double rkj = on ? R[k * ldr + j] : 0.0;
-                        double p[4] = {0.0, 0.0, 0.0, 0.0};
-                        TqDot<RL>::run(p, vr, b[t]);
-                        const double dot = tq_rows_sum((p[0] + p[1]) + (p[2] + p[3]));
-                        const double tt = on ? beta * __builtin_fma(v0, rkj, dot) : 0.0;
-                        TqAxpy<RL>::run(b[t], vr, -tt);
-                        if (on && r == 0) R[k * ldr + j] = __builtin_fma(-tt, v0, rkj);
+                        const double rnew = tq_apply_reflector<RL>(b[t], vr, v0, beta, rkj, on);
+                        if (on && r == 0) R[k * ldr + j] = rnew;
                     }
                 }
             }
@@ -627,151 +641,156 @@ __global__ __launch_bounds__(TQ_THREADS, WPE) void k_ekf_tsqr(const EkfStreamDev
     __shared__ __attribute__((aligned(16))) double sV[2 * (4 * RL + 2)];
     __shared__ int sFlag[2];
     if (ekf_compress_entry(S, s_w) != 2) return;                  // nothing active, or the stack is used uncompressed (all set up)
-    const int na = S.rows_out[2], K = S.rows_out[1], d = S.d, ld = S.ld;
-    const int tid = threadIdx.x;
-    if (na + 1 > (TQ_THREADS / 4) * NC) { if (tid == 0) S.rows_out[3] = 0x80; return; }      // (cannot happen: the launcher picks NC from the window)
+    const int na = S.rows_out[EKF_ROWS_NA], K = S.rows_out[EKF_ROWS_END], ld = S.ld;
+    if (na + 1 > (TQ_THREADS / 4) * NC) { if (threadIdx.x == 0) S.rows_out[EKF_ROWS_DIAG] = EKF_DIAG_REFUSED; return; }      // (cannot happen: the launcher picks NC from the window)
     double *Rg = S.W;
     tsqr_regs<RL, NC>(S, na, K, Rg, sV, sFlag);
-    // hand over in the layout the update expects: S.S = L = R^T (lower, ld-wide rows), column d of T = Q^T r
-    for (int e = tid; e < na * na; e += TQ_THREADS) {
-        const int i = e / na, j = e - i * na;
-        if (j <= i) S.S[(size_t)i * ld + j] = Rg[(size_t)j * ld + i];
+    ekf_hand_over_r(S, na, [=](int k, int j) -> double & { return Rg[(size_t)k * ld + j]; }, 0);
+}
+
+// ------------------------------------------------------------------------------------ Gram regularisation and its diagnostics
+// G = H^T H is rank deficient (unobserved clones, the gauge) and its small pivots are rounding noise: an unpivoted Cholesky
+// that skips or keeps them by a threshold is unstable (measured: up to 7e-5 relative error in P on few-feature updates,
+// tools/dev/update_truth.py).  Factor G + lambda I instead, lambda = 1e-14 d max(diag G): every pivot stays above the noise,
+// nothing is skipped, and the only effect is a prior of weight lambda / sigma^2 on the clone states (bias ~1e-11 relative,
+// same tool).  The three expressions of the rule, for the three kernels that factor a Gram matrix:
+__device__ __forceinline__ double gram_lambda(double max_diag, int d) { return (max_diag * (double)d) * 1e-14; }
+// a pivot (l = L_kk) that ends within 100 lambda of the regularisation floor (counted for the diagnostics only)
+__device__ __forceinline__ bool gram_tiny_pivot(double l, double lam) { return l * l < 100.0 * lam; }
+// the predicted relative bias of the posterior covariance from the lambda prior, lambda max(P_aa) / sigma^2, exceeds QR_BIAS_LIMIT
+__device__ __forceinline__ bool gram_biased(double lam, double max_paa, double sigma2) { return lam * max_paa > QR_BIAS_LIMIT * sigma2; }
+// The workgroup-wide form of k_ekf_chol_lds and k_ekf_chol (NT threads, all call; k_ekf_small_update has at most 24 entries and
+// leaves them to one thread).  diag(i): reference to the i-th diagonal entry in the caller's storage.  The reductions are fmax
+// and integer sums: whatever the order, the same bits.
+template <int NT> struct GramRegShared { double mx[NT / 64]; int tiny[NT / 64]; double lam; int diag; };
+// sh.lam = lambda, added to the diagonal (the caller's barrier follows)
+template <int NT, class Diag>
+__device__ __forceinline__ void gram_regularise(int n, int d, Diag diag, GramRegShared<NT> &sh) {
+    const int tid = threadIdx.x;
+    double mx = 0;
+    for (int i = tid; i < n; i += NT) mx = fmax(mx, diag(i));
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    if ((tid & 63) == 0) sh.mx[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) { double m = 0; for (int i = 0; i < NT / 64; ++i) m = fmax(m, sh.mx[i]); sh.lam = gram_lambda(m, d); }
+    __syncthreads();
+    const double lam = sh.lam;
+    for (int i = tid; i < n; i += NT) diag(i) += lam;
+}
+// After the factorisation (diag(i) = L_ii; pdiag(i) = P at active column i): sh.diag = the diagnostics word of the Gram factor,
+// valid after the caller's next barrier.
+template <int NT, class Diag, class PDiag>
+__device__ __forceinline__ void gram_diagnostics(int n, double sigma2, Diag diag, PDiag pdiag, GramRegShared<NT> &sh) {
+    const int tid = threadIdx.x;
+    int tiny = 0;
+    for (int i = tid; i < n; i += NT) tiny += gram_tiny_pivot(diag(i), sh.lam) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) tiny += __shfl_xor(tiny, o);
+    if ((tid & 63) == 0) sh.tiny[tid >> 6] = tiny;
+    __syncthreads();
+    double pm = 0;
+    for (int i = tid; i < n; i += NT) pm = fmax(pm, pdiag(i));
+    for (int o = 32; o > 0; o >>= 1) pm = fmax(pm, __shfl_xor(pm, o));
+    __syncthreads();
+    if ((tid & 63) == 0) sh.mx[tid >> 6] = pm;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0; for (int i = 0; i < NT / 64; ++i) t += sh.tiny[i];
+        double p = 0; for (int i = 0; i < NT / 64; ++i) p = fmax(p, sh.mx[i]);
+        sh.diag = ekf_diag_encode(t, gram_biased(sh.lam, p, sigma2));
     }
-    for (int k = tid; k < na; k += TQ_THREADS) S.T[(size_t)k * ld + d] = Rg[(size_t)k * ld + na];
-    if (tid == 0) S.rows_out[3] = 1;
 }
 
 // ------------------------------------------------------------------------------------ Cholesky
-// Fallback for active blocks that do not fit LDS (more than CHOL_LDS_MAX_ROWS rows: 50- and 60-clone windows): the same
-// blocked factorisation (chol_block.h) run in place on the row-major global matrix through a generic pointer — diagonal
-// block in registers, panel solve per row, trailing update on the matrix cores — with only the 16-wide panel in LDS.
-// A row is read up to 15 entries right of its diagonal as filler: those are the mirrored upper triangle and, for the
-// last rows, columns [n, n+16) of the ld-wide row (ld - n >= 21: the IMU columns are not part of the compact block).
-#define CHOLG_THREADS 512
-#define CHOL_LDS_MAX_ROWS 181     // k_ekf_chol_lds: active rows incl. the extra Q^T r row
-#define CHOL_PAN_RS 192           // k_ekf_chol_lds: row stride of the k-major panel (rows padded to a multiple of 16)
-// Which of the two factorisation kernels handles a stream is a property of the stream's own dimension, whatever else is in
-// the batch: 0 = k_ekf_chol_lds (the factor fits LDS), 1 = k_ekf_chol (global memory).
-__host__ __device__ inline int chol_class(int d) { return d - EKF_IMU_DIM + 1 <= CHOL_LDS_MAX_ROWS ? 0 : 1; }
-// dynamic LDS (doubles) of a k_ekf_chol_lds launch for a stream of dimension d alone: the packed factor and the panel
-__host__ __device__ inline int chol_lds_doubles(int d) { const int nt = d - EKF_IMU_DIM + 1; return nt * (nt + 1) / 2 + CHOL_PAN_RS * LNB; }
-__global__ __launch_bounds__(CHOLG_THREADS) void k_ekf_chol(const EkfStreamDev *streams, int which, int pan_rs, int cls) {
-    const EkfStreamDev &S = streams[blockIdx.y];
-    if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
-    if (cls >= 0 && chol_class(S.d) != cls) return;               // k_ekf_chol_lds's stream (ekf_launch_chol)
-    int entry = 0;
-    __shared__ int s_w[CHOLG_THREADS / 64];
-    if (which == 0) {
-        if (ekf_mode_householder(S.qr_mode)) return;      // compressed by k_ekf_tsqr (launched beside this kernel when the batch has such streams)
-        entry = ekf_compress_entry(S, s_w);
-        if (entry == 1) return;
-    }
-    const int n = which == 0 ? S.rows_out[2] : S.rows_out[4];   // active columns (Gram) / rows of the compressed measurement (S)
-    const int nt = n + (which == 0 ? 1 : 0);              // + the extra Q^T r row of the Gram factorisation
-    const int lda = S.ld;
-    double *A = which == 0 ? S.S : S.W;                   // G_c = [H_act|r]^T [H_act|r]  /  S = T[:, act] R^T + sigma^2 I
-    extern __shared__ double s_dyn[];
-    double *sPanT = s_dyn;                                // [LNB][pan_rs]
-    __shared__ double s_tol, s_mx[CHOLG_THREADS / 64];
-    __shared__ int s_diag;
-    __shared__ CholBlockShared s_cb;
-    const int tid = threadIdx.x;
-    if (tid == 0) s_diag = 0;
-    for (int e = tid; e < LNB * pan_rs; e += CHOLG_THREADS) sPanT[e] = 0.0;
-    if (which == 0) {
-        // regularised factorisation G + lambda I, lambda = 1e-14 d max(diag G) (see k_ekf_chol_lds)
-        double mx = 0;
-        for (int i = tid; i < n; i += CHOLG_THREADS) mx = fmax(mx, A[(size_t)i * lda + i]);
-        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
-        if ((tid & 63) == 0) s_mx[tid >> 6] = mx;
-        __syncthreads();
-        if (tid == 0) { double m = 0; for (int i = 0; i < CHOLG_THREADS / 64; ++i) m = fmax(m, s_mx[i]); s_tol = m * (double)S.d * 1e-14; }
-        __syncthreads();
-        const double lam = s_tol;
-        for (int i = tid; i < n; i += CHOLG_THREADS) A[(size_t)i * lda + i] += lam;
-    }
-    __syncthreads();
-    chol_blocked_lds<CHOLG_THREADS / 64>(A, [lda](int i, int j) { return i * lda + j; }, n, nt, 0.0, sPanT, pan_rs, s_cb);
-    if (which == 0) {
-        // pivots (L_kk^2) that end within 100 lambda of the regularisation floor (reported in the diagnostics only)
-        int tiny = 0;
-        for (int i = tid; i < n; i += CHOLG_THREADS) { const double l = A[(size_t)i * lda + i]; tiny += (l * l < 100.0 * s_tol) ? 1 : 0; }
-        for (int o = 32; o > 0; o >>= 1) tiny += __shfl_xor(tiny, o);
-        __shared__ int s_tiny[CHOLG_THREADS / 64];
-        if ((tid & 63) == 0) s_tiny[tid >> 6] = tiny;
-        __syncthreads();
-        // predicted relative bias of the posterior covariance from the lambda prior: lambda max(P_aa) / sigma^2
-        double pm = 0;
-        for (int i = tid; i < n; i += CHOLG_THREADS) pm = fmax(pm, S.P[(size_t)S.act[i] * lda + S.act[i]]);
-        for (int o = 32; o > 0; o >>= 1) pm = fmax(pm, __shfl_xor(pm, o));
-        __syncthreads();
-        if ((tid & 63) == 0) s_mx[tid >> 6] = pm;
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0; for (int i = 0; i < CHOLG_THREADS / 64; ++i) t += s_tiny[i];
-            double p = 0; for (int i = 0; i < CHOLG_THREADS / 64; ++i) p = fmax(p, s_mx[i]);
-            s_diag = (t << 8) | ((s_tol * p > QR_BIAS_LIMIT * S.sigma2) ? 2 : 0);
-        }
-        // column d of T <- (Q^T r) = the extra row of L, so the TRSM carries w = L2^-1 Q^T r along
-        for (int k = tid; k < n; k += CHOLG_THREADS) S.T[(size_t)k * lda + S.d] = A[(size_t)n * lda + k];
-        __syncthreads();
-        double *Rg = S.W;
-        // the TSQR's row block: the panel a launch for this stream alone allocates (the batch's is no smaller).  Sized from the
-        // launch's pan_rs, a 31-clone stream beside a 64-clone one took 32-row blocks instead of 16-row ones and its results
-        // differed in the last bits from the same update alone (tests/test_gpu_update_routes.py).
-        const int own_rs = (S.d - EKF_IMU_DIM + 1 + 15) / 16 * 16;
-        ekf_compress_exit(S, true, s_diag, [=](int k, int j) -> double & { return Rg[(size_t)k * lda + j]; }, sPanT, LNB * min(own_rs, pan_rs));
-    }
-}
-
-// ------------------------------------------------------------------------------------ LDS-resident Cholesky
-// Same factorisation with the active block held in LDS in packed lower form (row i at i(i+1)/2).
-// Structure used: the 21 IMU columns of every stacked Jacobian are zero (H_x only touches clone columns,
-// msckf_vio.cpp:698,713), so rows/cols [0,21) of G = [H|r]^T[H|r] are exactly zero (pivots skipped, L = 0)
-// and rows/cols [0,21) of S = T R^T + sigma^2 I are sigma^2 I (L = sigma I).  Only the trailing
-// (d-21) x (d-21) block is factorised: <= 180 rows for 30 clones = 129 KiB packed + a 16-wide panel.
-//
-// Right-looking, 16 columns per panel, one 512-thread workgroup (8 waves) per stream:
+// The factorisation of a stream's Gram matrix (which = 0: G_c = [H_act|r]^T [H_act|r], n = active columns, + the extra Q^T r
+// row) or of its innovation covariance (which = 1: S = T[:, act] R^T + sigma^2 I, n = rows of the compressed measurement), one
+// 512-thread workgroup (8 waves: 256 VGPRs per lane, the unrolled 16-column eliminations stay in registers) per stream.
+// Right-looking, 16 columns per panel (chol_block.h):
 //   1. wave 0 factors the 16x16 diagonal block in registers: lane r owns row r, the pivot and the column
 //      entries travel through v_mov_b64_dpp row_newbcast (no LDS round trips, no barriers inside the block); 1/sqrt(pivot)
 //      comes from v_rsq_f64 + two Newton steps, so the serial chain has no division;
 //   2. one thread per row below solves x L11^T = a against L11 broadcast the same way and leaves the panel k-major
 //      (sPanT[c][row]) for the MFMA operands;
 //   3. the trailing update A22 -= X X^T runs on v_mfma_f64_16x16x4_f64, one 16x16 tile of the lower triangle at
-//      a time per wave (4 MFMAs per tile), read-modify-write on the packed matrix.
-#define CHOL_THREADS 512          // 8 waves: 256 VGPRs per lane, the unrolled 16-column eliminations stay in registers
+//      a time per wave (4 MFMAs per tile), read-modify-write on the matrix.
+// Two kernels, one per storage; which of them a stream gets is a property of its own dimension (chol_class).  They share the
+// prologue (ekf_factor_entry), the regularisation and its diagnostics (above), chol_blocked_lds and the epilogue
+// (ekf_compress_exit); what each has of its own is where the matrix, the fallback TSQR's R and its row block live.  (A body
+// each: one templated over the storage costs k_ekf_chol 16 VGPRs.)
+#define CHOL_THREADS 512
 #define CHOL_WAVES (CHOL_THREADS / 64)
 
 __device__ __forceinline__ int pk(int i, int j) { return i * (i + 1) / 2 + j; }
+// dynamic LDS (doubles) of a k_ekf_chol_lds launch for a stream of dimension d alone: the packed factor and the panel
+__host__ __device__ inline int chol_lds_doubles(int d) { const int nt = d - EKF_IMU_DIM + 1; return nt * (nt + 1) / 2 + CHOL_PAN_RS * LNB; }
+// Does this workgroup factor its stream (class filter, route, mode; which = 0: ekf_compress_entry has run and left work)?
+__device__ __forceinline__ bool ekf_factor_entry(const EkfStreamDev &S, int which, int cls, int *s_w) {
+    if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return false;
+    if (cls >= 0 && chol_class(S.d) != cls) return false;         // the other kernel's stream (ekf_launch_chol)
+    if (which == 0) {
+        if (ekf_mode_householder(S.qr_mode)) return false;        // compressed by k_ekf_tsqr (launched beside this kernel when the batch has such streams)
+        if (ekf_compress_entry(S, s_w) == 1) return false;
+    }
+    return true;
+}
 
+// Active blocks that do not fit LDS (more than CHOL_LDS_MAX_ROWS rows: 31- to 64-clone windows): in place on the row-major global
+// matrix through a generic pointer, with only the 16-wide panel in LDS.  A row is read up to 15 entries right of its diagonal as
+// filler: those are the mirrored upper triangle and, for the last rows, columns [n, n+16) of the ld-wide row (ld - n >= 21: the
+// IMU columns are not part of the compact block).
+__global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol(const EkfStreamDev *streams, int which, int pan_rs, int cls) {
+    const EkfStreamDev &S = streams[blockIdx.y];
+    __shared__ int s_w[CHOL_WAVES];
+    if (!ekf_factor_entry(S, which, cls, s_w)) return;
+    const int n = which == 0 ? S.rows_out[EKF_ROWS_NA] : S.rows_out[EKF_ROWS_NK];   // active columns (Gram) / rows of the compressed measurement (S)
+    const int nt = n + (which == 0 ? 1 : 0);              // + the extra Q^T r row of the Gram factorisation
+    const int lda = S.ld;
+    double *A = which == 0 ? S.S : S.W;
+    extern __shared__ double s_dyn[];
+    double *sPanT = s_dyn;                                // [LNB][pan_rs]
+    __shared__ GramRegShared<CHOL_THREADS> s_reg;
+    __shared__ CholBlockShared s_cb;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < LNB * pan_rs; e += CHOL_THREADS) sPanT[e] = 0.0;
+    auto diag = [=](int i) -> double & { return A[(size_t)i * lda + i]; };
+    if (which == 0) gram_regularise<CHOL_THREADS>(n, S.d, diag, s_reg);
+    __syncthreads();
+    chol_blocked_lds<CHOL_WAVES>(A, [lda](int i, int j) { return i * lda + j; }, n, nt, 0.0, sPanT, pan_rs, s_cb);
+    if (which == 0) {
+        const double *P = S.P; const int *act = S.act;
+        gram_diagnostics<CHOL_THREADS>(n, S.sigma2, diag, [=](int i) { return P[(size_t)act[i] * lda + act[i]]; }, s_reg);
+        // column d of T <- (Q^T r) = the extra row of L, so the TRSM carries w = L2^-1 Q^T r along
+        for (int k = tid; k < n; k += CHOL_THREADS) S.T[(size_t)k * lda + S.d] = A[(size_t)n * lda + k];
+        __syncthreads();
+        double *Rg = S.W;
+        // the TSQR's row block: the panel a launch for this stream alone allocates (the batch's is no smaller).  Sized from the
+        // launch's pan_rs, a 31-clone stream beside a 64-clone one took 32-row blocks instead of 16-row ones and its results
+        // differed in the last bits from the same update alone (tests/test_gpu_update_routes.py).
+        const int own_rs = (S.d - EKF_IMU_DIM + 1 + 15) / 16 * 16;
+        ekf_compress_exit(S, true, s_reg.diag, [=](int k, int j) -> double & { return Rg[(size_t)k * lda + j]; }, sPanT, LNB * min(own_rs, pan_rs));
+    }
+}
+
+// The active block held in LDS in packed lower form (row i at i(i+1)/2): <= 180 rows for 30 clones = 129 KiB packed + a 16-wide
+// panel.  (The 21 IMU columns of every stacked Jacobian are zero - H_x only touches clone columns, msckf_vio.cpp:698,713 - and
+// are not part of the compact block.)
 __global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDev *streams, int which, int cls) {
     const EkfStreamDev &S = streams[blockIdx.y];
-    if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
-    if (cls >= 0 && chol_class(S.d) != cls) return;               // k_ekf_chol's stream (ekf_launch_chol)
-    const int lds_doubles = chol_lds_doubles(S.d);                // what a launch for this stream alone allocates (the batch's is no smaller)
-    int entry = 0;
     __shared__ int s_w[CHOL_WAVES];
-    if (which == 0) {
-        if (ekf_mode_householder(S.qr_mode)) return;      // compressed by k_ekf_tsqr (launched beside this kernel when the batch has such streams)
-        entry = ekf_compress_entry(S, s_w);
-        if (entry == 1) return;
-    }
+    if (!ekf_factor_entry(S, which, cls, s_w)) return;
+    const int lds_doubles = chol_lds_doubles(S.d);        // what a launch for this stream alone allocates (the batch's is no smaller)
     double *A = which == 0 ? S.S : S.W;
-    const int off = 0, lda = S.ld;                 // compact storage: index i <-> column act[i]
-    const int n = which == 0 ? S.rows_out[2] : S.rows_out[4];   // active columns (Gram) / rows of the compressed measurement (S)
-    const int nt = n + (which == 0 ? 1 : 0);       // rows incl. the extra row
-    const bool semidef = which == 0;
+    const int lda = S.ld;
+    const int n = which == 0 ? S.rows_out[EKF_ROWS_NA] : S.rows_out[EKF_ROWS_NK];   // active columns (Gram) / rows of the compressed measurement (S)
+    const int nt = n + (which == 0 ? 1 : 0);              // rows incl. the extra row
     extern __shared__ double s_dyn[];
-    double *sM = s_dyn;                            // packed lower, nt rows
-    double *sPanT = s_dyn + nt * (nt + 1) / 2;     // [LNB][CHOL_PAN_RS]
-    __shared__ double s_tol, s_mx[CHOL_WAVES];
-    __shared__ int s_diag;
+    double *sM = s_dyn;                                   // packed lower, nt rows
+    double *sPanT = s_dyn + nt * (nt + 1) / 2;            // [LNB][CHOL_PAN_RS]
+    __shared__ GramRegShared<CHOL_THREADS> s_reg;
     __shared__ CholBlockShared s_cb;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_diag = 0;
     // R of the TSQR lives where the packed factor does (packed upper by rows: the same n1 (n1 + 1) / 2 doubles), the row block in the panel's space
     auto Rl = [=](int k, int j) -> double & { return sM[k * nt - k * (k - 1) / 2 + (j - k)]; };
-    const int room = lds_doubles - nt * (nt + 1) / 2;       // what the launch's LDS leaves beside the packed factor / the resident R: the TSQR's row block
+    const int room = lds_doubles - nt * (nt + 1) / 2;     // what the launch's LDS leaves beside the packed factor / the resident R: the TSQR's row block
     // load: one matrix row per wave pass, coalesced along j
     // (8 rows x 3 column chunks = up to 24 loads in flight per lane: the copy is latency bound otherwise)
     for (int i0 = wave * 8; i0 < nt; i0 += CHOL_WAVES * 8) {
@@ -779,7 +798,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDe
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int i = i0 + u;
-            const double *src = A + (size_t)(off + i) * lda + off;
+            const double *src = A + (size_t)i * lda;
 #pragma unroll
             for (int k = 0; k < 3; ++k) { const int j = lane + 64 * k; v[u][k] = (i < nt && j <= i) ? src[j] : 0.0; }
         }
@@ -794,49 +813,20 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDe
     }
     for (int e = tid; e < LNB * CHOL_PAN_RS; e += CHOL_THREADS) sPanT[e] = 0.0;
     __syncthreads();
-    if (semidef) {
-        // G = H^T H is rank deficient (unobserved clones, the gauge) and its small pivots are rounding noise:
-        // an unpivoted Cholesky that skips or keeps them by a threshold is unstable (measured: up to 7e-5
-        // relative error in P on few-feature updates, tools/dev/update_truth.py).  Factor G + lambda I instead,
-        // lambda = 1e-14 d max(diag G): every pivot stays above the noise, nothing is skipped, and the only effect
-        // is a prior of weight lambda / sigma^2 on the clone states (bias ~1e-11 relative, same tool).
-        double mx = 0;
-        for (int i = tid; i < n; i += CHOL_THREADS) mx = fmax(mx, sM[pk(i, i)]);
-        for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        if (lane == 0) s_mx[wave] = mx;
-        __syncthreads();
-        if (tid == 0) { double m = 0; for (int i = 0; i < CHOL_WAVES; ++i) m = fmax(m, s_mx[i]); s_tol = m * (double)S.d * 1e-14; }
-        __syncthreads();
-        const double lam = s_tol;
-        for (int i = tid; i < n; i += CHOL_THREADS) sM[pk(i, i)] += lam;
+    auto diag = [=](int i) -> double & { return sM[pk(i, i)]; };
+    if (which == 0) {
+        gram_regularise<CHOL_THREADS>(n, S.d, diag, s_reg);
         __syncthreads();
     }
-    const double tol = 0.0;      // a pivot <= 0 (cannot happen for G + lambda I or for S >= sigma^2 I) zeroes its column
-    chol_blocked_lds<CHOL_WAVES>(sM, [](int i, int j) { return pk(i, j); }, n, nt, tol, sPanT, CHOL_PAN_RS, s_cb);
+    // a pivot <= 0 (cannot happen for G + lambda I or for S >= sigma^2 I) zeroes its column
+    chol_blocked_lds<CHOL_WAVES>(sM, [](int i, int j) { return pk(i, j); }, n, nt, 0.0, sPanT, CHOL_PAN_RS, s_cb);
     if (which == 0) {
-        // pivots (L_kk^2) that end within 100 lambda of the regularisation floor (reported in the diagnostics only)
-        int tiny = 0;
-        for (int i = tid; i < n; i += CHOL_THREADS) { const double l = sM[pk(i, i)]; tiny += (l * l < 100.0 * s_tol) ? 1 : 0; }
-        for (int o = 32; o > 0; o >>= 1) tiny += __shfl_xor(tiny, o);
-        __shared__ int s_tiny[CHOL_WAVES];
-        if (lane == 0) s_tiny[wave] = tiny;
-        __syncthreads();
-        // predicted relative bias of the posterior covariance from the lambda prior: lambda max(P_aa) / sigma^2
-        double pm = 0;
-        for (int i = tid; i < n; i += CHOL_THREADS) pm = fmax(pm, S.P[(size_t)S.act[i] * lda + S.act[i]]);
-        for (int o = 32; o > 0; o >>= 1) pm = fmax(pm, __shfl_xor(pm, o));
-        __syncthreads();
-        if (lane == 0) s_mx[wave] = pm;
-        __syncthreads();
-        if (tid == 0) {
-            int t = 0; for (int i = 0; i < CHOL_WAVES; ++i) t += s_tiny[i];
-            double p = 0; for (int i = 0; i < CHOL_WAVES; ++i) p = fmax(p, s_mx[i]);
-            s_diag = (t << 8) | ((s_tol * p > QR_BIAS_LIMIT * S.sigma2) ? 2 : 0);
-        }
+        const double *P = S.P; const int *act = S.act;
+        gram_diagnostics<CHOL_THREADS>(n, S.sigma2, diag, [=](int i) { return P[(size_t)act[i] * lda + act[i]]; }, s_reg);
     }
     // store back
     for (int i = wave; i < nt; i += CHOL_WAVES) {
-        double *dst = A + (size_t)(off + i) * lda + off;
+        double *dst = A + (size_t)i * lda;
         const double *src = sM + pk(i, 0);
 #pragma unroll
         for (int k = 0; k < 3; ++k) { const int j = lane + 64 * k; if (j <= i && j < n) dst[j] = src[j]; }
@@ -845,7 +835,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDe
         // column d of T <- (Q^T r) = the extra row of L, so the TRSM carries w = L2^-1 Q^T r along
         for (int k = tid; k < n; k += CHOL_THREADS) S.T[(size_t)k * lda + S.d] = sM[pk(n, k)];
         __syncthreads();
-        ekf_compress_exit(S, true, s_diag, Rl, sPanT, room);
+        ekf_compress_exit(S, true, s_reg.diag, Rl, sPanT, room);
     }
 }
 
@@ -854,11 +844,10 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_ekf_chol_lds(const EkfStreamDe
 // 32-column strip; the strip (na x 32 doubles) stays in LDS for the whole solve, L is staged 16 rows at a time.
 #define QR_MAX_N1 (6 * 64 + 1)     // active columns of a 64-clone window + the residual
 #define TS_COLS 32
-#define TS_RB 16
 __global__ __launch_bounds__(256) void k_ekf_trsm(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_feat <= 0 || (S.route & EKF_ROUTE_SMALL)) return;
-    const int n = S.rows_out[4], ld = S.ld, ncols = S.d + 1;      // rows of the compressed measurement, all d+1 columns
+    const int n = S.rows_out[EKF_ROWS_NK], ld = S.ld, ncols = S.d + 1;      // rows of the compressed measurement, all d+1 columns
     const int c0 = blockIdx.x * TS_COLS;
     if (c0 >= ncols) return;
     const double *L = S.W;
@@ -872,25 +861,24 @@ __global__ __launch_bounds__(256) void k_ekf_trsm(const EkfStreamDev *streams) {
         sY[e] = (c0 + cc < ncols) ? B[(size_t)i * ld + c0 + cc] : 0.0;
     }
     // L row blocks are prefetched one block ahead into registers: 16 threads per row, columns lr, lr + 16, ...
-    constexpr int LPF = 14;                       // ceil((max d + 16) / 16) for d <= 208
     const int lrow = tid >> 4, lr = tid & 15;
-    double lpf[LPF];
+    double lpf[TS_LPF];
     auto fetch_L = [&](int ib) {
         const int nb = min(TS_RB, n - ib), wcols = ib + nb;
 #pragma unroll
-        for (int q = 0; q < LPF; ++q) {
+        for (int q = 0; q < TS_LPF; ++q) {
             const int p = lr + 16 * q;
             lpf[q] = (lrow < nb && p < wcols) ? L[(size_t)(ib + lrow) * ld + p] : 0.0;
         }
     };
-    const bool l_fits = n + TS_RB <= 16 * LPF;    // else fall back to direct staging
+    const bool l_fits = trsm_l_fits(n);           // else fall back to direct staging
     if (l_fits) fetch_L(0);
     for (int ib = 0; ib < n; ib += TS_RB) {
         const int nb = min(TS_RB, n - ib);
         __syncthreads();
         if (l_fits) {
 #pragma unroll
-            for (int q = 0; q < LPF; ++q) {
+            for (int q = 0; q < TS_LPF; ++q) {
                 const int p = lr + 16 * q;
                 if (lrow < nb && p < ib + nb) sL[(size_t)lrow * (n + 1) + p] = lpf[q];
             }
@@ -939,6 +927,25 @@ __global__ __launch_bounds__(256) void k_ekf_trsm(const EkfStreamDev *streams) {
     }
 }
 
+// Unblocked right-looking Cholesky in LDS for k_ekf_small_update (256 threads, all call): the leading np x np block of the
+// row-major A (stride lda) is factored in place (lower), rows [np, nr) ride along (after it such a row r holds (L^-1 r)^T).
+// A pivot <= 0 zeroes its column.
+__device__ __forceinline__ void su_chol(double *A, int lda, int np, int nr) {
+    const int tid = threadIdx.x;
+    for (int k = 0; k < np; ++k) {
+        const double pv = A[k * lda + k];
+        const double inv = pv > 0.0 ? 1.0 / sqrt(pv) : 0.0;
+        __syncthreads();
+        if (tid >= k && tid < nr) A[tid * lda + k] = (tid == k) ? (pv > 0.0 ? sqrt(pv) : 0.0) : A[tid * lda + k] * inv;
+        __syncthreads();
+        for (int e = tid; e < (nr - k - 1) * (nr - k - 1); e += 256) {
+            const int i = k + 1 + e / (nr - k - 1), j = k + 1 + e % (nr - k - 1);
+            if (j <= i) A[i * lda + j] -= A[i * lda + k] * A[j * lda + k];
+        }
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------ small update, fused
 // The whole measurement update of a stream in ONE workgroup when the stack touches few clones (na <= SU_MAX_NA active
 // columns): the pruning update (msckf_vio.cpp:1073-1184) stacks hundreds of 2-observation features but only the two
@@ -947,7 +954,6 @@ __global__ __launch_bounds__(256) void k_ekf_trsm(const EkfStreamDev *streams) {
 // back to back out of LDS.  Same algebra as the general path: G = [H_act|r]^T [H_act|r] + lambda I = L L^T,
 // T = L^T[0:na,0:na] P[act,:], S = T[:,act] L[0:na,0:na] + sigma^2 I = L2 L2^T, Y = L2^-1 [T | Q^T r],
 // delta_x = Y^T w, P -= Y^T Y (symmetric by construction).  All sums run in a fixed order (no atomics).
-#define SU_CH 128         // stacked rows per Gram chunk
 __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *streams) {
     const EkfStreamDev &S = streams[blockIdx.y];
     if (S.n_feat <= 0 || !(S.route & EKF_ROUTE_SMALL)) return;
@@ -964,7 +970,6 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
     double *sS = sG + n1 * n1;                   // na x na: S, then its factor L2 (lower)
     double *sC = sS + na * na;                   // SU_CH x n1 chunk of [H_act | r]
     __shared__ int s_col[SU_MAX_NA + 1], s_clone[SU_MAX_NA + 1];
-    __shared__ double s_lam;
     if (tid < n1) {
         const int col = tid < na ? ekf_act_column(cap.clones, tid) : d;
         s_col[tid] = col;
@@ -975,7 +980,9 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
     //         the rows of a chunk into `groups` interleaved sets, summed in a fixed order at the end
     // (the Householder modes never use the Gram matrix: steps 1 and 2 are skipped for them and the TSQR of step 2b runs at once)
     const bool hh_only = ekf_mode_householder(S.qr_mode);
-    if (tid == 0) s_lam = 0.0;
+    __shared__ double s_lam;
+    __shared__ int s_tiny, s_bias;          // (16 bytes with s_lam: the dynamic LDS behind the static starts on a multiple of 16, for the b128 accesses below)
+    if (tid == 0) { s_lam = 0.0; s_tiny = 0; s_bias = 0; }
     if (!hh_only) {
     const int np = n1 * (n1 + 1) / 2;
     const int groups = np <= 128 ? 256 / np : 1;
@@ -996,9 +1003,7 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
             const int r = e / n1, c = e - r * n1, gk = k0 + r;
             double v = 0.0;
             if (gk < K) {
-                const unsigned long long rm = S.rowmask[gk];
-                const bool on = s_clone[c] < 0 ? rm != 0ULL : ((rm >> s_clone[c]) & 1ULL) != 0ULL;
-                if (on) v = S.Hs[(size_t)gk * ld + s_col[c]];
+                if (ekf_row_has(S.rowmask[gk], s_clone[c])) v = S.Hs[(size_t)gk * ld + s_col[c]];
             }
             sC[e] = v;
         }
@@ -1026,43 +1031,30 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
             if (pg[q] >= 0) { sG[pi[q] * n1 + pj[q]] = acc[q]; sG[pj[q] * n1 + pi[q]] = acc[q]; }
     }
     __syncthreads();
-    // ---- 2. G + lambda I = L L^T (lambda as in k_ekf_chol_lds), the Q^T r row rides along as row na
-    if (tid == 0) { double mx = 0; for (int i = 0; i < na; ++i) mx = fmax(mx, sG[i * n1 + i]); s_lam = mx * (double)d * 1e-14; }
+    // ---- 2. G + lambda I = L L^T (lambda and the diagnostics as in gram_regularise / gram_diagnostics; at most 24 entries:
+    //         one thread), the Q^T r row rides along as row na
+    if (tid == 0) { double mx = 0; for (int i = 0; i < na; ++i) mx = fmax(mx, sG[i * n1 + i]); s_lam = gram_lambda(mx, d); }
     __syncthreads();
     if (tid < na) sG[tid * n1 + tid] += s_lam;
     __syncthreads();
-    for (int k = 0; k < na; ++k) {
-        const double pv = sG[k * n1 + k];
-        const double inv = pv > 0.0 ? 1.0 / sqrt(pv) : 0.0;
-        __syncthreads();
-        if (tid >= k && tid < n1) sG[tid * n1 + k] = (tid == k) ? (pv > 0.0 ? sqrt(pv) : 0.0) : sG[tid * n1 + k] * inv;
-        __syncthreads();
-        for (int e = tid; e < (n1 - k - 1) * (n1 - k - 1); e += 256) {
-            const int i = k + 1 + e / (n1 - k - 1), j = k + 1 + e % (n1 - k - 1);
-            if (j <= i) sG[i * n1 + j] -= sG[i * n1 + k] * sG[j * n1 + k];
+    su_chol(sG, n1, na, n1);
+    if (tid == 0) {
+        int t = 0;
+        double pm = 0;
+        for (int i = 0; i < na; ++i) {
+            t += gram_tiny_pivot(sG[i * n1 + i], s_lam) ? 1 : 0;
+            pm = fmax(pm, S.P[(size_t)s_col[i] * ld + s_col[i]]);
         }
-        __syncthreads();
+        s_tiny = t;
+        s_bias = gram_biased(s_lam, pm, S.sigma2) ? 1 : 0;
     }
     }   // !hh_only
-    // ---- 2b. the same decision as ekf_compress_exit: bias flag, no more stacked rows than columns, or forced ->
-    //          Householder TSQR of the stacked rows, R in sG (full rows), then L = R^T back in place
+    // ---- 2b. bias flag, no more stacked rows than columns (no Gram factor to use: this route compresses such a stack too), or
+    //          forced -> Householder TSQR of the stacked rows, R in sG (full rows), then L = R^T back in place
     {
-        __shared__ int s_tiny, s_bias;
-        if (tid == 0 && hh_only) { s_tiny = 0; s_bias = 0; }
-        if (tid == 0 && !hh_only) {
-            int t = 0;
-            double pm = 0;
-            for (int i = 0; i < na; ++i) {
-                const double l = sG[i * n1 + i];
-                t += (l * l < 100.0 * s_lam) ? 1 : 0;
-                pm = fmax(pm, S.P[(size_t)s_col[i] * ld + s_col[i]]);
-            }
-            s_tiny = t;
-            s_bias = (s_lam * pm > QR_BIAS_LIMIT * S.sigma2) ? 1 : 0;
-        }
         __syncthreads();
-        const int tiny = s_tiny;
-        const bool need_qr = ekf_mode_householder(S.qr_mode) || (S.qr_mode == 0 && (cap.stacked <= na || s_bias));
+        const int diag = ekf_diag_encode(s_tiny, s_bias != 0);
+        const bool need_qr = ekf_mode_redo_householder(S.qr_mode, cap.stacked > na, (diag & EKF_DIAG_BIAS) != 0);
         if (need_qr) {
             for (int e = tid; e < n1 * n1; e += 256) sG[e] = 0.0;
             __syncthreads();
@@ -1084,10 +1076,7 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
                 auto loadH = [&](int blk, int row, int col) -> double {
                     const int gk = blk * 128 + row;
                     if (gk >= K || col >= n1) return 0.0;
-                    const unsigned long long rm = rowmask[gk];
-                    const int cl = s_clone[col];
-                    const bool on = cl < 0 ? rm != 0ULL : ((rm >> cl) & 1ULL) != 0ULL;
-                    return on ? Hs[(size_t)gk * ld + s_col[col]] : 0.0;
+                    return ekf_row_has(rowmask[gk], s_clone[col]) ? Hs[(size_t)gk * ld + s_col[col]] : 0.0;
                 };
                 double *Rmine = wv == 0 ? sG : sRw + (wv - 1) * n1 * n1;
                 tsqr_wave<32, 2>(n1, (K + 127) / 128, wv, 4, loadH, Rmine, n1, sVq + wv * 130, sFq + wv);
@@ -1105,7 +1094,7 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
             for (int e = tid; e < n1 * n1; e += 256) { const int i = e / n1, j = e - i * n1; if (j < i) sG[e] = sG[j * n1 + i]; }
             __syncthreads();
         }
-        if (tid == 0) S.rows_out[3] = (tiny << 8) | (s_bias ? 2 : 0) | (need_qr ? 1 : 0);
+        if (tid == 0) S.rows_out[EKF_ROWS_DIAG] = diag | (need_qr ? EKF_DIAG_HOUSEHOLDER : 0);
     }
     // ---- 3. T = R P[act, :] with R = L^T (upper): T[i][c] = sum_{k >= i} L[k][i] P[act[k]][c];  T[i][d] = (Q^T r)_i = L[na][i]
     const double *P = S.P;
@@ -1136,18 +1125,7 @@ __global__ __launch_bounds__(256) void k_ekf_small_update(const EkfStreamDev *st
     }
     __syncthreads();
     // ---- 5. S = L2 L2^T
-    for (int k = 0; k < na; ++k) {
-        const double pv = sS[k * na + k];
-        const double inv = pv > 0.0 ? 1.0 / sqrt(pv) : 0.0;
-        __syncthreads();
-        if (tid >= k && tid < na) sS[tid * na + k] = (tid == k) ? (pv > 0.0 ? sqrt(pv) : 0.0) : sS[tid * na + k] * inv;
-        __syncthreads();
-        for (int e = tid; e < (na - k - 1) * (na - k - 1); e += 256) {
-            const int i = k + 1 + e / (na - k - 1), j = k + 1 + e % (na - k - 1);
-            if (j <= i) sS[i * na + j] -= sS[i * na + k] * sS[j * na + k];
-        }
-        __syncthreads();
-    }
+    su_chol(sS, na, na, na);
     // ---- 6. Y = L2^-1 [T | Q^T r], one thread per column
     for (int c = tid; c <= d; c += 256) {
         double y[SU_MAX_NA];
@@ -1206,7 +1184,7 @@ void ekf_launch_chol(const EkfStreamDev *d, int n, int which, int min_d, int max
     if (hi == 1) {
         const int nt = max_d - EKF_IMU_DIM + 1;
         const int pan_rs = (nt + 15) / 16 * 16;
-        hipLaunchKernelGGL(k_ekf_chol, dim3(1, n), dim3(CHOLG_THREADS), (size_t)LNB * pan_rs * sizeof(double), st, d, which, pan_rs, lo == hi ? -1 : 1);
+        hipLaunchKernelGGL(k_ekf_chol, dim3(1, n), dim3(CHOL_THREADS), (size_t)LNB * pan_rs * sizeof(double), st, d, which, pan_rs, lo == hi ? -1 : 1);
     }
 }
 void ekf_launch_small_update(const EkfStreamDev *d, int n, int max_d, hipStream_t st) {

@@ -74,7 +74,7 @@ class EkfDirectArgs(C.Structure):
 
 
 assert C.sizeof(EkfDirectArgs) == 64
-DIRECT_MAX_ROWS = 6          # MSKF_DIRECT_MAX_ROWS (csrc/hip/ekf_device.h)
+DIRECT_MAX_ROWS = 6          # MSKF_DIRECT_MAX_ROWS (csrc/hip/ekf_limits.h)
 
 
 class FeEqualize(C.Structure):

@@ -35,7 +35,7 @@ import numpy as np
 import ekf_problems
 import feature_reference as FR
 
-FEAT_WAVE_CLONES, FEAT_SMALL_CLONES, TRI_SMALL_CLONES = 4, 16, 32       # csrc/hip/ekf_device.h
+FEAT_WAVE_CLONES, FEAT_SMALL_CLONES, TRI_SMALL_CLONES = 4, 16, 32       # csrc/hip/ekf_limits.h
 GATE_LDS_ROWS = 120                                                    # ekf_kernels.hip: 30 observations fit, 31 do not
 EKF_SLOTS = 64
 FAR = dict(depth_scale=30.0)

@@ -34,7 +34,8 @@ import feature_reference as FR
 
 LD = FR.LD
 SIGMA2 = 0.035 ** 2               # default_ekf_cfg().noise_feature ** 2
-# csrc/hip/ekf_device.h, ekf_linalg.hip
+# csrc/hip/ekf_limits.h; tests/test_update_limits.py holds these, the class functions and `predicted` against the header itself
+# (all but LNB, which mirrors chol_block.h, a header that needs the HIP runtime: not checked)
 IMU_DIM = 21
 SU_MAX_NA, SU_CH = 24, 128
 CHOL_LDS_MAX_ROWS, CHOL_PAN_RS, LNB = 181, 192, 16
