@@ -21,10 +21,11 @@ def _stream(gpu_ctx, oracle, w, h, **kw):
 
 @pytest.mark.parametrize("w,h", [(752, 480), (376, 240), (333, 251), (1280, 720), (64, 64), (65, 67), (129, 71), (255, 130), (257, 193), (1001, 99), (122, 509)])
 def test_pyramid_bit_exact(gpu_ctx, oracle, w, h):
-    """Levels 1 .. 3 from the one-launch kernel (k_pyr_down3: a workgroup owns a 16 x 8 tile of level 3 and the levels above
-    it, regions in LDS, reflected borders filled per level) equal three separate pyr_down passes of the oracle bit for bit:
-    the benchmark shapes, odd sizes at every level, sizes one pixel either side of a tile boundary at level 3 (16 x 8 tiles =
-    128 x 64 pixels of level 0), images smaller than one tile, long thin images."""
+    """Levels 1 .. 3 from the one-launch kernel (k_pyr_down3: a register / DPP row march, a 16-lane strip owns 12 level-3
+    columns and marches down a segment of level-3 rows, borders reflected per level) equal three separate pyr_down passes of
+    the oracle bit for bit: the benchmark shapes, odd sizes at every level, sizes one pixel either side of 128 x 64 pixels of
+    level 0, the smallest images a stream accepts, long thin images.  The seams of the march itself (strips of 96 level-0
+    columns, segments) are the subject of tests/test_gpu_pyramid_march.py."""
     rng = np.random.default_rng(w * 1000 + h)
     a = rng.integers(0, 256, (h, w), dtype=np.uint8)
     b = rng.integers(0, 256, (h, w), dtype=np.uint8)
@@ -311,7 +312,9 @@ def test_triangulation_matches_oracle(gpu_ctx, oracle):
 
 # ------------------------------------------------------------------ large-configuration code paths
 def test_detector_large_cells(gpu_ctx, oracle):
-    """Cells larger than the 32x32 LDS sub-tile (4K-like geometry: 2000/47 = 43, 1100/30 = 37 px)."""
+    """Cells larger than a 32-row segment of the detector's march and not a multiple of a lane's four columns (4K-like geometry:
+    2000/47 = 43, 1100/30 = 37 px): cell rows cross the segment ends, where two segments feed a cell through atomicMax.  Cells
+    wider than a strip and higher than several segments are in tests/test_gpu_detector_edges.py."""
     w, h = 2000, 1100
     rng = np.random.default_rng(4)
     base = rng.integers(0, 256, (h // 8 + 1, w // 8 + 1), dtype=np.uint8)
