@@ -43,7 +43,9 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  4 (round 4): the 2-point RANSAC inside the device frame (mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter);
                                  added under 4, symbols only, no struct changed: mskf_ekf_get_odom_cov, _batch, _batch_begin, _batch_end;
                                  mskf_fe_set_equalize, mskf_fe_get_equalize; mskf_fe_set_input_format, mskf_fe_get_input_format;
-                                 mskf_ekf_update_direct, _batch, _batch_begin, _batch_end (with their own mskf_ekf_direct_args) */
+                                 mskf_ekf_update_direct, _batch, _batch_begin, _batch_end (with their own mskf_ekf_direct_args);
+                                 mskf_fe_set_mask, mskf_fe_get_mask (with their own mskf_fe_mask) and the timing kind MSKF_K_FE_MASK, which is the
+                                 slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged) */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -65,7 +67,7 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
 
 /* Optional per-kernel timing with HIP events recorded on the context's own stream (bench / roofline).
  * `units` are the algorithmic work units of a launch (LK: point tracks, temporal + stereo of one track call in one launch — MSKF_K_PT_GEOM
- * is kept for ABI stability and stays empty since the per-point geometry moved into that launch; pyramid: output pixels;
+ * is kept for ABI stability, counts no geometry since that moved into that launch, and carries MSKF_K_FE_MASK instead; pyramid: output pixels;
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
  * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
@@ -73,7 +75,11 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
  * counts the launches of k_ekf_direct_update instead (mskf_ekf_update_direct*; units: streams with rows), which nothing but those calls makes. */
 enum {
     MSKF_K_PYR = 0, MSKF_K_DETECT, MSKF_K_LK, MSKF_K_EKF_PROPAGATE, MSKF_K_EKF_AUGMENT, MSKF_K_EKF_FEATURES,
-    MSKF_K_EKF_TSQR /* k_ekf_tsqr; rounds 1-3: the stacking-decision kernel, which no longer exists */, MSKF_K_EKF_GEMM, MSKF_K_EKF_CHOL, MSKF_K_EKF_TRSM, MSKF_K_EKF_SMALL, MSKF_K_EKF_REMOVE, MSKF_K_PT_GEOM, MSKF_K_FE_BOOK, MSKF_K_COUNT
+    MSKF_K_EKF_TSQR /* k_ekf_tsqr; rounds 1-3: the stacking-decision kernel, which no longer exists */, MSKF_K_EKF_GEMM, MSKF_K_EKF_CHOL, MSKF_K_EKF_TRSM, MSKF_K_EKF_SMALL, MSKF_K_EKF_REMOVE, MSKF_K_PT_GEOM, MSKF_K_FE_BOOK, MSKF_K_COUNT,
+    /* k_mask_points, the point gate of the image masks (mskf_fe_set_mask), launched behind a track launch only when a stream of that batch
+       has a mask; units: streams.  It takes the slot of MSKF_K_PT_GEOM, which nothing else fills (see above), so MSKF_K_COUNT and the
+       arrays of mskf_ctx_get_timing keep their size. */
+    MSKF_K_FE_MASK = MSKF_K_PT_GEOM
 };
 int mskf_ctx_set_timing(mskf_ctx *ctx, int enable);
 /* Accounting gate (default on): while it is off, launches are not timed and host seconds not accumulated.  Unlike
@@ -268,6 +274,38 @@ enum {
 typedef struct mskf_fe_input_format { int32_t format; int32_t shift; } mskf_fe_input_format;
 int mskf_fe_set_input_format(mskf_stream *s, const mskf_fe_input_format *cfg);
 int mskf_fe_get_input_format(mskf_stream *s, mskf_fe_input_format *out);
+
+/* ---- opt-in per-camera image masks: which pixels are scene
+ * Off by default, and then nothing new runs or is allocated.  A stream may hold one mask per camera (cam0, cam1, each optional)
+ * of the stream's level-0 size: an 8-bit plane with a pitch in which a pixel != 0 is USABLE and 0 is masked out (the opposite of
+ * some other stacks' convention).  `margin` (0 .. 64) erodes the usable set when the mask is set, on the host: a pixel stays
+ * usable iff every pixel of the image within Chebyshev distance `margin` is non-zero; pixels outside the image count as usable.
+ * A detector score at x reads the pixels x - 5 .. x + 4 in both directions, so a mask (or its margin) should reach at least
+ * 5 pixels beyond a hard edge.  DESIGN.md §3 has the contract:
+ *   detector (cam0 mask): a masked-out pixel is never recorded as a cell maximum; everything else (scores, the floor, ties, the
+ *           keys) is unchanged: the per-cell reduction runs over the score map with the masked pixels' scores set to 0.  One
+ *           launch as before, of another instantiation of the kernel, for every push call that has a stream with a cam0 mask;
+ *   point gate: one more launch (MSKF_K_FE_MASK) behind every track launch of a batch that has a masked stream: both track
+ *           launches of a device frame, and mskf_fe_track*.  The pixel of a point is ((int)(x + 0.5f), (int)(y + 0.5f)).  A point
+ *           with status bit 0 whose cam0 pixel (out0) is masked out is lost as a track loses one: status 0, out1 = und0 = und1 = 0,
+ *           out0 kept; otherwise a point with bit 1 whose cam1 pixel (out1) is masked out loses bit 1 and nothing else (as behind
+ *           the epipolar gate).  The bookkeeping drops what the status bits say, so the TrackingInfo counts of a device frame
+ *           count mask losses as tracking (cam0) and matching (cam1) losses.
+ * A new mask applies to the detector from the stream's next push and to the gate from its next track or frame call.
+ * mskf_fe_set_mask validates before it touches anything: MSKF_ERR_INVALID for a null cfg, with a plane given a size other than the
+ * stream's, a pitch below the width or a margin outside 0 .. 64, and while a track or device-frame batch of the stream's context is
+ * pending (mskf_last_error names it); the previous mask then stays in force.  Both planes null = off: the stream's planes are
+ * released and it is exactly as before.  The planes are read during the call (caller memory, a blocking copy); a replaced plane is
+ * released after the context's stream has been synchronised: call it outside a run. */
+typedef struct mskf_fe_mask {
+    const uint8_t *cam0, *cam1;   /* NULL: that camera is not masked */
+    int32_t width, height, pitch; /* of both planes; pitch in bytes */
+    int32_t margin;               /* 0 .. 64 */
+} mskf_fe_mask;
+int mskf_fe_set_mask(mskf_stream *s, const mskf_fe_mask *cfg);
+/* The mask of camera `cam` (0 / 1) as the stream holds it, eroded, one byte per pixel (0 masked out, 255 usable), dense;
+ * *w = *h = 0 when that camera has none (nothing is written to out, which may then be NULL).  No device call. */
+int mskf_fe_get_mask(mskf_stream *s, int cam, uint8_t *out, int capacity, int *w, int *h, int *margin);
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);

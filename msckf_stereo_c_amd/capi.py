@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from .ctypes_types import (CORNER, EQUALIZE_MODES, EkfDirectArgs, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
-                           FeInputFormat, ImuStep, raw_raster)
+                           FeInputFormat, FeMask, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -64,6 +64,7 @@ EXPORTS = [
     "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
+    "mskf_fe_set_mask", "mskf_fe_get_mask",
 ]
 
 
@@ -446,6 +447,31 @@ class Stream:
         self.L.mskf_fe_get_input_format.argtypes = [C.c_void_p, C.POINTER(FeInputFormat)]
         _chk(self.L.mskf_fe_get_input_format(self.h, C.byref(cfg)))
         return cfg.format, cfg.shift
+
+    def set_mask(self, cam0=None, cam1=None, margin=0):
+        """mskf_fe_set_mask: per-camera image masks, (h, w) arrays in which a pixel != 0 is USABLE and 0 is masked out (bool arrays
+        too); None = that camera is not masked, both None = off.  margin (0 .. 64) erodes the usable set; a detector score reads
+        5 pixels around its pixel, so a mask or its margin should reach that far beyond a hard edge.  The detector takes it from the
+        next push on, the point gate from the next track or frame call."""
+        planes = [None if m is None else np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8) for m in (cam0, cam1)]
+        shapes = {m.shape for m in planes if m is not None}
+        if len(shapes) > 1 or any(m.ndim != 2 for m in planes if m is not None):
+            raise MskfError("the masks are 2-D planes of one size", -1)
+        h, w = shapes.pop() if shapes else (0, 0)
+        cfg = FeMask(None if planes[0] is None else planes[0].ctypes.data, None if planes[1] is None else planes[1].ctypes.data, w, h, w, int(margin))
+        self.L.mskf_fe_set_mask.argtypes = [C.c_void_p, C.POINTER(FeMask)]
+        _chk(self.L.mskf_fe_set_mask(self.h, C.byref(cfg)))
+
+    def get_mask(self, cam):
+        """(mask, margin): the eroded mask of camera 0 / 1 as the stream holds it, (h, w) uint8 of 0 / 255, or None without one."""
+        w, h, margin = C.c_int(), C.c_int(), C.c_int()
+        out = np.zeros((self.calib.height, self.calib.width), np.uint8)
+        self.L.mskf_fe_get_mask.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.POINTER(C.c_int)] * 3
+        _chk(self.L.mskf_fe_get_mask(self.h, int(cam), _p(out), out.size, C.byref(w), C.byref(h), C.byref(margin)))
+        if w.value == 0:
+            return None, margin.value
+        assert (h.value, w.value) == out.shape
+        return out, margin.value
 
     def cell_maxima(self):
         n = self.fe_cfg.det_rows * self.fe_cfg.det_cols

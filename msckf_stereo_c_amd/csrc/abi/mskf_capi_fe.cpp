@@ -62,6 +62,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     mskf_t_collect(c);
     for (auto &e : c->t_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (int i = 0; i < 3; ++i) c->desc[i].release();
+    for (int i = 0; i < 2; ++i) c->mask_desc[i].release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
     c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
@@ -481,6 +482,7 @@ extern "C" void mskf_stream_destroy(mskf_stream *s) {
     if (s->book.mem) (void)hipFree(s->book.mem);
     if (s->eq.mem) (void)hipFree(s->eq.mem);
     if (s->px.raw) (void)hipFree(s->px.raw);
+    for (int c = 0; c < 2; ++c) if (s->mask.dev[c]) (void)hipFree(s->mask.dev[c]);
     mskf_ekf_stream_free(s);
     auto &v = s->home_ctx->streams;
     for (size_t i = 0; i < v.size(); ++i) if (v[i] == s) { v.erase(v.begin() + i); break; }
@@ -608,6 +610,86 @@ extern "C" int mskf_fe_get_input_format(mskf_stream *s, mskf_fe_input_format *ou
     return MSKF_OK;
 }
 
+// ---- opt-in image masks (include/mskf_hip.h; erosion, packing and the gate: fe_mask.h)
+static int mask_validate(const mskf_stream *s, const mskf_fe_mask *cfg) {
+    if (!s) return MSKF_ERR_INVALID;
+    if (!cfg) { mskf_set_error("mask: null configuration"); return MSKF_ERR_INVALID; }
+    if (cfg->cam0 || cfg->cam1) {
+        if (cfg->width != s->w || cfg->height != s->h) { mskf_set_error("mask: size differs from the stream's level 0"); return MSKF_ERR_INVALID; }
+        if (cfg->pitch < cfg->width) { mskf_set_error("mask: pitch below the width"); return MSKF_ERR_INVALID; }
+        if (cfg->margin < 0 || cfg->margin > FM_MAX_MARGIN) { mskf_set_error("mask: margin must be 0 .. 64"); return MSKF_ERR_INVALID; }
+    }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_mask(mskf_stream *s, const mskf_fe_mask *cfg) {
+    if (const int rc = mask_validate(s, cfg)) return rc;      // no HIP call before this
+    mskf_stream::Mask M;                                       // everything is decided here, the stream changes at the end
+    const uint8_t *const src[2] = {cfg->cam0, cfg->cam1};
+    const size_t words = (size_t)s->h * fm_pitch_words(s->w);
+    MSKF_HIPCHK(hipSetDevice(s->ctx->device));
+    auto give_up = [&M](hipError_t e) {
+        for (int c = 0; c < 2; ++c) if (M.dev[c]) (void)hipFree(M.dev[c]);
+        mskf_set_error(hipGetErrorString(e));
+        return MSKF_ERR_HIP;
+    };
+    if (src[0] || src[1]) {
+        M.margin = cfg->margin;
+        std::vector<uint8_t> usable((size_t)s->w * s->h);
+        for (int c = 0; c < 2; ++c) {
+            if (!src[c]) continue;
+            fm_erode(src[c], (size_t)cfg->pitch, s->w, s->h, cfg->margin, usable.data());
+            M.host[c].resize(words);
+            fm_pack(usable.data(), s->w, s->h, M.host[c].data());
+            hipError_t e = hipMalloc((void **)&M.dev[c], sizeof(uint32_t) * words);
+            if (e == hipSuccess) e = hipMemcpy(M.dev[c], M.host[c].data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice);     // (caller memory's image: as set_cov)
+            if (e != hipSuccess) return give_up(e);
+        }
+    }
+    if (s->mask.any()) {
+        // launches that still read the old planes finish first (a cold path: call it outside a run)
+        const hipError_t e = hipStreamSynchronize(s->ctx->stream);
+        if (e != hipSuccess) return give_up(e);
+        for (int c = 0; c < 2; ++c) if (s->mask.dev[c]) (void)hipFree(s->mask.dev[c]);
+    }
+    s->mask = std::move(M);
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_mask(mskf_stream *s, int cam, uint8_t *out, int capacity, int *w, int *h, int *margin) {
+    if (!s || cam < 0 || cam > 1 || !w || !h) return MSKF_ERR_INVALID;
+    if (margin) *margin = s->mask.margin;
+    if (!s->mask.dev[cam]) { *w = 0; *h = 0; return MSKF_OK; }
+    if (!out) return MSKF_ERR_INVALID;
+    if ((long long)capacity < (long long)s->w * s->h) return MSKF_ERR_CAPACITY;
+    fm_unpack(s->mask.host[cam].data(), s->w, s->h, out);
+    *w = s->w; *h = s->h;
+    return MSKF_OK;
+}
+
+// The masks of the streams of a launch, element for element beside its descriptors: 0 when no stream has a mask the launch
+// looks at (cam0_only: the detector) and nothing was touched, else the array is staged in mask_desc[which] and *cp is its copy.
+static int stage_masks(mskf_ctx *ctx, int which, int n, mskf_stream *const *streams, bool cam0_only, MskfCopy *cp, bool *any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) *any = *any || streams[i]->mask.dev[0] || (!cam0_only && streams[i]->mask.dev[1]);
+    if (!*any) return MSKF_OK;
+    PinnedDev<FeMaskDev> &A = ctx->mask_desc[which];
+    if (const int rc = A.ensure(n)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        A.h[i] = FeMaskDev{s->mask.dev[0], cam0_only ? nullptr : s->mask.dev[1], fm_pitch_words(s->w), 0};
+    }
+    *cp = MskfCopy{A.d, A.h, sizeof(FeMaskDev) * (size_t)n};
+    return MSKF_OK;
+}
+
+// The point gate behind a track launch over `desc_dev` (the masks staged in mask_desc[1]), timed as MSKF_K_FE_MASK.
+static void mask_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
+    const int ts = mskf_t_begin(ctx, MSKF_K_FE_MASK);
+    fe_launch_mask_points(desc_dev, ctx->mask_desc[1].d, n, max_pts, ctx->stream);
+    mskf_t_end(ctx, ts, n);
+}
+
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
 // 16-bit pixels on 2-byte boundaries.
 static int px_check_images(const mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, long long pitch) {
@@ -682,6 +764,10 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     int n_px = 0;
     for (int i = 0; i < n; ++i) n_px += streams[i]->px.raw ? 2 : 0;
     if (n_px && (rc = ctx->px_jobs.ensure((size_t)n_px)) != MSKF_OK) return rc;
+    // ... and the streams with a cam0 mask (mskf_fe_set_mask): the same holds
+    MskfCopy mask_cp{};
+    bool masked = false;
+    if ((rc = stage_masks(ctx, 0, n, streams, true, &mask_cp, &masked)) != MSKF_OK) return rc;
     if (P.cell_bytes > ctx->cell_arena.cap) { if ((rc = ctx->cell_arena.ensure(P.cell_bytes)) != MSKF_OK) return rc; ctx->cell_keys_dirty = true; }
     // ---- commit: the streams belong to this push from here on
     ++ctx->push_gen;
@@ -736,8 +822,9 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         }
         fill_fe_desc(s, ctx->desc[0].h[i]);
     }
-    MskfCopy cp[4] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
+    MskfCopy cp[5] = {{ctx->jobs.d, ctx->jobs.h, sizeof(Pyr3Job) * 2 * (size_t)n}, {ctx->desc[0].d, ctx->desc[0].h, sizeof(FeStreamDev) * (size_t)n}};
     int n_cp = 2;
+    if (masked) cp[n_cp++] = mask_cp;
     if (eql.n) cp[n_cp++] = {ctx->eq_jobs.d, ctx->eq_jobs.h, sizeof(EqJob) * (size_t)eql.n};
     if (pxl.n) cp[n_cp++] = {ctx->px_jobs.d, ctx->px_jobs.h, sizeof(PxJob) * (size_t)pxl.n};
     if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
@@ -756,7 +843,8 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         ctx->cell_keys_dirty = false;
     }
     ts = mskf_t_begin(ctx, MSKF_K_DETECT);
-    fe_launch_detect(ctx->desc[0].d, n, P.max_w, P.max_h, gen, st);
+    if (masked) fe_launch_detect_masked(ctx->desc[0].d, ctx->mask_desc[0].d, n, P.max_w, P.max_h, gen, st);      // the other instantiation of the same kernel
+    else fe_launch_detect(ctx->desc[0].d, n, P.max_w, P.max_h, gen, st);
     mskf_t_end(ctx, ts, P.px_det);
     if (copy_cells) {
         const MskfCopy out = {ctx->cell_arena.h, ctx->cell_arena.d, P.cell_bytes};
@@ -924,6 +1012,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     }
     if (max_pts <= 0) return MSKF_OK;      // nothing to track: no batch pending, _end is a no-op
     if ((rc = ctx->trk_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->trk_out.ensure(out_bytes)) != MSKF_OK) return rc;
+    MskfCopy mask_cp{};
+    bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind the track
+    if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -942,13 +1033,14 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     DrainOnError drain{st};
     {
         drain.armed = true;
-        const MskfCopy cp[2] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
-        if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+        const MskfCopy cp[3] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, mask_cp};
+        if ((rc = mskf_copy_async(ctx, cp, masked ? 3 : 2)) != MSKF_OK) return rc;
     }
     // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
     const int ts = mskf_t_begin(ctx, MSKF_K_LK);
     fe_launch_track(ctx->desc[1].d, n, max_pts, st);
     mskf_t_end(ctx, ts, 0);
+    if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
     { const MskfCopy cp = {ctx->trk_out.h, ctx->trk_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
     MSKF_HIPCHK(hipGetLastError());
     ctx->pend_trk.n = n; ctx->pend_trk.args = args; ctx->pend_trk.ts = ts;
@@ -1091,6 +1183,9 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         max_cand_est = std::max(max_cand_est, est);
     }
     if ((rc = ctx->book_out.ensure(out_bytes)) != MSKF_OK) return rc;
+    MskfCopy mask_cp{};
+    bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind both track launches
+    if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -1121,19 +1216,21 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         B.x_info = x.info; B.x_id = x.id; B.x_lifetime = x.lifetime; B.x_cam0 = x.cam0; B.x_cam1 = x.cam1; B.x_und0 = x.und0; B.x_und1 = x.und1;
     }
     {
-        const MskfCopy cp[3] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
-                                {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}};
-        if ((rc = mskf_copy_async(ctx, cp, 3)) != MSKF_OK) return rc;
+        const MskfCopy cp[4] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
+                                {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}, mask_cp};
+        if ((rc = mskf_copy_async(ctx, cp, masked ? 4 : 3)) != MSKF_OK) return rc;
     }
     const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
     fe_launch_track(ctx->desc[1].d, n, max_prev, st);
     mskf_t_end(ctx, ts1, 0);
+    if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
     int tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
     const int ts2 = mskf_t_begin(ctx, MSKF_K_LK);
     fe_launch_track(ctx->desc[2].d, n, std::max(max_cand_est, 4), st);
     mskf_t_end(ctx, ts2, 0);
+    if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 1, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);

@@ -8,6 +8,7 @@
 #include "../hip/fe_book.h"
 #include "../hip/fe_equalize.h"
 #include "../hip/fe_pixfmt.h"
+#include "../hip/fe_mask.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -21,6 +22,9 @@ void fe_launch_pyr_down3(const Pyr3Job *jobs_dev, int n_jobs, int max_w0, int ma
 int mskf_wait(mskf_ctx *c);
 void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts, hipStream_t st);
+// image masks (fe_mask.h): masks_dev[i] goes with streams_dev[i]
+void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
+void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);
@@ -150,6 +154,8 @@ struct mskf_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = true;          // false: created by mskf_ctx_create_shared on another context's stream
     PinnedDev<FeStreamDev> desc[3];   // 0: push/detect, 1: track (first track call of a device frame), 2: second track call of a device frame
+    PinnedDev<FeMaskDev> mask_desc[2];   // the streams' image masks, element for element beside desc[0] (push) and beside desc[1] / desc[2] (track calls:
+                                         // one array serves both launches of a device frame); front-end arenas, empty until a stream has a mask
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid
     PinnedDev<char> grid_in;          // staging of mskf_fe_set_grid (synchronous: no batch owns it)
@@ -243,6 +249,13 @@ struct mskf_stream {
         int bpp = 1;
         uint8_t *raw = nullptr;                    // raw staging of host pushes: both cameras, w * h * bpp bytes each (null on GRAY8)
     } px;
+    // ---- opt-in image masks (mskf_fe_set_mask; fe_mask.h): the eroded bit planes, on the device and (for mskf_fe_get_mask) on the host
+    struct Mask {
+        uint32_t *dev[2] = {nullptr, nullptr};     // cam0, cam1; null = not masked
+        std::vector<uint32_t> host[2];
+        int margin = 0;
+        bool any() const { return dev[0] || dev[1]; }
+    } mask;
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

@@ -150,6 +150,30 @@ int main(int argc, char *argv[]) {
 
     const int input_format = system.imgproc_ptr_->inputFormat().format, want_layout = layout_of_format(input_format);
 
+    // image masks (mask_cam0 / mask_cam1 / mask_margin of app_imgproc.yaml): 8-bit grey PNG or PGM of the calibration's size
+    if (system.maskFiles().any()) {
+        const cg::MaskFiles &mf = system.maskFiles();
+        const std::string *const path[2] = {&mf.cam0, &mf.cam1};
+        FileImage plane[2];
+        int w = 0, h = 0;
+        for (int c = 0; c < 2; ++c) {
+            if (path[c]->empty()) continue;
+            if (!load_image(*path[c], plane[c]) || plane[c].raw.empty()) { std::cerr << "ERROR: cannot read the mask " << *path[c] << std::endl; return 2; }
+            if (plane[c].layout != FILE_GRAY8) { std::cerr << "ERROR: the mask " << *path[c] << " holds " << layout_name(plane[c].layout) << ", a mask is an 8-bit grey file" << std::endl; return 2; }
+            const int pw = (int)plane[c].raw.cols(), ph = (int)plane[c].raw.rows();
+            if (pw != system.imgproc_ptr_->imageWidth() || ph != system.imgproc_ptr_->imageHeight()) {
+                std::cerr << "ERROR: the mask " << *path[c] << " is " << pw << " x " << ph << ", not the " << system.imgproc_ptr_->imageWidth() << " x "
+                          << system.imgproc_ptr_->imageHeight() << " of the calibration" << std::endl;
+                return 2;
+            }
+            w = pw; h = ph;
+        }
+        if (system.imgproc_ptr_->setMask(path[0]->empty() ? nullptr : plane[0].raw.data(), path[1]->empty() ? nullptr : plane[1].raw.data(), w, h, w, mf.margin) != MSKF_OK) {
+            std::cerr << "ERROR: the masks " << mf.cam0 << " " << mf.cam1 << " were refused (mask_margin " << mf.margin << "): " << mskf_last_error() << std::endl;
+            return 2;
+        }
+    }
+
     std::vector<std::vector<std::pair<double, std::string>>> data_img(num_cams);
     for (int n = 0; n < num_cams; ++n) {
         std::ifstream cam_file(euroc_dir + "/cam" + std::to_string(n) + "/data.csv");

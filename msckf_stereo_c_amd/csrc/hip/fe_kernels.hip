@@ -5,6 +5,8 @@
 //  k_track4       : cg::optical_flow_multi_level (:410 temporal, :569 stereo) with the prediction (:321-350), the
 //                   image-bounds gates (:416-424, :575-583), the stereo initial guess (:542-548), undistortion and
 //                   the epipolar gate (:587-617): one launch per track call, four points per wavefront.
+//  k_mask_points  : — (opt-in image masks, fe_mask.h): the point gate behind a track launch; k_detect_cells<true> is the
+//                   detector of a push that has a masked stream.
 //
 // Arithmetic contract: every decision-bearing quantity is integer or a fixed
 // sequence of IEEE-754 double operations; this file must be compiled with -ffp-contract=off.
@@ -15,6 +17,7 @@
 #include <stdlib.h>
 #include <mutex>
 #include "fe_device.h"
+#include "fe_mask.h"
 
 // ------------------------------------------------------------------------------------------ pyr_down
 __device__ __forceinline__ int reflect101(int i, int n) {
@@ -313,7 +316,13 @@ __device__ __forceinline__ void det_vadd(const int P[12], int Va[4], int Vb[4], 
 // the one atomicMax.
 // Block -> (stream, four jobs): the jobs (strip, segment) of ONE stream get block ids congruent modulo 8, so an image
 // travels through the L2 of one XCD (blocks b and b + 8 share an XCD).
-__global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams, int n_streams, int strips, int seg_rows, int waves, unsigned int gen) {
+// MASKED (fe_mask.h; launched only when a stream of the push has a cam0 mask): masks[si].mask0 is the stream's bit plane, null
+// = this stream is not masked.  A lane's first output column xs + 4 r is a multiple of 4, so the bits of its four columns
+// are one aligned nibble of one word: one more small load per row, and a pixel whose bit is clear takes no part (its column's
+// best score is not touched either, so the maximum is that of the usable pixels alone).  MASKED = false is the kernel as it
+// was: it never looks at `masks`.
+template <bool MASKED>
+__global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams, const FeMaskDev *masks, int n_streams, int strips, int seg_rows, int waves, unsigned int gen) {
     const int xcd = blockIdx.x & 7, qb = blockIdx.x >> 3;
     const int si = xcd + 8 * (qb / waves), wi = qb - (qb / waves) * waves;
     if (si >= n_streams) return;
@@ -347,6 +356,15 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
         cx[j] = x / cw; xin[j] = x - cx[j] * cw;
         col_ok[j] = job_on && r < DS_LANES && x < W - DET_BORDER;
     }
+    // the lane's mask word of a row: column (xs + 4 r) >> 5 of the plane (a lane right of the image reads the row's last word:
+    // none of its columns is valid)
+    const uint32_t *mrow = nullptr;
+    int mpw = 0, msh = 0;
+    if constexpr (MASKED) {
+        mrow = masks[si].mask0; mpw = masks[si].pitch_w;
+        if (mrow) mrow += min(c0 + 4, W - 1) >> 5;
+        msh = (c0 + 4) & 31;
+    }
     int Va[4] = {0, 0, 0, 0}, Vb[4] = {0, 0, 0, 0}, Vc[4] = {0, 0, 0, 0};
     // ---- fill the window of the first output row: product rows ys - 4 .. ys + 3
     int pr = ys - 4;
@@ -374,9 +392,13 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
         const int y = ys + k;
         const bool row_ok = y < y_end;
         const DetPix enx = load(pr + 3), lnx = load(y - 1);
+        uint32_t nib = 15u;                                      // usable columns of the lane in this row
+        if constexpr (MASKED) { if (mrow) nib = (mrow[(size_t)min(y, H - 1) * mpw] >> msh) & 15u; }
+        if (!MASKED || nib)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (!(col_ok[j] && row_ok)) continue;
+            if (MASKED && !((nib >> j) & 1u)) continue;
             const int a = Va[j], b = Vb[j], d = Vc[j];
             // score > T  <=>  isqrt(disc) < X := a + d - T  <=>  disc < X^2 (X > 0): decided exactly (everything is below
             // 2^50) before the square root.  T = the detection floor or the best score of this column in this cell: a
@@ -460,7 +482,7 @@ __global__ __launch_bounds__(64) void k_detect_cells(const FeStreamDev *streams,
     }
 }
 
-extern "C" void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st) {
+static void det_launch(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st) {
     // rows per segment: short segments give more wavefronts (a launch should fill the device several times over) but every
     // segment pays seven window-filling rows
     const int strips = (max_w - 2 * DET_BORDER + DS_COLS - 1) / DS_COLS, rows = max_h - 2 * DET_BORDER;
@@ -469,7 +491,16 @@ extern "C" void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, 
     while (seg_rows < 128 && (long long)n_streams * strips * ((rows + seg_rows - 1) / seg_rows) / 4 > 32768) seg_rows *= 2;
     const int segs = (rows + seg_rows - 1) / seg_rows;
     const int waves = (strips * segs + 3) / 4;
-    hipLaunchKernelGGL(k_detect_cells, dim3(8 * ((n_streams + 7) / 8) * waves), dim3(64), 0, st, streams_dev, n_streams, strips, seg_rows, waves, gen);
+    if (masks_dev) hipLaunchKernelGGL(k_detect_cells<true>, dim3(8 * ((n_streams + 7) / 8) * waves), dim3(64), 0, st, streams_dev, masks_dev, n_streams, strips, seg_rows, waves, gen);
+    else hipLaunchKernelGGL(k_detect_cells<false>, dim3(8 * ((n_streams + 7) / 8) * waves), dim3(64), 0, st, streams_dev, masks_dev, n_streams, strips, seg_rows, waves, gen);
+}
+extern "C" void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st) {
+    det_launch(streams_dev, nullptr, n_streams, max_w, max_h, gen, st);
+}
+// The masked instantiation: masks_dev[i] goes with streams_dev[i] (a null mask0 = that stream is not masked).
+extern "C" void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st) {
+    if (!masks_dev) return;
+    det_launch(streams_dev, masks_dev, n_streams, max_w, max_h, gen, st);
 }
 
 // ------------------------------------------------------------------------------------------ point math
@@ -1434,4 +1465,33 @@ extern "C" void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, i
     if (max_pts <= 0) return;
     const int gps = (max_pts + 3) / 4;
     hipLaunchKernelGGL(k_track4, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, n_streams, gps);
+}
+
+// ------------------------------------------------------------------------------------------ image masks: the point gate (fe_mask.h)
+// Behind a track launch of a batch that has a masked stream, over the same descriptors: a pure function of the track's outputs.
+// A point whose cam0 pixel is masked out is lost as k_track4 loses one (status 0, out1 = und0 = und1 = 0, out0 kept); else a
+// stereo inlier whose cam1 pixel is masked out loses bit 1, like a point the epipolar gate refuses.  One lane per point, the
+// points of a stream strided over the blocks of its grid row (the count may live on the device: n_pts_dev); streams without
+// a mask return at once.
+__global__ __launch_bounds__(256) void k_mask_points(const FeStreamDev *streams, const FeMaskDev *masks) {
+    const FeMaskDev M = masks[blockIdx.y];
+    if (!M.mask0 && !M.mask1) return;
+    const FeStreamDev &S = streams[blockIdx.y];
+    const int n_pts = S.n_pts_dev ? *S.n_pts_dev : S.n_pts;
+    const int W = S.curr0.w[0], H = S.curr0.h[0];
+    for (int pt = blockIdx.x * 256 + threadIdx.x; pt < n_pts; pt += gridDim.x * 256) {
+        const int st = S.status[pt];
+        if (!(st & 3)) continue;
+        const mskf_point2f p0 = S.out0[pt], p1 = S.out1[pt];
+        int what;
+        const int ns = fm_gate(M.mask0, M.mask1, M.pitch_w, W, H, p0.x, p0.y, p1.x, p1.y, st, &what);
+        if (what == FM_LOST) {
+            S.out1[pt] = mskf_point2f{0.f, 0.f}; S.und0[pt] = mskf_point2f{0.f, 0.f}; S.und1[pt] = mskf_point2f{0.f, 0.f};
+        }
+        if (ns != st) S.status[pt] = (uint8_t)ns;
+    }
+}
+extern "C" void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st) {
+    if (max_pts <= 0 || n_streams <= 0 || !masks_dev) return;
+    hipLaunchKernelGGL(k_mask_points, dim3((max_pts + 255) / 256, n_streams), dim3(256), 0, st, streams_dev, masks_dev);
 }

@@ -233,6 +233,18 @@ int mskfh_runner_set_input_format(void *h, int stream, const mskf_fe_input_forma
     }
     return MSKF_OK;
 }
+// ImageProcessor::setMask (mskf_fe_set_mask) of one stream, or of all (stream < 0); between runs.  Returns the first status that
+// is not MSKF_OK (mskf_last_error has the text): bad arguments refuse at the first stream, which then keeps its previous masks.
+int mskfh_runner_set_mask(void *h, int stream, const mskf_fe_mask *cfg) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) {
+            const int rc = r->system(i).imgproc_ptr_->setMask(cfg->cam0, cfg->cam1, cfg->width, cfg->height, cfg->pitch, cfg->margin);
+            if (rc != MSKF_OK) return rc;
+        }
+    return MSKF_OK;
+}
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
 void mskfh_runner_publish_covariance(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

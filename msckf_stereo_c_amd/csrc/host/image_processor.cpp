@@ -105,6 +105,50 @@ int ImageProcessor::setEqualize(const mskf_fe_equalize &cfg) {
     return rc;
 }
 
+MaskFiles mask_files_from_yaml(const YAML::Node &y) {
+    MaskFiles m;
+    if (y["mask_cam0"].IsDefined()) m.cam0 = y["mask_cam0"].as<std::string>();
+    if (y["mask_cam1"].IsDefined()) m.cam1 = y["mask_cam1"].as<std::string>();
+    if (y["mask_margin"].IsDefined()) m.margin = y["mask_margin"].as<int>();
+    return m;
+}
+
+int ImageProcessor::setMask(const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch, int margin) {
+    if (!initialized_ || !stream_) {      // deferred: initialize() / the stream's creation validates it
+        const uint8_t *const src[2] = {cam0, cam1};
+        MaskKept K;
+        if ((cam0 || cam1) && (width <= 0 || height <= 0 || pitch < width)) { error_ = "setMask: planes need a size and a pitch of at least the width"; return MSKF_ERR_INVALID; }
+        K.w = width; K.h = height; K.margin = margin;
+        for (int c = 0; c < 2; ++c) {
+            if (!src[c]) continue;
+            K.on[c] = true;
+            K.plane[c].resize((size_t)width * height);
+            for (int y = 0; y < height; ++y) std::memcpy(&K.plane[c][(size_t)y * width], src[c] + (size_t)y * pitch, (size_t)width);
+        }
+        mask_kept_ = std::move(K);
+        return MSKF_OK;
+    }
+    const mskf_fe_mask cfg{cam0, cam1, width, height, pitch, margin};
+    const int rc = mskf_fe_set_mask(stream_, &cfg);
+    if (rc != MSKF_OK) fail("mskf_fe_set_mask", rc);      // refused: the stream keeps the masks it had
+    return rc;
+}
+
+int ImageProcessor::applyKeptMask() {
+    MaskKept K = std::move(mask_kept_);
+    mask_kept_ = MaskKept();
+    if (!K.on[0] && !K.on[1]) return MSKF_OK;
+    return setMask(K.on[0] ? K.plane[0].data() : nullptr, K.on[1] ? K.plane[1].data() : nullptr, K.w, K.h, K.w, K.margin);
+}
+
+bool ImageProcessor::mask(int cam, std::vector<uint8_t> &out, int &width, int &height, int &margin) const {
+    width = height = margin = 0;
+    if (!stream_) return false;
+    out.resize((size_t)calib_.width * calib_.height);
+    if (mskf_fe_get_mask(stream_, cam, out.data(), (int)out.size(), &width, &height, &margin) != MSKF_OK || width == 0) { out.clear(); return false; }
+    return true;
+}
+
 ImageProcessor::ImageProcessor(YAML::Node cfg_cam_imu)
     : feature_msg_ptr_(new CameraMeasurement), cfg_cam_imu_(cfg_cam_imu), have_yaml_(true) {
     std::memset(&calib_, 0, sizeof(calib_));
@@ -169,6 +213,8 @@ bool ImageProcessor::initialize() {
     if (stream_ && eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return false;
     // ... and the opt-in input pixel format, likewise
     if (stream_ && (px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return false;
+    // ... and the opt-in image masks, likewise
+    if (stream_ && applyKeptMask() != MSKF_OK) return false;
     return true;
 }
 
@@ -212,6 +258,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         mskf_fe_set_detect_floor(stream_, cfg_.fast_threshold * 256);
         if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return;
         if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return;
+        if (applyKeptMask() != MSKF_OK) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
     if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {

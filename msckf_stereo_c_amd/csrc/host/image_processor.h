@@ -28,6 +28,10 @@ mskf_fe_equalize equalize_from_yaml(const YAML::Node &cfg_imgproc);
 // input_shift: 0 .. 8 (mskf_fe_set_input_format; absent = gray8, 0).  Throws YAML::Exception on an unknown name.
 mskf_fe_input_format input_format_from_yaml(const YAML::Node &cfg_imgproc);
 const char *input_format_name(int format);      // nullptr: no such format
+// ... and the image masks: mask_cam0: <file>, mask_cam1: <file>, mask_margin: 0 .. 64 (mskf_fe_set_mask; absent = off, 0).  The
+// paths are used as given; whoever has an image reader (the app) loads the files and hands the planes to ImageProcessor::setMask.
+struct MaskFiles { std::string cam0, cam1; int margin = 0; bool any() const { return !cam0.empty() || !cam1.empty(); } };
+MaskFiles mask_files_from_yaml(const YAML::Node &cfg_imgproc);
 
 // twoPointRansac of image_processor.cpp:911-1135 on points already undistorted to normalised coordinates; `ransac_draws`
 // is the state of the counter-based draw generator (see ImageProcessor::twoPointRansac)
@@ -97,6 +101,14 @@ class ImageProcessor {
     // With a format other than gray8 a cg::Image carries the raw byte raster (cg_types.h).
     int setInputFormat(const mskf_fe_input_format &cfg);
     const mskf_fe_input_format &inputFormat() const { return px_cfg_; }
+    // opt-in image masks (mskf_fe_set_mask): 8-bit planes of the stream's image size, rows `pitch` bytes apart, a pixel != 0 is
+    // usable; a null plane = that camera is not masked, both null = off.  The planes are copied during the call.  Kept and set
+    // like setEqualize; a refusal leaves the previous masks in force.
+    int setMask(const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch, int margin);
+    // the eroded mask of a camera as the stream holds it (0 / 255 per pixel, dense); false = none.  After the stream exists.
+    bool mask(int cam, std::vector<uint8_t> &out, int &width, int &height, int &margin) const;
+    int imageWidth() const { return calib_.width; }       // the calibration's image size: what a mask has to have
+    int imageHeight() const { return calib_.height; }
     mskf_stream *stream() const { return stream_; }
     void phaseBegin(double time_stamp, int width, int height);      // timestamps, Q2 aliasing, grid size (Q7)
     void phasePrepare1(mskf_fe_track_args &args);                   // first frame: detections; else prev features
@@ -181,6 +193,8 @@ class ImageProcessor {
     bool have_yaml_ = false;
     mskf_fe_equalize eq_cfg_{0, 8, 8, 0, 40.0};
     mskf_fe_input_format px_cfg_{0, 0};
+    struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
+    int applyKeptMask();
     bool initialized_ = false;
     mskf_calib calib_;
     mskf_fe_cfg cfg_;

@@ -12,6 +12,7 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         mskf_fe_cfg fe = fe_cfg_from_yaml(cfg_imgproc);
         equalize_ = equalize_from_yaml(cfg_imgproc);
         input_format_ = input_format_from_yaml(cfg_imgproc);
+        mask_files_ = mask_files_from_yaml(cfg_imgproc);
         const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);

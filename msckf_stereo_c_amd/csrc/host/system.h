@@ -32,6 +32,9 @@ class System {
     void set_feature_msg(const std::shared_ptr<CameraMeasurement> &m) { feature_msg_ptr_ = m; }
     mskf_stream *stream() const { return stream_; }
     bool ok() const { return ok_; }
+    // the mask files app_imgproc.yaml names (mask_files_from_yaml; the YAML constructor reads them): the application loads them
+    // with its image reader and calls imgproc_ptr_->setMask before the first frame
+    const MaskFiles &maskFiles() const { return mask_files_; }
     bool copy_draw_buffers = true;   // backend_callback copies path_/points3d_ every frame in the reference (Q20)
 
   private:
@@ -39,6 +42,7 @@ class System {
     YAML::Node cfg_cam_imu_;
     mskf_fe_input_format input_format_{0, 0};          // likewise (input_format_from_yaml)
     mskf_fe_equalize equalize_{0, 8, 8, 0, 40.0};      // the YAML constructor reads it from app_imgproc.yaml (equalize_from_yaml)
+    MaskFiles mask_files_;
     std::shared_ptr<CameraMeasurement> feature_msg_ptr_;
     cg::MsckfVioPtr msckfvio_ptr_;
     mskf_ctx *own_ctx_ = nullptr;

@@ -98,6 +98,15 @@ INPUT_FORMATS = {"gray8": 0, "gray16": 1, "rgb8": 2, "bgr8": 3, "rgba8": 4, "bgr
 INPUT_FORMAT_BPP = [1, 2, 3, 3, 4, 4, 1, 1, 1, 1]
 
 
+class FeMask(C.Structure):
+    """mskf_fe_mask (include/mskf_hip.h): per-camera image masks, a pixel != 0 is usable; a null plane = that camera is not masked."""
+    _fields_ = [("cam0", C.c_void_p), ("cam1", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("margin", C.c_int32)]
+
+
+assert C.sizeof(FeMask) == 32
+MASK_MAX_MARGIN = 64         # FM_MAX_MARGIN (csrc/hip/fe_mask.h)
+
+
 def raw_raster(img, fmt):
     """An image in format number fmt as the contiguous array a push takes: (h, w) uint16 for gray16 (native byte order, which the
     device reads as little-endian), (h, w, 3 | 4) uint8 for the colour formats, (h, w) uint8 otherwise.  A wrong shape or a

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .capi import MskfError
-from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat,
+from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat, FeMask,
                            ImuSample, TrackingInfo, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -208,6 +208,22 @@ class Runner:
         (global histogram equalisation), "clahe" / 2 with tiles = (tiles_x, tiles_y) and clip_limit.  Call before the first frame."""
         cfg = FeEqualize(int(EQUALIZE_MODES.get(mode, mode)), int(tiles[0]), int(tiles[1]), 0, float(clip_limit))
         rc = self.L.mskfh_runner_set_equalize(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
+    def set_mask(self, cam0=None, cam1=None, margin=0, stream=None):
+        """Opt-in image masks of one stream or of all (mskf_fe_set_mask): (h, w) arrays in which a pixel != 0 is USABLE and 0 is
+        masked out; None = that camera is not masked, both None = off.  margin (0 .. 64) erodes the usable set.  The detector
+        records no masked-out cam0 pixel, tracked points that land on a masked-out pixel are dropped.  Call between runs."""
+        planes = [None if m is None else np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8) for m in (cam0, cam1)]
+        shapes = {m.shape for m in planes if m is not None}
+        if len(shapes) > 1 or any(m.ndim != 2 for m in planes if m is not None):
+            raise MskfError("the masks are 2-D planes of one size", -1)
+        h, w = shapes.pop() if shapes else (0, 0)
+        cfg = FeMask(None if planes[0] is None else planes[0].ctypes.data, None if planes[1] is None else planes[1].ctypes.data, w, h, w, int(margin))
+        self.L.mskfh_runner_set_mask.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeMask)]
+        rc = self.L.mskfh_runner_set_mask(self.h, -1 if stream is None else int(stream), C.byref(cfg))
         if rc != 0:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
