@@ -96,6 +96,9 @@ void orc_distort(const double K[4], const double D[4], int model, int n, const m
     CamModel c; for (int i = 0; i < 4; ++i) { c.K[i] = K[i]; c.D[i] = D[i]; } c.model = model;
     for (int i = 0; i < n; ++i) distort_point(c, in[i].x, in[i].y, out[i].x, out[i].y);
 }
+// the deterministic atan / tan of the equidistant model (o_math.h) as doubles, for the accuracy sweep of the tests
+void orc_det_atan(int n, const double *in, double *out) { for (int i = 0; i < n; ++i) out[i] = det_atan(in[i]); }
+void orc_det_tan(int n, const double *in, double *out) { for (int i = 0; i < n; ++i) out[i] = det_tan(in[i]); }
 
 // stereoMatch on a fresh image pair (image_processor.cpp:534-620): cam1 initial guess by projection
 void orc_stereo_match(const mskf_calib *calib, const mskf_fe_cfg *cfg, const uint8_t *cam0, const uint8_t *cam1, int n,

@@ -301,7 +301,10 @@ inline bool chol_solve(Mat S, Mat &B) {
 // Deterministic atan / tan for the equidistant (fisheye) camera model.  cv::fisheye::distortPoints needs atan(r),
 // cv::fisheye::undistortPoints needs tan(theta); libm and the GPU math library do not round them identically, so both
 // sides evaluate the SAME sequence of IEEE double operations (+ - * / only, no contraction): argument reduction to a
-// small interval and an odd Taylor polynomial.  Accuracy ~2e-16 relative (checked against libm in the tests).
+// small interval and an odd Taylor polynomial.  Accuracy as doubles: within 8 * 2^-53 = 8.9e-16 relative of tanl on
+// (0, pi/2] and of atanl on (0, 1e300) (observed 4.5e-16 / 4.1e-16; tests/test_camera_reference.py sweeps oracle/o_math.h's
+// copy); through the camera models the float32 outputs equal the rounded long-double model
+// (tests/test_gpu_camera_geometry.py on the device).
 
 // atan(x), x >= 0:  x > 1 -> pi/2 - atan(1/x);  then atan(x) = atan(c) + atan((x - c) / (1 + x c)) with the nearest
 // c in {0, 1/4, 1/2, 3/4, 1} (|z| <= 1/8 -> 11 odd terms leave < 1e-21)
@@ -329,10 +332,12 @@ static inline double det_atan(double x) {
     const double a = ac + z * p;
     return inv ? 1.5707963267948966192 - a : a;
 }
-// tan(t), 0 <= t <= pi/2:  t > pi/4 -> 1 / tan(pi/2 - t);  tan = sin / cos with Taylor series on [0, pi/4]
+// tan(t), 0 <= t <= pi/2:  t > pi/4 -> 1 / tan(pi/2 - t);  tan = sin / cos with Taylor series on [0, pi/4].  pi/2 is taken
+// in two parts (the double nearest it, whose difference with t is exact for t >= pi/4, plus the 6.1e-17 that double lacks):
+// with one part the reduced argument is 0 at the double pi/2, where undistort_pt clamps theta_d, and tan there is inf.
 static inline double det_tan(double t) {
     const bool inv = t > 0.78539816339744830962;
-    if (inv) t = 1.5707963267948966192 - t;
+    if (inv) t = (1.5707963267948966192 - t) + 6.123233995736766e-17;
     const double t2 = t * t;
     double s = 1.0 / 121645100408832000.0;              // 1/19!
     s = 1.0 / 355687428096000.0 - t2 * s;                // 1/17!

@@ -334,6 +334,17 @@ def distort(K, D, pts, model=0):
     return out
 
 
+def det_trig(name, x):
+    """det_atan (x >= 0) / det_tan (0 <= t <= pi/2) of o_math.h on doubles: the operation sequence of the device functions."""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros_like(a)
+    f = getattr(lib(), {"atan": "orc_det_atan", "tan": "orc_det_tan"}[name])
+    f.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    f.restype = None
+    f(a.size, _p(a), _p(out))
+    return out
+
+
 def stereo_match(calib, fe_cfg, cam0, cam1, pts0):
     a = np.ascontiguousarray(pts0, dtype=np.float32).reshape(-1, 2)
     b = np.zeros_like(a)
