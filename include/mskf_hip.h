@@ -45,7 +45,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  mskf_fe_set_equalize, mskf_fe_get_equalize; mskf_fe_set_input_format, mskf_fe_get_input_format;
                                  mskf_ekf_update_direct, _batch, _batch_begin, _batch_end (with their own mskf_ekf_direct_args);
                                  mskf_fe_set_mask, mskf_fe_get_mask (with their own mskf_fe_mask) and the timing kind MSKF_K_FE_MASK, which is the
-                                 slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged) */
+                                 slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged);
+                                 mskf_fe_describe, _batch, _batch_begin, _batch_end (with their own mskf_fe_describe_args), mskf_fe_descriptor_pattern */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -309,6 +310,36 @@ int mskf_fe_get_mask(mskf_stream *s, int cam, uint8_t *out, int capacity, int *w
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);
+
+/* ---- opt-in 256-bit binary descriptors of points of a resident level-0 image ("Descriptors")
+ * Nothing runs or is allocated for a context that never calls these.  A descriptor is upright, single-scale BRIEF: 256 tests
+ * (ax, ay, bx, by), offsets within -12 .. 12 (mskf_fe_descriptor_pattern), over 5 x 5 box sums S of the image with a replicated
+ * border; for a point (x, y) in level-0 pixels the centre is ((int)(x + 0.5f), (int)(y + 0.5f)), the point is valid iff
+ * 0 <= x + 0.5f < width and 0 <= y + 0.5f < height in float32 (false for NaN), and bit t, in byte t >> 3 at bit t & 7, is
+ * S(c + a_t) < S(c + b_t), strictly.  An invalid point gets 32 zero bytes and valid 0, a valid one valid 1.  Descriptors are
+ * compared by Hamming distance.
+ * The image is the stream's level 0 of `role` as mskf_fe_get_level returns it (equalised or converted where those options are on;
+ * a mask does not enter); a borrowed device image (on_device 2) is read in place, under the duty to keep it valid that the push
+ * states.  Points and results travel through arenas of the call's own: one copy in, one launch (k_fe_describe, one wavefront per
+ * point; not timed, there is no MSKF_K_* kind for it) and one copy out for the whole batch.
+ * Everything is validated before anything is touched.  MSKF_ERR_INVALID, mskf_last_error naming the reason: a null argument, role
+ * outside 0 .. 2, a role whose image the stream does not hold yet (nothing pushed, or no previous image), n < 0, null pts, desc or
+ * valid with n > 0, a stream of another context, and while a track, device-frame or describe batch of the context is pending.
+ * Pushes and frames enqueued after _begin run behind it on the context's stream: the image pointers are resolved at _begin.  A
+ * batch whose every n is 0 is MSKF_OK and leaves nothing pending.  The args and their arrays stay valid until _end. */
+typedef struct mskf_fe_describe_args {
+    int32_t role;              /* image, as mskf_fe_get_level: 0 prev cam0, 1 curr cam0, 2 curr cam1 */
+    int32_t n;                 /* points, >= 0 */
+    const mskf_point2f *pts;   /* in: level-0 pixels */
+    uint8_t *desc;             /* out: 32 n bytes */
+    uint8_t *valid;            /* out: n bytes */
+} mskf_fe_describe_args;
+int mskf_fe_describe(mskf_stream *s, mskf_fe_describe_args *args);          /* batch of one; synchronises */
+int mskf_fe_describe_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args);
+int mskf_fe_describe_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args);
+int mskf_fe_describe_batch_end(mskf_ctx *ctx);
+/* ax, ay, bx, by of test 0, 1, .. 255; no device call */
+void mskf_fe_descriptor_pattern(int8_t out[1024]);
 
 /* ------------------------------------------------------------------ EKF (covariance resident in HBM)
  * Replaces, inside cg::MsckfVio (msckf_vio.cpp):

@@ -24,6 +24,7 @@ HIP_SRCS = [
     "hip/ekf_kernels.hip",
     "hip/ekf_linalg.hip",
     "hip/ekf_direct.hip",
+    "hip/fe_describe.hip",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_ekf.cpp",
 ]

@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import (CORNER, EQUALIZE_MODES, EkfDirectArgs, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
+from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
                            FeInputFormat, FeMask, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -65,6 +65,7 @@ EXPORTS = [
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
     "mskf_fe_set_mask", "mskf_fe_get_mask",
+    "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
 ]
 
 
@@ -138,6 +139,25 @@ def _pts(a):
     return np.ascontiguousarray(a) if a.dtype == POINT2F else np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 2).view(POINT2F).reshape(-1)
 
 
+def descriptor_pattern():
+    """mskf_fe_descriptor_pattern: the 256 tests of the descriptor, (256, 4) int8 of ax, ay, bx, by.  No device call."""
+    out = np.zeros((256, 4), np.int8)
+    L = lib()
+    L.mskf_fe_descriptor_pattern.argtypes = [C.c_void_p]
+    L.mskf_fe_descriptor_pattern.restype = None
+    L.mskf_fe_descriptor_pattern(_p(out))
+    return out
+
+
+def _describe_args(role, pts):
+    """(mskf_fe_describe_args, buffers it points into, (desc, valid) the call fills) for one stream."""
+    pts = _pts(np.zeros((0, 2), np.float32) if pts is None else pts)
+    n = len(pts)
+    desc, valid = np.zeros((n, DESCRIPTOR_BYTES), np.uint8), np.zeros(n, np.uint8)
+    a = FeDescribeArgs(int(role), n, pts.ctypes.data if n else None, desc.ctypes.data if n else None, valid.ctypes.data if n else None)
+    return a, pts, (desc, valid)
+
+
 def _imu_steps(steps):
     """mskf_imu_step records as a contiguous IMU_STEP array (None / empty: no steps)."""
     if steps is None:
@@ -161,6 +181,7 @@ class Context:
         self._trk_pending = None
         self._frame_pending = None
         self._direct_pending = None
+        self._dsc_pending = None
 
     def close(self):
         if self.h:
@@ -208,6 +229,29 @@ class Context:
         self.L.mskf_fe_track_batch_end.argtypes = [C.c_void_p]
         _chk(self.L.mskf_fe_track_batch_end(self.h))
         self._trk_pending = None
+
+    def describe_batch(self, streams, roles, pts_list):
+        """One mskf_fe_describe_batch: 256-bit descriptors of pts_list[i] (n x 2 level-0 pixels, None = none) on the image roles[i]
+        (0 prev cam0, 1 curr cam0, 2 curr cam1) of streams[i].  Returns [(desc uint8[n, 32], valid uint8[n])]."""
+        out = self.describe_batch_begin(streams, roles, pts_list)
+        self.describe_batch_end()
+        return out
+
+    def describe_batch_begin(self, streams, roles, pts_list):
+        """mskf_fe_describe_batch_begin: enqueue the batch; the returned arrays are filled by describe_batch_end."""
+        n = len(streams)
+        built = [_describe_args(r, p) for r, p in zip(roles, pts_list)]
+        args = (FeDescribeArgs * n)(*[b[0] for b in built])
+        hs = _handles(streams)
+        self.L.mskf_fe_describe_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(FeDescribeArgs)]
+        _chk(self.L.mskf_fe_describe_batch_begin(self.h, n, hs, args))
+        self._dsc_pending = (built, args, hs)          # must stay alive until _end
+        return [b[2] for b in built]
+
+    def describe_batch_end(self):
+        self.L.mskf_fe_describe_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_fe_describe_batch_end(self.h))
+        self._dsc_pending = None
 
     def push_stereo_batch(self, streams, cam0s, cam1s, on_device=0):
         """One mskf_fe_push_stereo_batch: host images (on_device = 0) or device addresses (1: copied, 2: borrowed)."""
@@ -472,6 +516,14 @@ class Stream:
             return None, margin.value
         assert (h.value, w.value) == out.shape
         return out, margin.value
+
+    def describe(self, role, pts):
+        """mskf_fe_describe: the 256-bit descriptors of pts (n x 2, level-0 pixels) on the image `role` (0 prev cam0, 1 curr cam0,
+        2 curr cam1) as get_level(role, 0) returns it.  Returns (desc uint8[n, 32], valid uint8[n]); synchronises."""
+        a, _keep, out = _describe_args(role, pts)
+        self.L.mskf_fe_describe.argtypes = [C.c_void_p, C.POINTER(FeDescribeArgs)]
+        _chk(self.L.mskf_fe_describe(self.h, C.byref(a)))
+        return out
 
     def cell_maxima(self):
         n = self.fe_cfg.det_rows * self.fe_cfg.det_cols

@@ -67,6 +67,8 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
     if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
+    c->dsc_jobs.release(); c->dsc_in.release(); c->dsc_out.release();
+    if (c->pend_dsc.done) (void)hipEventDestroy(c->pend_dsc.done);
     c->ekf_desc.release();
     c->pred_arena.release();
     if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
@@ -264,7 +266,7 @@ extern "C" int mskf_ctx_set_timing(mskf_ctx *c, int enable) {
 
 extern "C" int mskf_ctx_set_wait_mode(mskf_ctx *c, int block) {
     if (!c) return MSKF_ERR_INVALID;
-    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
+    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
     c->wait_block = block != 0;
     return MSKF_OK;
 }
@@ -784,6 +786,7 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         s->lvl0[s->i_curr0] = borrow ? cam0[i] : nullptr;
         s->lvl0[s->i_curr1] = borrow ? cam1[i] : nullptr;
         s->has_curr = true;
+        s->held[s->i_curr0] = s->held[s->i_curr1] = true;
     }
     // ---- enqueue: level 0 of both cameras unless it is borrowed or already there, then the levels 1 .. 3 of both cameras of
     // every stream in ONE launch (k_pyr_down3), its jobs staged together with the detector's descriptors
@@ -1301,4 +1304,105 @@ extern "C" int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *o
     if (w) *w = s->lw[level];
     if (h) *h = s->lh[level];
     return MSKF_OK;
+}
+
+// ------------------------------------------------------------------------------------------ descriptors (fe_brief.h)
+extern "C" void mskf_fe_descriptor_pattern(int8_t out[4 * FB_TESTS]) {
+    static constexpr FbPattern pat = fb_make_pattern();
+    if (out) std::memcpy(out, pat.t, sizeof(pat.t));
+}
+
+static int refuse_describe(const char *why) { mskf_set_error(std::string("describe: ") + why); return MSKF_ERR_INVALID; }
+
+// One stream's block of a describe batch: np points in dsc_in, FB_BYTES * np descriptor bytes and np validity bytes in dsc_out.
+static inline size_t describe_in_bytes(size_t np) { return (sizeof(mskf_point2f) * np + 63) & ~(size_t)63; }
+static inline size_t describe_out_bytes(size_t np) { return ((FB_BYTES + 1) * np + 63) & ~(size_t)63; }
+
+extern "C" int mskf_fe_describe_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args) {
+    // ---- plan: every refusal comes from here, before anything is touched
+    if (!ctx || !streams || !args) return refuse_describe("null argument");
+    if (n <= 0) return refuse_describe("a batch has at least one stream");
+    if (const int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE)) return rc;
+    if (ctx->pend_dsc.active) return refuse_describe("a describe batch of this context is still pending (call mskf_fe_describe_batch_end)");
+    size_t in_bytes = 0, out_bytes = 0;
+    int max_pts = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        const mskf_fe_describe_args &a = args[i];
+        if (!s) return refuse_describe("null stream");
+        if (s->ctx != ctx) return refuse_describe("a stream of another context");
+        if (a.role < 0 || a.role > 2) return refuse_describe("role must be 0 (prev cam0), 1 (curr cam0) or 2 (curr cam1)");
+        if (a.n < 0) return refuse_describe("negative point count");
+        if (a.n > 0 && (!a.pts || !a.desc || !a.valid)) return refuse_describe("null pts, desc or valid with n > 0");
+        const int idx = a.role == 0 ? s->i_prev0 : (a.role == 1 ? s->i_curr0 : s->i_curr1);
+        if (!s->held[idx]) return refuse_describe(a.role == 0 ? "the stream holds no previous image yet" : "no stereo pair pushed yet");
+        in_bytes += describe_in_bytes((size_t)a.n);
+        out_bytes += describe_out_bytes((size_t)a.n);
+        max_pts = std::max(max_pts, a.n);
+    }
+    if (max_pts <= 0) return MSKF_OK;      // nothing to describe: no batch pending, _end is a no-op
+    // ---- grow
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ctx->dsc_jobs.ensure(n)) != MSKF_OK || (rc = ctx->dsc_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->dsc_out.ensure(out_bytes)) != MSKF_OK) return rc;
+    std::vector<size_t> &out_off = ctx->pend_dsc.out_off;      // (no batch is pending: nobody reads it)
+    out_off.resize(n);
+    size_t in_off = 0, o_off = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        const mskf_fe_describe_args &a = args[i];
+        const size_t np = (size_t)a.n;
+        const int idx = a.role == 0 ? s->i_prev0 : (a.role == 1 ? s->i_curr0 : s->i_curr1);
+        FeDescribeDev &j = ctx->dsc_jobs.h[i];
+        j.img = s->lvl0[idx] ? s->lvl0[idx] : s->pyr[idx] + s->lvl_off[0];
+        j.w = s->w; j.h = s->h; j.pitch = s->w;
+        if (np) std::memcpy(ctx->dsc_in.h + in_off, a.pts, sizeof(mskf_point2f) * np);
+        j.pts = (const float *)(ctx->dsc_in.d + in_off);
+        j.n = a.n; j.pad_ = 0;
+        j.desc = (uint8_t *)(ctx->dsc_out.d + o_off);
+        j.valid = j.desc + FB_BYTES * np;
+        out_off[i] = o_off;
+        in_off += describe_in_bytes(np); o_off += describe_out_bytes(np);
+    }
+    // ---- enqueue: one copy in, one launch, one copy out
+    DrainOnError drain{ctx->stream, true};
+    const MskfCopy cp[2] = {{ctx->dsc_in.d, ctx->dsc_in.h, in_bytes}, {ctx->dsc_jobs.d, ctx->dsc_jobs.h, sizeof(FeDescribeDev) * (size_t)n}};
+    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+    fe_launch_describe(ctx->dsc_jobs.d, n, max_pts, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
+    { const MskfCopy out = {ctx->dsc_out.h, ctx->dsc_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
+    MSKF_HIPCHK(hipGetLastError());
+    ctx->pend_dsc.n = n; ctx->pend_dsc.args = args;
+    if ((rc = mskf_batch_arm(ctx, ctx->pend_dsc)) != MSKF_OK) return rc;
+    drain.armed = false;
+    return MSKF_OK;
+}
+
+// Wait for the batch started by mskf_fe_describe_batch_begin and copy its results into the args given there.  No-op when nothing
+// is pending.
+extern "C" int mskf_fe_describe_batch_end(mskf_ctx *ctx) {
+    if (!ctx) return MSKF_ERR_INVALID;
+    mskf_ctx::PendingDescribe &D = ctx->pend_dsc;
+    if (!D.active) return MSKF_OK;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    if (const int rc = mskf_batch_finish(ctx, D)) return rc;
+    for (int i = 0; i < D.n; ++i) {
+        const mskf_fe_describe_args &a = D.args[i];
+        const size_t np = (size_t)a.n;
+        if (!np) continue;
+        const char *src = ctx->dsc_out.h + D.out_off[i];
+        std::memcpy(a.desc, src, FB_BYTES * np);
+        std::memcpy(a.valid, src + FB_BYTES * np, np);
+    }
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_describe_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args) {
+    const int rc = mskf_fe_describe_batch_begin(ctx, n, streams, args);
+    return rc != MSKF_OK ? rc : mskf_fe_describe_batch_end(ctx);
+}
+
+extern "C" int mskf_fe_describe(mskf_stream *s, mskf_fe_describe_args *args) {
+    if (!s || !args) return refuse_describe("null argument");
+    mskf_stream *ss[1] = {s};
+    return mskf_fe_describe_batch(s->ctx, 1, ss, args);
 }

@@ -9,6 +9,7 @@
 #include "../hip/fe_equalize.h"
 #include "../hip/fe_pixfmt.h"
 #include "../hip/fe_mask.h"
+#include "../hip/fe_brief.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -25,6 +26,8 @@ void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts,
 // image masks (fe_mask.h): masks_dev[i] goes with streams_dev[i]
 void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
+// descriptors (fe_brief.h): jobs of any size and count in one launch; max_pts = the largest count
+void fe_launch_describe(const FeDescribeDev *jobs_dev, int n_jobs, int max_pts, hipStream_t st);
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);
@@ -106,6 +109,7 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 
 // Which pending batch owns which arenas of the context:
 //   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
+//   a pending describe batch owns dsc_jobs, dsc_in and dsc_out, which nothing else touches: only a describe call refuses for it;
 //   a pending update (a feature update or a direct update: one slot for both kinds) owns ekf_desc, upd_in and upd_out;
 //   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
 //   descriptors from and writes results into the host side).
@@ -193,6 +197,13 @@ struct mskf_ctx {
         bool direct = false; struct mskf_ekf_direct_args *dargs = nullptr;
         std::vector<size_t> d_out;             // direct: byte offset of each stream's results in upd_out
     } pend_upd;
+    // descriptors (mskf_fe_describe_batch_*; fe_brief.h): arenas of the call's own, empty until the first call, owned by pend_dsc
+    PinnedDev<FeDescribeDev> dsc_jobs;
+    PinnedDev<char> dsc_in, dsc_out;     // the points / desc + valid of every stream of a describe batch (one copy each way)
+    struct PendingDescribe : PendingBatch {
+        int n = 0; struct mskf_fe_describe_args *args = nullptr;
+        std::vector<size_t> out_off;           // per stream: byte offset of its results in dsc_out
+    } pend_dsc;
     // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
     struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;
 };
@@ -226,6 +237,7 @@ struct mskf_stream {
     const uint8_t *lvl0[3] = {nullptr, nullptr, nullptr};   // level 0 of each pyramid: own buffer or a borrowed device image
     int i_prev0 = 0, i_curr0 = 1, i_curr1 = 2;
     bool has_curr = false;
+    bool held[3] = {false, false, false};   // pyr[i] (or lvl0[i]) holds an image a push has enqueued (mskf_fe_describe refuses a role without one)
     int pt_cap = 0;
     size_t cell_off = 0;              // slice of ctx->cell_arena
     unsigned long long push_gen = 0;

@@ -245,6 +245,21 @@ int mskfh_runner_set_mask(void *h, int stream, const mskf_fe_mask *cfg) {
         }
     return MSKF_OK;
 }
+// ImageProcessor::setDescriptors of one stream, or of all (stream < 0); between runs, from the next frame on
+int mskfh_runner_set_descriptors(void *h, int stream, int on) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i) if (stream < 0 || i == stream) r->system(i).imgproc_ptr_->setDescriptors(on != 0);
+    return MSKF_OK;
+}
+// the descriptors of the stream's last frame, aligned with its message: ids, 32 bytes each, validity; 0 entries with the option off
+int mskfh_num_descriptors(void *h, int stream) { return (int)((MultiRunner *)h)->system(stream).imgproc_ptr_->descriptorIds().size(); }
+void mskfh_get_descriptors(void *h, int stream, uint64_t *ids, uint8_t *desc, uint8_t *valid) {
+    const ImageProcessor &ip = *((MultiRunner *)h)->system(stream).imgproc_ptr_;
+    const size_t n = ip.descriptorIds().size();
+    for (size_t i = 0; i < n; ++i) ids[i] = ip.descriptorIds()[i];
+    if (n) { std::memcpy(desc, ip.descriptors().data(), 32 * n); std::memcpy(valid, ip.descriptorValid().data(), n); }
+}
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
 void mskfh_runner_publish_covariance(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

@@ -113,6 +113,47 @@ MaskFiles mask_files_from_yaml(const YAML::Node &y) {
     return m;
 }
 
+bool descriptors_from_yaml(const YAML::Node &y) {
+    if (!y["descriptors"].IsDefined()) return false;
+    const std::string m = y["descriptors"].as<std::string>();
+    if (m != "off" && m != "brief256") throw YAML::Exception("yaml: descriptors must be off or brief256, not " + m);
+    return m == "brief256";
+}
+
+// The frame has been published and rotated on both paths (the device frame swaps inside its call, the phased frame at the end of
+// phaseAfter2): the grid is prev_, in message order, and its image is the stream's previous cam0 (role 0).
+void ImageProcessor::describePrepare(mskf_fe_describe_args &a) {
+    const size_t n = prev_.size();
+    desc_ids_.assign(prev_.id.begin(), prev_.id.end());
+    desc_.assign(32 * n, 0); desc_valid_.assign(n, 0);
+    a.role = 0; a.n = (int)n;
+    a.pts = prev_.cam0.data(); a.desc = desc_.data(); a.valid = desc_valid_.data();
+}
+
+void ImageProcessor::describeDone() {
+    if (!desc_out_.is_open()) return;
+    static const char hex[] = "0123456789abcdef";
+    std::string line(64, '0');
+    for (size_t i = 0; i < desc_ids_.size(); ++i) {
+        for (int b = 0; b < 32; ++b) { const uint8_t v = desc_[32 * i + b]; line[2 * b] = hex[v >> 4]; line[2 * b + 1] = hex[v & 15]; }
+        desc_out_ << std::fixed << std::setprecision(9) << cam0_curr_time << " " << desc_ids_[i] << " " << line << "\n";
+    }
+    desc_out_.flush();
+}
+
+int ImageProcessor::describeFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, FrameScratch &s, std::string &err) {
+    s.da.clear(); s.ds.clear();
+    for (int i = 0; i < n; ++i) {
+        if (!ip[i]->descriptors_) continue;
+        s.da.emplace_back();
+        ip[i]->describePrepare(s.da.back());
+        s.ds.push_back(streams[i]);
+    }
+    FRAME_CHK(mskf_fe_describe_batch, (ctx, (int)s.ds.size(), s.ds.data(), s.da.data()));
+    for (int i = 0; i < n; ++i) if (ip[i]->descriptors_) ip[i]->describeDone();
+    return MSKF_OK;
+}
+
 int ImageProcessor::setMask(const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch, int margin) {
     if (!initialized_ || !stream_) {      // deferred: initialize() / the stream's creation validates it
         const uint8_t *const src[2] = {cam0, cam1};
@@ -180,6 +221,7 @@ bool ImageProcessor::loadParameters() {
         cfg_ = fe_cfg_from_yaml(cfg_imgproc);
         eq_cfg_ = equalize_from_yaml(cfg_imgproc);
         px_cfg_ = input_format_from_yaml(cfg_imgproc);
+        descriptors_ = descriptors_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
     processor_config.grid_col = cfg_.grid_col;
@@ -278,6 +320,8 @@ int ImageProcessor::runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, ms
                              const uint8_t *const *cam1, int on_device, const double *t, bool is_draw, FrameScratch &s, const ParFor &par,
                              double *acc, std::string &err) {
     PhaseLaps lap(acc);
+    bool describing = false;                       // (off by default: nothing below the frame then runs)
+    for (int i = 0; i < n; ++i) describing |= ip[i]->descriptors_;
     // Every frame after a stream's first runs as ONE device call (mskf_fe_frame_batch_*): pyramids, detector, both track calls
     // and the bookkeeping between and after them; the host prepares the prediction and takes the grid.
     bool all_dev = true;
@@ -293,6 +337,7 @@ int ImageProcessor::runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, ms
         FRAME_CHK(mskf_fe_frame_batch_end, (ctx));
         lap(PH_TRACK1);
         par_for(par, n, [&](int i) { ip[i]->frameEnd(s.fa[i], is_draw); });
+        if (describing) { const int rc = describeFrame(ctx, n, ip, streams, s, err); if (rc != MSKF_OK) return rc; }
         lap(PH_AFTER2);
         return MSKF_OK;
     }
@@ -318,6 +363,7 @@ int ImageProcessor::runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, ms
     if (any2 && (rc = track(s.a2)) != MSKF_OK) return rc;
     lap(PH_TRACK2);
     par_for(par, n, [&](int i) { ip[i]->phaseAfter2(is_draw); });
+    if (describing && (rc = describeFrame(ctx, n, ip, streams, s, err)) != MSKF_OK) return rc;
     lap(PH_AFTER2);
     return MSKF_OK;
 }

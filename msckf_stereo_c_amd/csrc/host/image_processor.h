@@ -32,6 +32,9 @@ const char *input_format_name(int format);      // nullptr: no such format
 // paths are used as given; whoever has an image reader (the app) loads the files and hands the planes to ImageProcessor::setMask.
 struct MaskFiles { std::string cam0, cam1; int margin = 0; bool any() const { return !cam0.empty() || !cam1.empty(); } };
 MaskFiles mask_files_from_yaml(const YAML::Node &cfg_imgproc);
+// ... and descriptors: off | brief256 (absent = off): 256-bit binary descriptors of the published features (mskf_fe_describe_batch),
+// with descriptors_out: <file> for their text output (which turns them on).  Throws YAML::Exception on an unknown value.
+bool descriptors_from_yaml(const YAML::Node &cfg_imgproc);
 
 // twoPointRansac of image_processor.cpp:911-1135 on points already undistorted to normalised coordinates; `ransac_draws`
 // is the state of the counter-based draw generator (see ImageProcessor::twoPointRansac)
@@ -85,7 +88,12 @@ class ImageProcessor {
     // (mskf_fe_frame_batch_*) when every stream canDeviceFrame(), otherwise phased for all.  Image size: the streams' own.
     // `par` shares the per-stream host phases, `acc` (or nullptr) receives the wall time per PH_* phase.  Returns the
     // status of the call that failed and its name in `err`.
-    struct FrameScratch { std::vector<mskf_fe_track_args> a1, a2; std::vector<mskf_fe_frame_args> fa; };   // argument records, valid until the call's *_end
+    // With descriptors on for any stream of the group (setDescriptors) one more batched call follows, mskf_fe_describe_batch over
+    // those streams: one more launch and one more host wait per frame; the others take no part.
+    struct FrameScratch {   // argument records, valid until the call's *_end
+        std::vector<mskf_fe_track_args> a1, a2; std::vector<mskf_fe_frame_args> fa;
+        std::vector<mskf_fe_describe_args> da; std::vector<mskf_stream *> ds;
+    };
     static int runFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, const uint8_t *const *cam0,
                         const uint8_t *const *cam1, int on_device, const double *t, bool is_draw, FrameScratch &scratch, const ParFor &par,
                         double *acc, std::string &err);
@@ -107,6 +115,16 @@ class ImageProcessor {
     int setMask(const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch, int margin);
     // the eroded mask of a camera as the stream holds it (0 / 255 per pixel, dense); false = none.  After the stream exists.
     bool mask(int cam, std::vector<uint8_t> &out, int &width, int &height, int &margin) const;
+    // opt-in 256-bit descriptors (mskf_fe_describe_batch; DESIGN.md section 3, "Descriptors") of the features a frame publishes:
+    // frame k's cam0 level 0 at the cam0 pixels of the features of frame k's message, in message order.  Off by default; takes
+    // effect with the next frame.  descriptorIds() / descriptors() (32 bytes each) / descriptorValid() are those of the last frame.
+    void setDescriptors(bool on) { descriptors_ = on; if (!on) { desc_ids_.clear(); desc_.clear(); desc_valid_.clear(); } }
+    bool descriptorsOn() const { return descriptors_; }
+    const std::vector<FeatureIDType> &descriptorIds() const { return desc_ids_; }
+    const std::vector<uint8_t> &descriptors() const { return desc_; }
+    const std::vector<uint8_t> &descriptorValid() const { return desc_valid_; }
+    // one text line per feature and frame: "time id" and 64 hex digits (byte 0 first); turns the descriptors on
+    void enableDescriptorOutput(const std::string &path) { descriptors_ = true; if (!desc_out_.is_open()) desc_out_.open(path); }
     int imageWidth() const { return calib_.width; }       // the calibration's image size: what a mask has to have
     int imageHeight() const { return calib_.height; }
     mskf_stream *stream() const { return stream_; }
@@ -195,6 +213,13 @@ class ImageProcessor {
     mskf_fe_input_format px_cfg_{0, 0};
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
     int applyKeptMask();
+    bool descriptors_ = false;
+    std::vector<FeatureIDType> desc_ids_;
+    std::vector<uint8_t> desc_, desc_valid_;
+    std::ofstream desc_out_;
+    static int describeFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, FrameScratch &scratch, std::string &err);
+    void describePrepare(mskf_fe_describe_args &a);     // the published grid's cam0 pixels on the image that holds this frame
+    void describeDone();                                 // the text output
     bool initialized_ = false;
     mskf_calib calib_;
     mskf_fe_cfg cfg_;

@@ -13,10 +13,13 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         equalize_ = equalize_from_yaml(cfg_imgproc);
         input_format_ = input_format_from_yaml(cfg_imgproc);
         mask_files_ = mask_files_from_yaml(cfg_imgproc);
+        descriptors_ = descriptors_from_yaml(cfg_imgproc);
         const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
         setup(calib, fe, ekf, nullptr, 0);
         if (ok_) { imgproc_ptr_->enableFileOutputs(); msckfvio_ptr_->enableFileOutputs(); }   // pose_out.txt, debug_imageprocessor.txt
+        // optional (not a key of the reference's file): "descriptors_out: <file>" writes the published features' descriptors
+        if (ok_ && cfg_imgproc["descriptors_out"].IsDefined()) imgproc_ptr_->enableDescriptorOutput(cfg_imgproc["descriptors_out"].as<std::string>());
         if (ok_) msckfvio_ptr_->setZupt(zupt_cfg_from_yaml(cfg_msckfvio));        // optional keys zupt*: absent means off
         // optional (not a key of the reference's file): "covariance_out: <file>" writes publish()'s covariances, one line per pose
         if (ok_ && cfg_msckfvio["covariance_out"].IsDefined()) msckfvio_ptr_->enableCovarianceOutput(cfg_msckfvio["covariance_out"].as<std::string>());
@@ -42,6 +45,7 @@ void System::setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ek
     imgproc_ptr_->attach(stream_);
     imgproc_ptr_->setEqualize(equalize_);      // (kept until initialize())
     imgproc_ptr_->setInputFormat(input_format_);
+    imgproc_ptr_->setDescriptors(descriptors_);
     if (!imgproc_ptr_->initialize()) { std::cerr << "Cannot initialize Image Processor..." << std::endl; return; }
     msckfvio_ptr_.reset(new cg::MsckfVio(calib, ekf));
     msckfvio_ptr_->attach(stream_);

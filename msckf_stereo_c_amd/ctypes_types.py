@@ -107,6 +107,15 @@ assert C.sizeof(FeMask) == 32
 MASK_MAX_MARGIN = 64         # FM_MAX_MARGIN (csrc/hip/fe_mask.h)
 
 
+class FeDescribeArgs(C.Structure):
+    """mskf_fe_describe_args (include/mskf_hip.h): n points of the image of `role` in, 32 n descriptor bytes and n validity bytes out."""
+    _fields_ = [("role", C.c_int32), ("n", C.c_int32), ("pts", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p)]
+
+
+assert C.sizeof(FeDescribeArgs) == 32
+DESCRIPTOR_BYTES = 32        # FB_BYTES (csrc/hip/fe_brief.h)
+
+
 def raw_raster(img, fmt):
     """An image in format number fmt as the contiguous array a push takes: (h, w) uint16 for gray16 (native byte order, which the
     device reads as little-endian), (h, w, 3 | 4) uint8 for the colour formats, (h, w) uint8 otherwise.  A wrong shape or a

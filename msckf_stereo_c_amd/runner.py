@@ -228,6 +228,25 @@ class Runner:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
 
+    def set_descriptors(self, on, stream=None):
+        """Opt-in 256-bit binary descriptors (upright BRIEF) of the features every frame publishes, of one stream
+        or of all: one more batched device call per frame of a group with a describing stream.  Off by default; call between runs."""
+        self.L.mskfh_runner_set_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.L.mskfh_runner_set_descriptors(self.h, -1 if stream is None else int(stream), int(bool(on)))
+        if rc != 0:
+            raise MskfError("set_descriptors: the stream is not one of the runner's", rc)
+
+    def descriptors(self, stream=0):
+        """(ids uint64[n], desc uint8[n, 32], valid uint8[n]) of the stream's last frame, aligned with msg(stream): the descriptors
+        of that frame's cam0 image at the cam0 pixels of its features.  Empty arrays with the option off."""
+        self.L.mskfh_num_descriptors.argtypes = [C.c_void_p, C.c_int]
+        self.L.mskfh_get_descriptors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = self.L.mskfh_num_descriptors(self.h, stream)
+        ids, desc, valid = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        if n:
+            self.L.mskfh_get_descriptors(self.h, stream, _p(ids), _p(desc), _p(valid))
+        return ids, desc, valid
+
     def _raw(self, img, fmt):
         r = raw_raster(img, fmt)
         if r.shape[:2] != (self.calib.height, self.calib.width):
