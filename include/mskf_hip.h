@@ -46,7 +46,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  mskf_ekf_update_direct, _batch, _batch_begin, _batch_end (with their own mskf_ekf_direct_args);
                                  mskf_fe_set_mask, mskf_fe_get_mask (with their own mskf_fe_mask) and the timing kind MSKF_K_FE_MASK, which is the
                                  slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged);
-                                 mskf_fe_describe, _batch, _batch_begin, _batch_end (with their own mskf_fe_describe_args), mskf_fe_descriptor_pattern */
+                                 mskf_fe_describe, _batch, _batch_begin, _batch_end (with their own mskf_fe_describe_args), mskf_fe_descriptor_pattern;
+                                 mskf_fe_match, _batch, _batch_begin, _batch_end (with their own mskf_fe_match_args and mskf_match) */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -340,6 +341,40 @@ int mskf_fe_describe_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *strea
 int mskf_fe_describe_batch_end(mskf_ctx *ctx);
 /* ax, ay, bx, by of test 0, 1, .. 255; no device call */
 void mskf_fe_descriptor_pattern(int8_t out[1024]);
+
+/* ---- opt-in brute-force Hamming matcher of those descriptors ("Descriptor matching")
+ * Nothing runs or is allocated for a context that never calls these.  A job matches nq query descriptors against nt train
+ * descriptors (32 bytes each, 0 .. 65535 of either); query_valid / train_valid are what describe returns (one byte each, != 0 =
+ * valid; NULL = all valid).  The distance is the popcount of the XOR, 0 .. 256.  For a valid query, nearest is the valid train of
+ * the smallest (distance, index): among equal distances the lowest index wins; dist is that distance and second the smallest
+ * distance to a valid train other than nearest (it may equal dist).  Without a valid train, or for an invalid query, nearest = -1
+ * and dist = second = 0xFFFF; with exactly one valid train second = 0xFFFF.  idx = nearest iff nearest >= 0, dist <= max_distance,
+ * the ratio test holds (ratio == 0: off; second == 0xFFFF: passes; else (float)dist < ratio * (float)second in float32) and, with
+ * cross_check != 0, the valid query of the smallest (distance, index) to train `nearest` is this one; otherwise idx = -1.  nearest,
+ * dist and second are always the raw values.  n_matches counts the queries with idx >= 0.
+ * The calls take a context, not streams: matching reads no image.  Sets and results travel through arenas of the call's own: one
+ * copy in, ONE launch (k_fe_match, cross-checked or not; not timed, there is no MSKF_K_* kind for it) and one copy out for the whole
+ * batch.  A descriptor set or validity array that several jobs of a batch name by the same (pointer, count) is copied once: a
+ * query against K keyframes is K jobs with one query pointer.  The host arrays need no alignment.
+ * Everything is validated before anything is touched.  MSKF_ERR_INVALID, mskf_last_error naming the reason: a null ctx or args,
+ * n <= 0, nq or nt negative or above 65535, null query with nq > 0, null train with nt > 0, null matches with nq > 0, max_distance
+ * outside 0 .. 256, a ratio that is NaN, negative or above 1, and while a match batch of the context is pending (nothing else
+ * refuses for it, and it refuses for nothing else).  A batch whose every nq is 0 is MSKF_OK, sets every n_matches to 0 and leaves
+ * nothing pending.  The args and their arrays stay valid until _end, which fills matches and n_matches. */
+typedef struct mskf_fe_match_args {
+    int32_t nq, nt;
+    const uint8_t *query, *query_valid;   /* 32 nq bytes; nq bytes or NULL */
+    const uint8_t *train, *train_valid;   /* 32 nt bytes; nt bytes or NULL */
+    int32_t max_distance;                 /* 0 .. 256 */
+    float   ratio;                        /* 0 = off, else (0, 1] */
+    int32_t cross_check;
+    mskf_match *matches;                  /* out: nq */
+    int32_t n_matches;                    /* out */
+} mskf_fe_match_args;
+int mskf_fe_match(mskf_ctx *ctx, mskf_fe_match_args *args);            /* batch of one; synchronises */
+int mskf_fe_match_batch(mskf_ctx *ctx, int n, mskf_fe_match_args *args);
+int mskf_fe_match_batch_begin(mskf_ctx *ctx, int n, mskf_fe_match_args *args);
+int mskf_fe_match_batch_end(mskf_ctx *ctx);
 
 /* ------------------------------------------------------------------ EKF (covariance resident in HBM)
  * Replaces, inside cg::MsckfVio (msckf_vio.cpp):

@@ -86,6 +86,15 @@ typedef struct mskf_imu_sample {    /* == cg::Imu */
 
 typedef struct mskf_point2f { float x, y; } mskf_point2f;
 
+/* one query descriptor's result of mskf_fe_match* ("Descriptor matching"): nearest, dist and second are always the
+ * raw values, idx is nearest where the match passed the call's thresholds and -1 otherwise */
+typedef struct mskf_match {
+    int32_t idx;        /* accepted train index, or -1 */
+    int32_t nearest;    /* valid train index of the smallest (distance, index), or -1: none */
+    uint16_t dist;      /* Hamming distance to nearest, 0 .. 256; 0xFFFF: none */
+    uint16_t second;    /* smallest distance to a valid train other than nearest (may equal dist); 0xFFFF: none */
+} mskf_match;           /* 12 bytes */
+
 /* one detector candidate: per-cell best corner */
 typedef struct mskf_corner {
     float x, y;

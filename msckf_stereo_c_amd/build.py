@@ -25,6 +25,7 @@ HIP_SRCS = [
     "hip/ekf_linalg.hip",
     "hip/ekf_direct.hip",
     "hip/fe_describe.hip",
+    "hip/fe_match.hip",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_ekf.cpp",
 ]

@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, IMU_STEP, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
+from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
                            FeInputFormat, FeMask, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +66,7 @@ EXPORTS = [
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
     "mskf_fe_set_mask", "mskf_fe_get_mask",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
+    "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
 ]
 
 
@@ -158,6 +159,33 @@ def _describe_args(role, pts):
     return a, pts, (desc, valid)
 
 
+def _descriptor_set(desc, valid):
+    """(uint8[n, 32] contiguous, uint8[n] contiguous or None) of a descriptor set; arrays that already are so are passed as they are,
+    so that jobs naming the same array share one copy on the device."""
+    d = desc if isinstance(desc, np.ndarray) and desc.dtype == np.uint8 and desc.flags.c_contiguous else np.ascontiguousarray(desc, dtype=np.uint8)
+    d = d.reshape(-1, DESCRIPTOR_BYTES)
+    if valid is None:
+        return d, None
+    v = valid if isinstance(valid, np.ndarray) and valid.dtype == np.uint8 and valid.flags.c_contiguous else np.ascontiguousarray(valid, dtype=np.uint8)
+    v = v.reshape(-1)
+    if len(v) != len(d):
+        raise ValueError("a validity array has one byte per descriptor")
+    return d, v
+
+
+def _match_args(job):
+    """(mskf_fe_match_args, buffers it points into, matches the call fills) for one job: a dict with query, train and optionally
+    query_valid, train_valid, max_distance (256), ratio (0 = off), cross_check (False)."""
+    q, qv = _descriptor_set(job["query"], job.get("query_valid"))
+    t, tv = _descriptor_set(job["train"], job.get("train_valid"))
+    m = np.zeros(len(q), MATCH)
+    a = FeMatchArgs(len(q), len(t), q.ctypes.data if len(q) else None, None if qv is None or not len(q) else qv.ctypes.data,
+                    t.ctypes.data if len(t) else None, None if tv is None or not len(t) else tv.ctypes.data,
+                    int(job.get("max_distance", 256)), float(job.get("ratio", 0.0)), int(bool(job.get("cross_check", False))),
+                    m.ctypes.data if len(q) else None, -1)
+    return a, (q, qv, t, tv), m
+
+
 def _imu_steps(steps):
     """mskf_imu_step records as a contiguous IMU_STEP array (None / empty: no steps)."""
     if steps is None:
@@ -182,6 +210,7 @@ class Context:
         self._frame_pending = None
         self._direct_pending = None
         self._dsc_pending = None
+        self._mch_pending = None
 
     def close(self):
         if self.h:
@@ -252,6 +281,42 @@ class Context:
         self.L.mskf_fe_describe_batch_end.argtypes = [C.c_void_p]
         _chk(self.L.mskf_fe_describe_batch_end(self.h))
         self._dsc_pending = None
+
+    def match_batch(self, jobs):
+        """One mskf_fe_match_batch: brute-force Hamming matching of 256-bit descriptors, a job per dict of jobs (query, train uint8[n, 32];
+        optional query_valid, train_valid uint8[n], max_distance = 256, ratio = 0.0 (off), cross_check = False).  Jobs that name the same
+        array share one copy on the device.  Returns [(matches MATCH[nq], n_matches)]: idx = the accepted train index or -1, nearest /
+        dist / second the raw nearest neighbour (lowest index among equal distances), its distance and the next smallest distance."""
+        self.match_batch_begin(jobs)
+        return self.match_batch_end()
+
+    def match_batch_begin(self, jobs):
+        """mskf_fe_match_batch_begin: enqueue the batch; match_batch_end returns the results."""
+        built = [_match_args(j) for j in jobs]
+        n = len(built)
+        args = (FeMatchArgs * max(n, 1))(*[b[0] for b in built])
+        self.L.mskf_fe_match_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeMatchArgs)]
+        _chk(self.L.mskf_fe_match_batch_begin(self.h, n, args))
+        self._mch_pending = (built, args)             # must stay alive until _end
+        return [b[2] for b in built]
+
+    def match_batch_end(self):
+        """mskf_fe_match_batch_end: [(matches, n_matches)] of the batch begun, None when there was none."""
+        self.L.mskf_fe_match_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_fe_match_batch_end(self.h))
+        pend, self._mch_pending = self._mch_pending, None
+        if pend is None:
+            return None
+        built, args = pend
+        return [(b[2], int(args[i].n_matches)) for i, b in enumerate(built)]
+
+    def match(self, query, train, query_valid=None, train_valid=None, max_distance=256, ratio=0.0, cross_check=False):
+        """mskf_fe_match: one job; returns (matches MATCH[nq], n_matches); synchronises."""
+        a, _keep, m = _match_args(dict(query=query, train=train, query_valid=query_valid, train_valid=train_valid, max_distance=max_distance,
+                                       ratio=ratio, cross_check=cross_check))
+        self.L.mskf_fe_match.argtypes = [C.c_void_p, C.POINTER(FeMatchArgs)]
+        _chk(self.L.mskf_fe_match(self.h, C.byref(a)))
+        return m, int(a.n_matches)
 
     def push_stereo_batch(self, streams, cam0s, cam1s, on_device=0):
         """One mskf_fe_push_stereo_batch: host images (on_device = 0) or device addresses (1: copied, 2: borrowed)."""

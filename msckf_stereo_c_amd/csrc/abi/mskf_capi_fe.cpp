@@ -7,6 +7,7 @@
 #include <cstring>
 #include <chrono>
 #include <atomic>
+#include <map>
 #include <type_traits>
 #include <vector>
 #include "mskf_internal.h"
@@ -69,6 +70,8 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
     c->dsc_jobs.release(); c->dsc_in.release(); c->dsc_out.release();
     if (c->pend_dsc.done) (void)hipEventDestroy(c->pend_dsc.done);
+    c->mch_jobs.release(); c->mch_in.release(); c->mch_out.release();
+    if (c->pend_mch.done) (void)hipEventDestroy(c->pend_mch.done);
     c->ekf_desc.release();
     c->pred_arena.release();
     if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
@@ -266,7 +269,7 @@ extern "C" int mskf_ctx_set_timing(mskf_ctx *c, int enable) {
 
 extern "C" int mskf_ctx_set_wait_mode(mskf_ctx *c, int block) {
     if (!c) return MSKF_ERR_INVALID;
-    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
+    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active || c->pend_mch.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
     c->wait_block = block != 0;
     return MSKF_OK;
 }
@@ -1406,3 +1409,116 @@ extern "C" int mskf_fe_describe(mskf_stream *s, mskf_fe_describe_args *args) {
     mskf_stream *ss[1] = {s};
     return mskf_fe_describe_batch(s->ctx, 1, ss, args);
 }
+
+// ------------------------------------------------------------------------------------------ descriptor matching (fe_match.h)
+static int refuse_match(const char *why) { mskf_set_error(std::string("match: ") + why); return MSKF_ERR_INVALID; }
+
+static inline size_t match_block(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+
+// The distinct host arrays of a match batch, by (pointer, bytes), and where the one copy of each lies in mch_in.
+struct MatchSets {
+    std::map<std::pair<const uint8_t *, size_t>, size_t> off;
+    size_t bytes = 0;
+    size_t place(const uint8_t *p, size_t n) {
+        const auto it = off.find({p, n});
+        if (it != off.end()) return it->second;
+        const size_t o = bytes;
+        off[{p, n}] = o;
+        bytes += match_block(n);
+        return o;
+    }
+};
+
+extern "C" int mskf_fe_match_batch_begin(mskf_ctx *ctx, int n, mskf_fe_match_args *args) {
+    // ---- plan: every refusal comes from here, before anything is touched
+    if (!ctx || !args) return refuse_match("null argument");
+    if (n <= 0) return refuse_match("a batch has at least one job");
+    if (ctx->pend_mch.active) return refuse_match("a match batch of this context is still pending (call mskf_fe_match_batch_end)");
+    int max_nq = 0, max_nt = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_match_args &a = args[i];
+        if (a.nq < 0 || a.nt < 0) return refuse_match("negative descriptor count");
+        if (a.nq > FM_MAX_N || a.nt > FM_MAX_N) return refuse_match("more than 65535 descriptors in a set");
+        if (a.nq > 0 && !a.query) return refuse_match("null query with nq > 0");
+        if (a.nt > 0 && !a.train) return refuse_match("null train with nt > 0");
+        if (a.nq > 0 && !a.matches) return refuse_match("null matches with nq > 0");
+        if (a.max_distance < 0 || a.max_distance > FM_MAX_DISTANCE) return refuse_match("max_distance must be 0 .. 256");
+        if (!(a.ratio >= 0.f && a.ratio <= 1.f)) return refuse_match("ratio must be 0 (off) or in (0, 1]");
+        max_nq = std::max(max_nq, a.nq);
+        max_nt = std::max(max_nt, a.nt);
+    }
+    if (max_nq <= 0) {                     // nothing to match: no batch pending, _end is a no-op
+        for (int i = 0; i < n; ++i) args[i].n_matches = 0;
+        return MSKF_OK;
+    }
+    MatchSets sets;
+    std::vector<size_t> &out_off = ctx->pend_mch.out_off;      // (no batch is pending: nobody reads it)
+    out_off.resize(n);
+    size_t out_bytes = 0;
+    struct Placed { size_t q, qv, t, tv; };
+    std::vector<Placed> placed(n);
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_match_args &a = args[i];
+        out_off[i] = out_bytes;
+        if (a.nq <= 0) continue;
+        placed[i].q = sets.place(a.query, (size_t)FM_BYTES * a.nq);
+        placed[i].qv = a.query_valid ? sets.place(a.query_valid, (size_t)a.nq) : 0;
+        placed[i].t = a.nt > 0 ? sets.place(a.train, (size_t)FM_BYTES * a.nt) : 0;
+        placed[i].tv = a.nt > 0 && a.train_valid ? sets.place(a.train_valid, (size_t)a.nt) : 0;
+        out_bytes += match_block(sizeof(mskf_match) * (size_t)a.nq);
+    }
+    // ---- grow
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ctx->mch_jobs.ensure(n)) != MSKF_OK || (rc = ctx->mch_in.ensure(sets.bytes)) != MSKF_OK || (rc = ctx->mch_out.ensure(out_bytes)) != MSKF_OK) return rc;
+    for (const auto &s : sets.off) std::memcpy(ctx->mch_in.h + s.second, s.first.first, s.first.second);      // each distinct array once
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_match_args &a = args[i];
+        FeMatchDev &j = ctx->mch_jobs.h[i];
+        std::memset(&j, 0, sizeof(j));
+        if (a.nq <= 0) continue;           // (nq = 0: the launch skips it)
+        const uint8_t *base = (const uint8_t *)ctx->mch_in.d;
+        j.query = base + placed[i].q;
+        j.query_valid = a.query_valid ? base + placed[i].qv : nullptr;
+        j.train = a.nt > 0 ? base + placed[i].t : nullptr;
+        j.train_valid = a.nt > 0 && a.train_valid ? base + placed[i].tv : nullptr;
+        j.nq = a.nq; j.nt = a.nt;
+        j.max_distance = a.max_distance; j.ratio = a.ratio; j.cross_check = a.cross_check != 0;
+        j.matches = (mskf_match *)(ctx->mch_out.d + out_off[i]);
+    }
+    // ---- enqueue: one copy in, one launch, one copy out
+    DrainOnError drain{ctx->stream, true};
+    const MskfCopy cp[2] = {{ctx->mch_in.d, ctx->mch_in.h, sets.bytes}, {ctx->mch_jobs.d, ctx->mch_jobs.h, sizeof(FeMatchDev) * (size_t)n}};
+    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+    fe_launch_match(ctx->mch_jobs.d, n, max_nq, max_nt, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
+    { const MskfCopy out = {ctx->mch_out.h, ctx->mch_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
+    MSKF_HIPCHK(hipGetLastError());
+    ctx->pend_mch.n = n; ctx->pend_mch.args = args;
+    if ((rc = mskf_batch_arm(ctx, ctx->pend_mch)) != MSKF_OK) return rc;
+    drain.armed = false;
+    return MSKF_OK;
+}
+
+// Wait for the batch started by mskf_fe_match_batch_begin and copy its results into the args given there.  No-op when nothing
+// is pending.
+extern "C" int mskf_fe_match_batch_end(mskf_ctx *ctx) {
+    if (!ctx) return MSKF_ERR_INVALID;
+    mskf_ctx::PendingMatch &M = ctx->pend_mch;
+    if (!M.active) return MSKF_OK;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    if (const int rc = mskf_batch_finish(ctx, M)) return rc;
+    for (int i = 0; i < M.n; ++i) {
+        mskf_fe_match_args &a = M.args[i];
+        const mskf_match *src = (const mskf_match *)(ctx->mch_out.h + M.out_off[i]);
+        if (a.nq > 0) std::memcpy(a.matches, src, sizeof(mskf_match) * (size_t)a.nq);
+        a.n_matches = a.nq > 0 ? fm_count_matches(src, a.nq) : 0;
+    }
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_match_batch(mskf_ctx *ctx, int n, mskf_fe_match_args *args) {
+    const int rc = mskf_fe_match_batch_begin(ctx, n, args);
+    return rc != MSKF_OK ? rc : mskf_fe_match_batch_end(ctx);
+}
+
+extern "C" int mskf_fe_match(mskf_ctx *ctx, mskf_fe_match_args *args) { return mskf_fe_match_batch(ctx, 1, args); }

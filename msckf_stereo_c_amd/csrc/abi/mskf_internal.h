@@ -10,6 +10,7 @@
 #include "../hip/fe_pixfmt.h"
 #include "../hip/fe_mask.h"
 #include "../hip/fe_brief.h"
+#include "../hip/fe_match.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -28,6 +29,8 @@ void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *ma
 void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
 // descriptors (fe_brief.h): jobs of any size and count in one launch; max_pts = the largest count
 void fe_launch_describe(const FeDescribeDev *jobs_dev, int n_jobs, int max_pts, hipStream_t st);
+// descriptor matching (fe_match.h): jobs of any size and count in one launch, cross-checked or not; max_nq / max_nt = the largest counts
+void fe_launch_match(const FeMatchDev *jobs_dev, int n_jobs, int max_nq, int max_nt, hipStream_t st);
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);
@@ -110,6 +113,8 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 // Which pending batch owns which arenas of the context:
 //   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
 //   a pending describe batch owns dsc_jobs, dsc_in and dsc_out, which nothing else touches: only a describe call refuses for it;
+//   a pending match batch owns mch_jobs, mch_in and mch_out, which nothing else touches: only a match call refuses for it (it
+//   reads no image and no stream, so pushes, frames, describe batches and updates may run between its _begin and its _end);
 //   a pending update (a feature update or a direct update: one slot for both kinds) owns ekf_desc, upd_in and upd_out;
 //   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
 //   descriptors from and writes results into the host side).
@@ -204,6 +209,13 @@ struct mskf_ctx {
         int n = 0; struct mskf_fe_describe_args *args = nullptr;
         std::vector<size_t> out_off;           // per stream: byte offset of its results in dsc_out
     } pend_dsc;
+    // descriptor matching (mskf_fe_match_batch_*; fe_match.h): arenas of the call's own, empty until the first call, owned by pend_mch
+    PinnedDev<FeMatchDev> mch_jobs;
+    PinnedDev<char> mch_in, mch_out;     // every distinct descriptor set and validity array / the matches of every job of a match batch (one copy each way)
+    struct PendingMatch : PendingBatch {
+        int n = 0; struct mskf_fe_match_args *args = nullptr;
+        std::vector<size_t> out_off;           // per job: byte offset of its matches in mch_out
+    } pend_mch;
     // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
     struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;
 };

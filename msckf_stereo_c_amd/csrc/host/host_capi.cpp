@@ -260,6 +260,49 @@ void mskfh_get_descriptors(void *h, int stream, uint64_t *ids, uint8_t *desc, ui
     for (size_t i = 0; i < n; ++i) ids[i] = ip.descriptorIds()[i];
     if (n) { std::memcpy(desc, ip.descriptors().data(), 32 * n); std::memcpy(valid, ip.descriptorValid().data(), n); }
 }
+// ---- keyframes (keyframes.h): stored copies of a stream's last-frame descriptors and their matching; between runs.
+// The stream's last frame (time, ids, desc, valid) becomes a keyframe; returns its index, -1 with descriptors off for the stream.
+int mskfh_add_keyframe(void *h, int stream) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream < 0 || stream >= r->n_streams()) return -1;
+    ImageProcessor &ip = *r->system(stream).imgproc_ptr_;
+    if (!ip.descriptorsOn()) return -1;
+    return ip.keyframes.add(ip.descriptorTime(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(), ip.descriptorValid());
+}
+int mskfh_num_keyframes(void *h, int stream) { return ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.size(); }
+// the feature count of keyframe k, -1: no such keyframe
+int mskfh_keyframe_size(void *h, int stream, int k) {
+    const KeyframeStore &s = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes;
+    return k < 0 || k >= s.size() ? -1 : (int)s.at(k).ids.size();
+}
+void mskfh_get_keyframe(void *h, int stream, int k, double *time, uint64_t *ids, uint8_t *desc, uint8_t *valid) {
+    const Keyframe &f = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.at(k);
+    *time = f.time;
+    const size_t n = f.ids.size();
+    if (n) { std::memcpy(ids, f.ids.data(), 8 * n); std::memcpy(desc, f.desc.data(), 32 * n); std::memcpy(valid, f.valid.data(), n); }
+}
+void mskfh_clear_keyframes(void *h, int stream) {      // of one stream, or of all (stream < 0)
+    MultiRunner *r = (MultiRunner *)h;
+    for (int i = 0; i < r->n_streams(); ++i) if (stream < 0 || i == stream) r->system(i).imgproc_ptr_->keyframes.clear();
+}
+// The stream's last-frame descriptors against every keyframe of the stream, one mskf_fe_match_batch on the stream's context.
+// Returns the number of keyframes with n_matches >= min_matches (mskfh_keyframe_hit reads them), or a negative mskf status.
+int mskfh_query_keyframes(void *h, int stream, int max_distance, float ratio, int cross_check, int min_matches) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream < 0 || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    ImageProcessor &ip = *r->system(stream).imgproc_ptr_;
+    if (!ip.descriptorsOn()) { return MSKF_ERR_INVALID; }
+    int local;
+    const int rc = ip.keyframes.query(r->group_of(stream, local).ctx(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(),
+                                      ip.descriptorValid(), max_distance, ratio, cross_check != 0, min_matches);
+    return rc != MSKF_OK ? rc : (int)ip.keyframes.hits().size();
+}
+// hit i of the last query: the keyframe's index, time and match count; pairs (when not null) takes 2 * n_matches ids
+void mskfh_keyframe_hit(void *h, int stream, int i, int *k, double *time, int *n_matches, uint64_t *pairs) {
+    const KeyframeHit &hit = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.hits()[i];
+    *k = hit.k; *time = hit.time; *n_matches = hit.n_matches;
+    if (pairs && !hit.pairs.empty()) std::memcpy(pairs, hit.pairs.data(), 8 * hit.pairs.size());
+}
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
 void mskfh_runner_publish_covariance(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

@@ -15,6 +15,7 @@
 #include "../../../include/mskf_hip.h"
 #include "cg_types.h"
 #include "frame_seq.h"
+#include "keyframes.h"
 #include "yaml_lite.h"
 
 namespace cg {
@@ -123,6 +124,10 @@ class ImageProcessor {
     const std::vector<FeatureIDType> &descriptorIds() const { return desc_ids_; }
     const std::vector<uint8_t> &descriptors() const { return desc_; }
     const std::vector<uint8_t> &descriptorValid() const { return desc_valid_; }
+    double descriptorTime() const { return cam0_curr_time; }       // the time stamp of the frame they belong to
+    // Keyframes of this stream, for a place-recognition caller (keyframes.h): copies of those getters' arrays, added and queried
+    // only when the caller says so; empty, and nothing of it runs, otherwise.
+    KeyframeStore keyframes;
     // one text line per feature and frame: "time id" and 64 hex digits (byte 0 first); turns the descriptors on
     void enableDescriptorOutput(const std::string &path) { descriptors_ = true; if (!desc_out_.is_open()) desc_out_.open(path); }
     int imageWidth() const { return calib_.width; }       // the calibration's image size: what a mask has to have

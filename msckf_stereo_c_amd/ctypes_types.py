@@ -116,6 +116,20 @@ assert C.sizeof(FeDescribeArgs) == 32
 DESCRIPTOR_BYTES = 32        # FB_BYTES (csrc/hip/fe_brief.h)
 
 
+class FeMatchArgs(C.Structure):
+    """mskf_fe_match_args (include/mskf_hip.h): nq query against nt train descriptors with their optional validity arrays in, nq
+    mskf_match records and their count of accepted ones out."""
+    _fields_ = [("nq", C.c_int32), ("nt", C.c_int32), ("query", C.c_void_p), ("query_valid", C.c_void_p), ("train", C.c_void_p), ("train_valid", C.c_void_p),
+                ("max_distance", C.c_int32), ("ratio", C.c_float), ("cross_check", C.c_int32), ("matches", C.c_void_p), ("n_matches", C.c_int32)]
+
+
+assert C.sizeof(FeMatchArgs) == 72
+MATCH = np.dtype([("idx", "<i4"), ("nearest", "<i4"), ("dist", "<u2"), ("second", "<u2")])       # mskf_match
+assert MATCH.itemsize == 12
+MATCH_MAX_N = 65535          # FM_MAX_N (csrc/hip/fe_match.h)
+MATCH_NONE = 0xFFFF          # FM_NONE: dist / second without a neighbour
+
+
 def raw_raster(img, fmt):
     """An image in format number fmt as the contiguous array a push takes: (h, w) uint16 for gray16 (native byte order, which the
     device reads as little-endian), (h, w, 3 | 4) uint8 for the colour formats, (h, w) uint8 otherwise.  A wrong shape or a

@@ -247,6 +247,57 @@ class Runner:
             self.L.mskfh_get_descriptors(self.h, stream, _p(ids), _p(desc), _p(valid))
         return ids, desc, valid
 
+    def add_keyframe(self, stream=0):
+        """Keep a copy of the stream's last-frame (time, ids, desc, valid), what descriptors(stream) returns, as a keyframe in host
+        memory; returns its index.  The runner decides neither when a frame becomes a keyframe nor what counts as a revisit: that is
+        the caller's policy.  Raises with descriptors off for the stream.  Call between runs."""
+        self.L.mskfh_add_keyframe.argtypes = [C.c_void_p, C.c_int]
+        k = self.L.mskfh_add_keyframe(self.h, int(stream))
+        if k < 0:
+            raise MskfError("add_keyframe: descriptors are off for the stream (set_descriptors), or it is not one of the runner's", -1)
+        return k
+
+    def num_keyframes(self, stream=0):
+        self.L.mskfh_num_keyframes.argtypes = [C.c_void_p, C.c_int]
+        return self.L.mskfh_num_keyframes(self.h, int(stream))
+
+    def keyframe(self, stream, k):
+        """(time, ids uint64[n], desc uint8[n, 32], valid uint8[n]) of the stream's keyframe k."""
+        self.L.mskfh_keyframe_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self.L.mskfh_get_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p]
+        n = self.L.mskfh_keyframe_size(self.h, int(stream), int(k))
+        if n < 0:
+            raise IndexError("keyframe %d of stream %d" % (k, stream))
+        t = C.c_double(0)
+        ids, desc, valid = np.zeros(n, np.uint64), np.zeros((n, 32), np.uint8), np.zeros(n, np.uint8)
+        self.L.mskfh_get_keyframe(self.h, int(stream), int(k), C.byref(t), _p(ids), _p(desc), _p(valid))
+        return t.value, ids, desc, valid
+
+    def clear_keyframes(self, stream=None):
+        """Forget the keyframes of one stream, or of all."""
+        self.L.mskfh_clear_keyframes.argtypes = [C.c_void_p, C.c_int]
+        self.L.mskfh_clear_keyframes(self.h, -1 if stream is None else int(stream))
+
+    def query_keyframes(self, stream=0, max_distance=256, ratio=0.0, cross_check=True, min_matches=0):
+        """Match the stream's last-frame descriptors against every keyframe of that stream in one mskf_fe_match_batch (the query set
+        is shared, one job per keyframe; DESIGN.md section 3, "Descriptor matching").  Returns [(k, time, n_matches, pairs)] of the
+        keyframes with n_matches >= min_matches, pairs uint64[m, 2] of (query feature id, keyframe feature id) in query order.
+        Verifying a candidate and fusing it (fuse_position) stay with the caller.  Call between runs."""
+        self.L.mskfh_query_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
+        self.L.mskfh_keyframe_hit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
+        n = self.L.mskfh_query_keyframes(self.h, int(stream), int(max_distance), float(ratio), int(bool(cross_check)), int(min_matches))
+        if n < 0:
+            from . import capi
+            raise MskfError("query_keyframes: mskf status %d: %s" % (n, capi.lib().mskf_last_error().decode()), n)
+        out = []
+        for i in range(n):
+            k, t, m = C.c_int(0), C.c_double(0), C.c_int(0)
+            self.L.mskfh_keyframe_hit(self.h, int(stream), i, C.byref(k), C.byref(t), C.byref(m), None)
+            pairs = np.zeros((m.value, 2), np.uint64)
+            self.L.mskfh_keyframe_hit(self.h, int(stream), i, C.byref(k), C.byref(t), C.byref(m), _p(pairs))
+            out.append((k.value, t.value, m.value, pairs))
+        return out
+
     def _raw(self, img, fmt):
         r = raw_raster(img, fmt)
         if r.shape[:2] != (self.calib.height, self.calib.width):
