@@ -47,7 +47,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  mskf_fe_set_mask, mskf_fe_get_mask (with their own mskf_fe_mask) and the timing kind MSKF_K_FE_MASK, which is the
                                  slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged);
                                  mskf_fe_describe, _batch, _batch_begin, _batch_end (with their own mskf_fe_describe_args), mskf_fe_descriptor_pattern;
-                                 mskf_fe_match, _batch, _batch_begin, _batch_end (with their own mskf_fe_match_args and mskf_match) */
+                                 mskf_fe_match, _batch, _batch_begin, _batch_end (with their own mskf_fe_match_args and mskf_match);
+                                 mskf_fe_verify, _batch, _batch_begin, _batch_end (with their own mskf_fe_verify_args) */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -375,6 +376,45 @@ int mskf_fe_match(mskf_ctx *ctx, mskf_fe_match_args *args);            /* batch 
 int mskf_fe_match_batch(mskf_ctx *ctx, int n, mskf_fe_match_args *args);
 int mskf_fe_match_batch_begin(mskf_ctx *ctx, int n, mskf_fe_match_args *args);
 int mskf_fe_match_batch_end(mskf_ctx *ctx);
+
+/* ---- opt-in stereo RANSAC pose check of matched pairs ("Geometric verification")
+ * Nothing runs or is allocated for a context that never calls these.  A job takes n pairs (0 .. 4096) of stereo observations, each
+ * the four undistorted normalised coordinates (x0, y0, x1, y1) of a feature (what the published feature message carries as u0, v0, u1,
+ * v1): query_obs of the frame asked about, train_obs of the keyframe, and says whether the pairs agree on one rigid motion
+ * p_k = R p_q + t (query cam0 -> keyframe cam0).  Both sides are triangulated with T_cam1_cam0 (p_c1 = R10 p_c0 + t10); a pair is
+ * usable iff its usable byte is != 0 (NULL = all) and both depths are finite and in [min_depth, max_depth].  Hypothesis h = 0 ..
+ * n_hypotheses - 1 (1 .. 1024) is fitted to three distinct usable pairs drawn as a function of (seed, h, n_usable) alone; a pair is
+ * an inlier of (R, t) iff the query point lands in front of both keyframe cameras (z >= min_depth) and the sum of the four squared
+ * differences between its projections and the keyframe's observation is < max_error^2 (strictly; normalised units).  The hypothesis
+ * with the most inliers wins, the lowest h among equal counts; its pose is refined by five Gauss-Newton steps on its inlier set.
+ * Out: n_usable, n_inliers, best (the winning h, or -1), inlier (n bytes at the ORIGINAL indices, may be NULL), R (row-major), t,
+ * info = J^T J of the four residuals per inlier (6 x 6 row-major, order [theta, t], left perturbation; a covariance is sigma^2
+ * info^-1 with sigma the caller's observation noise in normalised units), rms of the residuals, and status: 0 ok; 1 no hypothesis
+ * (fewer than 3 usable pairs, or every sampled triangle degenerate): best = -1, n_inliers = 0, identity pose, zero info; 2 the
+ * refinement failed: R, t are the three-pair fit, info is zero.
+ * The calls take a context, not streams: no image is read.  The host triangulates and compacts the usable pairs in _begin; they and
+ * the results travel through arenas of the call's own: one copy in, ONE launch (k_fe_verify; not timed) and one copy out (a 64-bit
+ * key per 64 hypotheses) for the whole batch; _end re-forms the winner, marks its inliers and refines it on the host.
+ * Everything is validated before anything is touched.  MSKF_ERR_INVALID, mskf_last_error naming the reason: a null ctx or args, a
+ * batch of n_jobs <= 0, n negative or above 4096, null query_obs or train_obs with n > 0, n_hypotheses outside 1 .. 1024, max_error
+ * not > 0 or not finite, depths that are not 0 < min_depth < max_depth < infinity, a T_cam1_cam0 that is not finite, and while a
+ * verify batch of the context is pending (nothing else refuses for it, and it refuses for nothing else).  A batch whose every n is
+ * 0 is MSKF_OK, fills every job's outputs (status 1) and leaves nothing pending.  The args and their arrays stay valid until _end. */
+typedef struct mskf_fe_verify_args {
+    int32_t n, n_hypotheses;
+    const double *query_obs, *train_obs;  /* 4 n doubles each */
+    const uint8_t *usable;                /* n bytes or NULL */
+    double T_cam1_cam0[16];
+    uint64_t seed;
+    double max_error, min_depth, max_depth;
+    uint8_t *inlier;                      /* out: n bytes, or NULL */
+    int32_t n_usable, n_inliers, best, status;      /* out */
+    double R[9], t[3], info[36], rms;     /* out */
+} mskf_fe_verify_args;
+int mskf_fe_verify(mskf_ctx *ctx, mskf_fe_verify_args *args);            /* batch of one; synchronises */
+int mskf_fe_verify_batch(mskf_ctx *ctx, int n_jobs, mskf_fe_verify_args *args);
+int mskf_fe_verify_batch_begin(mskf_ctx *ctx, int n_jobs, mskf_fe_verify_args *args);
+int mskf_fe_verify_batch_end(mskf_ctx *ctx);
 
 /* ------------------------------------------------------------------ EKF (covariance resident in HBM)
  * Replaces, inside cg::MsckfVio (msckf_vio.cpp):

@@ -26,6 +26,7 @@ HIP_SRCS = [
     "hip/ekf_direct.hip",
     "hip/fe_describe.hip",
     "hip/fe_match.hip",
+    "hip/fe_verify.hip",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_ekf.cpp",
 ]

@@ -5,7 +5,7 @@ import os
 
 import numpy as np
 
-from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
+from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, FeVerifyArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
                            FeInputFormat, FeMask, ImuStep, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +67,7 @@ EXPORTS = [
     "mskf_fe_set_mask", "mskf_fe_get_mask",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
     "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
+    "mskf_fe_verify", "mskf_fe_verify_batch", "mskf_fe_verify_batch_begin", "mskf_fe_verify_batch_end",
 ]
 
 
@@ -186,6 +187,39 @@ def _match_args(job):
     return a, (q, qv, t, tv), m
 
 
+def _verify_args(job):
+    """(mskf_fe_verify_args, buffers it points into, inlier bytes the call fills) for one job: a dict with query_obs, train_obs
+    (float64[n, 4]: x0, y0, x1, y1 normalised), T_cam1_cam0 (16 doubles, row-major) and optionally usable (uint8[n]), n_hypotheses
+    (256), seed (0), max_error (normalised units; required), min_depth (0.1), max_depth (40.0)."""
+    q = np.ascontiguousarray(job["query_obs"], dtype=np.float64).reshape(-1, 4)
+    t = np.ascontiguousarray(job["train_obs"], dtype=np.float64).reshape(-1, 4)
+    if len(q) != len(t):
+        raise ValueError("a pair has one observation on each side")
+    u = job.get("usable")
+    if u is not None:
+        u = np.ascontiguousarray(u, dtype=np.uint8).reshape(-1)
+        if len(u) != len(q):
+            raise ValueError("a usable array has one byte per pair")
+    inl = np.zeros(len(q), np.uint8)
+    a = FeVerifyArgs()
+    a.n, a.n_hypotheses = len(q), int(job.get("n_hypotheses", 256))
+    a.query_obs, a.train_obs = (q.ctypes.data, t.ctypes.data) if len(q) else (None, None)
+    a.usable = None if u is None or not len(q) else u.ctypes.data
+    a.T_cam1_cam0[:] = [float(v) for v in np.asarray(job["T_cam1_cam0"], dtype=np.float64).reshape(-1)]
+    a.seed = int(job.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+    a.max_error, a.min_depth, a.max_depth = float(job["max_error"]), float(job.get("min_depth", 0.1)), float(job.get("max_depth", 40.0))
+    a.inlier = inl.ctypes.data if len(q) else None
+    a.n_usable = a.n_inliers = a.status = -9
+    a.best = -9
+    return a, (q, t, u), inl
+
+
+def _verify_result(a, inl):
+    """What a verify call returns for one job."""
+    return dict(n_usable=int(a.n_usable), n_inliers=int(a.n_inliers), best=int(a.best), status=int(a.status), inlier=inl,
+                R=np.array(a.R[:], np.float64).reshape(3, 3), t=np.array(a.t[:], np.float64), info=np.array(a.info[:], np.float64).reshape(6, 6), rms=float(a.rms))
+
+
 def _imu_steps(steps):
     """mskf_imu_step records as a contiguous IMU_STEP array (None / empty: no steps)."""
     if steps is None:
@@ -211,6 +245,7 @@ class Context:
         self._direct_pending = None
         self._dsc_pending = None
         self._mch_pending = None
+        self._vfy_pending = None
 
     def close(self):
         if self.h:
@@ -317,6 +352,41 @@ class Context:
         self.L.mskf_fe_match.argtypes = [C.c_void_p, C.POINTER(FeMatchArgs)]
         _chk(self.L.mskf_fe_match(self.h, C.byref(a)))
         return m, int(a.n_matches)
+
+    def verify_batch(self, jobs):
+        """One mskf_fe_verify_batch: the stereo RANSAC pose check of matched pairs ("Geometric verification"), a
+        job per dict of jobs (see _verify_args).  Returns a dict per job: n_usable, n_inliers, best (the winning hypothesis or -1),
+        status (0 ok, 1 no hypothesis, 2 refinement failed), inlier uint8[n] at the original indices, R (3, 3) and t with
+        p_keyframe = R p_query + t in cam0 coordinates, info (6, 6; J^T J in the order [theta, t]) and rms."""
+        self.verify_batch_begin(jobs)
+        return self.verify_batch_end()
+
+    def verify_batch_begin(self, jobs):
+        """mskf_fe_verify_batch_begin: stage and enqueue the batch; verify_batch_end returns the results."""
+        built = [_verify_args(j) for j in jobs]
+        n = len(built)
+        args = (FeVerifyArgs * max(n, 1))(*[b[0] for b in built])
+        self.L.mskf_fe_verify_batch_begin.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeVerifyArgs)]
+        _chk(self.L.mskf_fe_verify_batch_begin(self.h, n, args))
+        self._vfy_pending = (built, args)             # must stay alive until _end
+
+    def verify_batch_end(self):
+        """mskf_fe_verify_batch_end: the results of the batch begun, None when there was none."""
+        self.L.mskf_fe_verify_batch_end.argtypes = [C.c_void_p]
+        _chk(self.L.mskf_fe_verify_batch_end(self.h))
+        pend, self._vfy_pending = self._vfy_pending, None
+        if pend is None:
+            return None
+        built, args = pend
+        return [_verify_result(args[i], b[2]) for i, b in enumerate(built)]
+
+    def verify(self, query_obs, train_obs, T_cam1_cam0, max_error, usable=None, n_hypotheses=256, seed=0, min_depth=0.1, max_depth=40.0):
+        """mskf_fe_verify: one job; returns its result dict (verify_batch); synchronises."""
+        a, _keep, inl = _verify_args(dict(query_obs=query_obs, train_obs=train_obs, T_cam1_cam0=T_cam1_cam0, max_error=max_error, usable=usable,
+                                          n_hypotheses=n_hypotheses, seed=seed, min_depth=min_depth, max_depth=max_depth))
+        self.L.mskf_fe_verify.argtypes = [C.c_void_p, C.POINTER(FeVerifyArgs)]
+        _chk(self.L.mskf_fe_verify(self.h, C.byref(a)))
+        return _verify_result(a, inl)
 
     def push_stereo_batch(self, streams, cam0s, cam1s, on_device=0):
         """One mskf_fe_push_stereo_batch: host images (on_device = 0) or device addresses (1: copied, 2: borrowed)."""

@@ -72,6 +72,8 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     if (c->pend_dsc.done) (void)hipEventDestroy(c->pend_dsc.done);
     c->mch_jobs.release(); c->mch_in.release(); c->mch_out.release();
     if (c->pend_mch.done) (void)hipEventDestroy(c->pend_mch.done);
+    c->vfy_jobs.release(); c->vfy_in.release(); c->vfy_out.release();
+    if (c->pend_vfy.done) (void)hipEventDestroy(c->pend_vfy.done);
     c->ekf_desc.release();
     c->pred_arena.release();
     if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
@@ -112,13 +114,13 @@ int mskf_wait_event(mskf_ctx *c, hipEvent_t *ev_slot, bool record) {
     }
     if (!c->flag_h) {
         unsigned int *p = nullptr;
-        MSKF_HIPCHK(hipHostMalloc((void **)&p, 8 * 64, hipHostMallocCoherent | hipHostMallocMapped));      // one cache line per slot
-        std::memset(p, 0, 8 * 64);
+        MSKF_HIPCHK(hipHostMalloc((void **)&p, mskf_ctx::kMarkSlots * 64, hipHostMallocCoherent | hipHostMallocMapped));      // one cache line per slot
+        std::memset(p, 0, mskf_ctx::kMarkSlots * 64);
         c->flag_h = p;
     }
     int k = 0;
-    while (k < 8 && c->flag_slot[k] && c->flag_slot[k] != ev_slot) ++k;
-    if (k == 8) { mskf_set_error("too many completion marks"); return MSKF_ERR_INVALID; }
+    while (k < mskf_ctx::kMarkSlots && c->flag_slot[k] && c->flag_slot[k] != ev_slot) ++k;
+    if (k == mskf_ctx::kMarkSlots) { mskf_set_error("too many completion marks"); return MSKF_ERR_INVALID; }
     if (record) c->flag_slot[k] = ev_slot;       // a slot is claimed when its first mark is recorded; waiting only reads the context
     else if (c->flag_slot[k] != ev_slot) { mskf_set_error("waiting for a completion mark that was never recorded"); return MSKF_ERR_INVALID; }
     volatile unsigned int *w = c->flag_h + 16 * k;
@@ -269,7 +271,7 @@ extern "C" int mskf_ctx_set_timing(mskf_ctx *c, int enable) {
 
 extern "C" int mskf_ctx_set_wait_mode(mskf_ctx *c, int block) {
     if (!c) return MSKF_ERR_INVALID;
-    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active || c->pend_mch.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
+    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active || c->pend_mch.active || c->pend_vfy.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
     c->wait_block = block != 0;
     return MSKF_OK;
 }
@@ -1522,3 +1524,121 @@ extern "C" int mskf_fe_match_batch(mskf_ctx *ctx, int n, mskf_fe_match_args *arg
 }
 
 extern "C" int mskf_fe_match(mskf_ctx *ctx, mskf_fe_match_args *args) { return mskf_fe_match_batch(ctx, 1, args); }
+
+// ------------------------------------------------------------------------------------------ geometric verification (fe_verify.h)
+static int refuse_verify(const char *why) { mskf_set_error(std::string("verify: ") + why); return MSKF_ERR_INVALID; }
+
+// the job record of args a over `pairs` (host or device side) with n_usable staged pairs
+static FeVerifyDev verify_job(const mskf_fe_verify_args &a, const double *pairs, int n_usable, unsigned long long *keys) {
+    FeVerifyDev j;
+    std::memset(&j, 0, sizeof(j));
+    j.pairs = pairs; j.keys = keys;
+    j.cam = fv_cam(a.T_cam1_cam0);
+    j.seed = a.seed;
+    j.max_error2 = a.max_error * a.max_error; j.min_depth = a.min_depth;
+    j.n = n_usable; j.K = a.n_hypotheses;
+    return j;
+}
+
+static void verify_write(mskf_fe_verify_args &a, const FvResult &r) {
+    a.n_usable = r.n_usable; a.n_inliers = r.n_inliers; a.best = r.best; a.status = r.status;
+    std::memcpy(a.R, r.R, sizeof(a.R)); std::memcpy(a.t, r.t, sizeof(a.t)); std::memcpy(a.info, r.info, sizeof(a.info));
+    a.rms = r.rms;
+}
+
+// Bytes of the verify arenas of a context (device side): 0 until the first verify call that launches.  NOT part of the C ABI
+// (declared in mskf_internal.h only, like the fe_launch_* functions): tests/test_gpu_verify.py reads it.
+extern "C" int fe_mark_slots_used(const mskf_ctx *ctx) {      // completion-mark slots claimed so far (spinning mode); internal, as below
+    int k = 0;
+    while (k < mskf_ctx::kMarkSlots && ctx->flag_slot[k]) ++k;
+    return k;
+}
+extern "C" size_t fe_verify_arena_bytes(const mskf_ctx *ctx) {
+    return ctx->vfy_jobs.cap * sizeof(FeVerifyDev) + ctx->vfy_in.cap * sizeof(double) + ctx->vfy_out.cap * sizeof(unsigned long long);
+}
+
+extern "C" int mskf_fe_verify_batch_begin(mskf_ctx *ctx, int n, mskf_fe_verify_args *args) {
+    // ---- plan: every refusal comes from here, before anything is touched
+    if (!ctx || !args) return refuse_verify("null argument");
+    if (n <= 0) return refuse_verify("a batch has at least one job");
+    if (ctx->pend_vfy.active) return refuse_verify("a verify batch of this context is still pending (call mskf_fe_verify_batch_end)");
+    int max_n = 0, max_K = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_verify_args &a = args[i];
+        if (a.n < 0) return refuse_verify("negative pair count");
+        if (a.n > FV_MAX_N) return refuse_verify("more than 4096 pairs in a job");
+        if (a.n > 0 && !a.query_obs) return refuse_verify("null query_obs with n > 0");
+        if (a.n > 0 && !a.train_obs) return refuse_verify("null train_obs with n > 0");
+        if (a.n_hypotheses < 1 || a.n_hypotheses > FV_MAX_K) return refuse_verify("n_hypotheses must be 1 .. 1024");
+        if (!(a.max_error > 0.0) || !std::isfinite(a.max_error)) return refuse_verify("max_error must be > 0 and finite");
+        if (!(a.min_depth > 0.0) || !(a.min_depth < a.max_depth) || !std::isfinite(a.max_depth)) return refuse_verify("depths must be 0 < min_depth < max_depth, finite");
+        for (int k = 0; k < 12; ++k) if (!std::isfinite(a.T_cam1_cam0[k])) return refuse_verify("T_cam1_cam0 is not finite");
+        max_n = std::max(max_n, a.n);
+        max_K = std::max(max_K, a.n_hypotheses);
+    }
+    // ---- stage (host memory of the call's own): triangulate, compact the usable pairs in order, keep the map back
+    mskf_ctx::PendingVerify &V = ctx->pend_vfy;                // (no batch is pending: nobody reads it)
+    V.in_off.assign(n, 0); V.orig.assign(n, {});
+    std::vector<std::vector<double>> staged(n);
+    size_t in_doubles = 0;
+    int max_usable = 0;
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_verify_args &a = args[i];
+        V.in_off[i] = in_doubles;
+        const int nu = fv_stage_host(fv_cam(a.T_cam1_cam0), a.n, a.query_obs, a.train_obs, a.usable, a.min_depth, a.max_depth, staged[i], V.orig[i]);
+        in_doubles += (size_t)FV_PAIR * nu;
+        max_usable = std::max(max_usable, nu);
+    }
+    if (max_usable < 3) {                  // no job can form a hypothesis: no launch, no batch pending, _end is a no-op
+        for (int i = 0; i < n; ++i) {
+            const FeVerifyDev j = verify_job(args[i], staged[i].data(), (int)V.orig[i].size(), nullptr);
+            verify_write(args[i], fv_finish_host(j, V.orig[i].data(), args[i].n, FV_KEY_NONE, args[i].inlier));
+        }
+        return MSKF_OK;
+    }
+    // ---- grow
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = ctx->vfy_jobs.ensure(n)) != MSKF_OK || (rc = ctx->vfy_in.ensure(in_doubles)) != MSKF_OK || (rc = ctx->vfy_out.ensure((size_t)FV_MAX_BLOCKS * n)) != MSKF_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (!staged[i].empty()) std::memcpy(ctx->vfy_in.h + V.in_off[i], staged[i].data(), sizeof(double) * staged[i].size());
+        ctx->vfy_jobs.h[i] = verify_job(args[i], ctx->vfy_in.d + V.in_off[i], (int)V.orig[i].size(), ctx->vfy_out.d + (size_t)FV_MAX_BLOCKS * i);
+    }
+    // ---- enqueue: one copy in, one launch, one copy out
+    DrainOnError drain{ctx->stream, true};
+    const MskfCopy cp[2] = {{ctx->vfy_in.d, ctx->vfy_in.h, sizeof(double) * in_doubles}, {ctx->vfy_jobs.d, ctx->vfy_jobs.h, sizeof(FeVerifyDev) * (size_t)n}};
+    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
+    fe_launch_verify(ctx->vfy_jobs.d, n, max_K, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
+    { const MskfCopy out = {ctx->vfy_out.h, ctx->vfy_out.d, sizeof(unsigned long long) * FV_MAX_BLOCKS * (size_t)n}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
+    MSKF_HIPCHK(hipGetLastError());
+    V.n = n; V.args = args;
+    if ((rc = mskf_batch_arm(ctx, V)) != MSKF_OK) return rc;
+    drain.armed = false;
+    return MSKF_OK;
+}
+
+// Wait for the batch started by mskf_fe_verify_batch_begin; merge every job's block keys, re-form the winner, mark its inliers
+// and refine it (all with fe_verify.h, on the staged pairs still in vfy_in's host side).  No-op when nothing is pending.
+extern "C" int mskf_fe_verify_batch_end(mskf_ctx *ctx) {
+    if (!ctx) return MSKF_ERR_INVALID;
+    mskf_ctx::PendingVerify &V = ctx->pend_vfy;
+    if (!V.active) return MSKF_OK;
+    MSKF_HIPCHK(hipSetDevice(ctx->device));
+    if (const int rc = mskf_batch_finish(ctx, V)) return rc;
+    for (int i = 0; i < V.n; ++i) {
+        mskf_fe_verify_args &a = V.args[i];
+        const FeVerifyDev j = verify_job(a, ctx->vfy_in.h + V.in_off[i], (int)V.orig[i].size(), nullptr);
+        unsigned long long key = FV_KEY_NONE;
+        const int blocks = (a.n_hypotheses + FV_HYP_BLOCK - 1) / FV_HYP_BLOCK;
+        for (int b = 0; b < blocks; ++b) key = fv_merge(key, ctx->vfy_out.h[(size_t)FV_MAX_BLOCKS * i + b]);
+        verify_write(a, fv_finish_host(j, V.orig[i].data(), a.n, key, a.inlier));
+    }
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_verify_batch(mskf_ctx *ctx, int n, mskf_fe_verify_args *args) {
+    const int rc = mskf_fe_verify_batch_begin(ctx, n, args);
+    return rc != MSKF_OK ? rc : mskf_fe_verify_batch_end(ctx);
+}
+
+extern "C" int mskf_fe_verify(mskf_ctx *ctx, mskf_fe_verify_args *args) { return mskf_fe_verify_batch(ctx, 1, args); }

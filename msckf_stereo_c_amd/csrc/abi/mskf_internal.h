@@ -11,6 +11,7 @@
 #include "../hip/fe_mask.h"
 #include "../hip/fe_brief.h"
 #include "../hip/fe_match.h"
+#include "../hip/fe_verify.h"
 #include "../hip/ekf_device.h"
 #include "host_math.h"
 
@@ -31,6 +32,10 @@ void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *mask
 void fe_launch_describe(const FeDescribeDev *jobs_dev, int n_jobs, int max_pts, hipStream_t st);
 // descriptor matching (fe_match.h): jobs of any size and count in one launch, cross-checked or not; max_nq / max_nt = the largest counts
 void fe_launch_match(const FeMatchDev *jobs_dev, int n_jobs, int max_nq, int max_nt, hipStream_t st);
+// geometric verification (fe_verify.h): jobs of any n and K in one launch; max_K = the largest hypothesis count
+void fe_launch_verify(const FeVerifyDev *jobs_dev, int n_jobs, int max_K, hipStream_t st);
+extern "C" int fe_mark_slots_used(const struct mskf_ctx *ctx);               // internal, for the tests: not in include/mskf_hip.h
+extern "C" size_t fe_verify_arena_bytes(const struct mskf_ctx *ctx);      // internal, for the tests: not in include/mskf_hip.h
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);
@@ -115,6 +120,7 @@ int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 //   a pending describe batch owns dsc_jobs, dsc_in and dsc_out, which nothing else touches: only a describe call refuses for it;
 //   a pending match batch owns mch_jobs, mch_in and mch_out, which nothing else touches: only a match call refuses for it (it
 //   reads no image and no stream, so pushes, frames, describe batches and updates may run between its _begin and its _end);
+//   a pending verify batch owns vfy_jobs, vfy_in and vfy_out in the same way: only a verify call refuses for it;
 //   a pending update (a feature update or a direct update: one slot for both kinds) owns ekf_desc, upd_in and upd_out;
 //   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
 //   descriptors from and writes results into the host side).
@@ -175,8 +181,9 @@ struct mskf_ctx {
     hipEvent_t wait_ev = nullptr;     // mark of mskf_wait
     bool wait_block = false;
     volatile unsigned int *flag_h = nullptr;   // pinned host words the mark kernels write (spinning mode), one per mark slot
-    unsigned int flag_seq[8] = {0};
-    hipEvent_t *flag_slot[8] = {nullptr};
+    static constexpr int kMarkSlots = 16;      // completion-mark slots: every kind of pending batch and wait_ev claims one at its first use (nine kinds today)
+    unsigned int flag_seq[kMarkSlots] = {0};
+    hipEvent_t *flag_slot[kMarkSlots] = {nullptr};
     PinnedDev<char> cell_arena;       // per-cell maximum keys of every stream of the last push batch (one D2H copy)
     PinnedDev<char> trk_in, trk_out;  // input points / results of every stream of a track batch (one copy each way)
     unsigned long long push_gen = 0;
@@ -216,6 +223,15 @@ struct mskf_ctx {
         int n = 0; struct mskf_fe_match_args *args = nullptr;
         std::vector<size_t> out_off;           // per job: byte offset of its matches in mch_out
     } pend_mch;
+    // geometric verification (mskf_fe_verify_batch_*; fe_verify.h): arenas of the call's own, empty until the first call, owned by pend_vfy
+    PinnedDev<FeVerifyDev> vfy_jobs;
+    PinnedDev<double> vfy_in;                      // the staged usable pairs of every job of a verify batch (one copy in)
+    PinnedDev<unsigned long long> vfy_out;         // FV_MAX_BLOCKS keys per job (one copy out)
+    struct PendingVerify : PendingBatch {
+        int n = 0; struct mskf_fe_verify_args *args = nullptr;
+        std::vector<size_t> in_off;            // per job: where its staged pairs start in vfy_in, in doubles
+        std::vector<std::vector<int>> orig;    // per job: the original index of every staged pair
+    } pend_vfy;
     // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
     struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;
 };

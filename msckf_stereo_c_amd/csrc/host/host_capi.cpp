@@ -267,7 +267,7 @@ int mskfh_add_keyframe(void *h, int stream) {
     if (stream < 0 || stream >= r->n_streams()) return -1;
     ImageProcessor &ip = *r->system(stream).imgproc_ptr_;
     if (!ip.descriptorsOn()) return -1;
-    return ip.keyframes.add(ip.descriptorTime(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(), ip.descriptorValid());
+    return ip.keyframes.add(ip.descriptorTime(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(), ip.descriptorValid(), ip.descriptorObs());
 }
 int mskfh_num_keyframes(void *h, int stream) { return ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.size(); }
 // the feature count of keyframe k, -1: no such keyframe
@@ -293,7 +293,7 @@ int mskfh_query_keyframes(void *h, int stream, int max_distance, float ratio, in
     ImageProcessor &ip = *r->system(stream).imgproc_ptr_;
     if (!ip.descriptorsOn()) { return MSKF_ERR_INVALID; }
     int local;
-    const int rc = ip.keyframes.query(r->group_of(stream, local).ctx(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(),
+    const int rc = ip.keyframes.query(r->group_of(stream, local).ctx(), ip.descriptorTime(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()), ip.descriptors(),
                                       ip.descriptorValid(), max_distance, ratio, cross_check != 0, min_matches);
     return rc != MSKF_OK ? rc : (int)ip.keyframes.hits().size();
 }
@@ -302,6 +302,37 @@ void mskfh_keyframe_hit(void *h, int stream, int i, int *k, double *time, int *n
     const KeyframeHit &hit = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.hits()[i];
     *k = hit.k; *time = hit.time; *n_matches = hit.n_matches;
     if (pairs && !hit.pairs.empty()) std::memcpy(pairs, hit.pairs.data(), 8 * hit.pairs.size());
+}
+// the stereo observations of keyframe k: 4 doubles per feature (mskfh_keyframe_size of them)
+void mskfh_get_keyframe_obs(void *h, int stream, int k, double *obs) {
+    const Keyframe &f = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.at(k);
+    if (!f.obs.empty()) std::memcpy(obs, f.obs.data(), 8 * f.obs.size());
+}
+// The stereo RANSAC pose check of every hit of the stream's last mskfh_query_keyframes against the stream's last frame, one
+// mskf_fe_verify_batch on the stream's context.  Returns the number of records (one per hit; mskfh_keyframe_verification reads
+// them), or a negative mskf status (stale hits among them: mskf_last_error names the reason).
+int mskfh_verify_keyframes(void *h, int stream, int n_hypotheses, uint64_t seed, double max_error, double min_depth, double max_depth) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream < 0 || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    ImageProcessor &ip = *r->system(stream).imgproc_ptr_;
+    if (!ip.descriptorsOn()) return MSKF_ERR_INVALID;
+    int local;
+    std::string why;
+    const int rc = ip.keyframes.verify(r->group_of(stream, local).ctx(), ip.descriptorTime(), std::vector<uint64_t>(ip.descriptorIds().begin(), ip.descriptorIds().end()),
+                                       ip.descriptorObs(), ip.stereoExtrinsics(), n_hypotheses, seed, max_error, min_depth, max_depth, why);
+    ip.keyframes.refused = why;               // empty: the status is mskf_fe_verify_batch's own, and mskf_last_error has its reason
+    return rc != MSKF_OK ? rc : (int)ip.keyframes.verified().size();
+}
+// why the store itself refused the last mskfh_verify_keyframes of the stream ("" when it did not)
+const char *mskfh_verify_refused(void *h, int stream) { return ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.refused.c_str(); }
+// record i of the last verification: ints = k, n_matches, n_usable, n_inliers, best, status; doubles = time, rms, R[9], t[3],
+// info[36] (50 of them); inlier (when not null) takes n_matches bytes, one per pair of the hit
+void mskfh_keyframe_verification(void *h, int stream, int i, int *ints, double *doubles, uint8_t *inlier) {
+    const KeyframeVerification &v = ((MultiRunner *)h)->system(stream).imgproc_ptr_->keyframes.verified()[i];
+    ints[0] = v.k; ints[1] = v.n_matches; ints[2] = v.n_usable; ints[3] = v.n_inliers; ints[4] = v.best; ints[5] = v.status;
+    doubles[0] = v.time; doubles[1] = v.rms;
+    std::memcpy(doubles + 2, v.R, sizeof(v.R)); std::memcpy(doubles + 11, v.t, sizeof(v.t)); std::memcpy(doubles + 14, v.info, sizeof(v.info));
+    if (inlier && !v.inlier.empty()) std::memcpy(inlier, v.inlier.data(), v.inlier.size());
 }
 // MsckfVio::publishCovariance of one stream, or of all (stream < 0); set before the first frame
 void mskfh_runner_publish_covariance(void *h, int stream, int on) {

@@ -126,6 +126,14 @@ void ImageProcessor::describePrepare(mskf_fe_describe_args &a) {
     const size_t n = prev_.size();
     desc_ids_.assign(prev_.id.begin(), prev_.id.end());
     desc_.assign(32 * n, 0); desc_valid_.assign(n, 0);
+    desc_obs_.clear();                          // what publish() has just sent for these features; left empty (KeyframeStore::verify then
+    if (prev_.und0.size() == n && prev_.und1.size() == n) {      // refuses) should the grid ever not carry them for every feature
+        desc_obs_.resize(4 * n);
+        for (size_t i = 0; i < n; ++i) {
+            desc_obs_[4 * i] = prev_.und0[i].x; desc_obs_[4 * i + 1] = prev_.und0[i].y;
+            desc_obs_[4 * i + 2] = prev_.und1[i].x; desc_obs_[4 * i + 3] = prev_.und1[i].y;
+        }
+    }
     a.role = 0; a.n = (int)n;
     a.pts = prev_.cam0.data(); a.desc = desc_.data(); a.valid = desc_valid_.data();
 }

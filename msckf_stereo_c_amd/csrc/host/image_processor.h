@@ -119,11 +119,14 @@ class ImageProcessor {
     // opt-in 256-bit descriptors (mskf_fe_describe_batch; DESIGN.md section 3, "Descriptors") of the features a frame publishes:
     // frame k's cam0 level 0 at the cam0 pixels of the features of frame k's message, in message order.  Off by default; takes
     // effect with the next frame.  descriptorIds() / descriptors() (32 bytes each) / descriptorValid() are those of the last frame.
-    void setDescriptors(bool on) { descriptors_ = on; if (!on) { desc_ids_.clear(); desc_.clear(); desc_valid_.clear(); } }
+    void setDescriptors(bool on) { descriptors_ = on; if (!on) { desc_ids_.clear(); desc_.clear(); desc_valid_.clear(); desc_obs_.clear(); } }
     bool descriptorsOn() const { return descriptors_; }
     const std::vector<FeatureIDType> &descriptorIds() const { return desc_ids_; }
     const std::vector<uint8_t> &descriptors() const { return desc_; }
     const std::vector<uint8_t> &descriptorValid() const { return desc_valid_; }
+    // x0, y0, x1, y1 per id: the undistorted normalised stereo coordinates the frame published for the same features
+    const std::vector<double> &descriptorObs() const { return desc_obs_; }
+    const double *stereoExtrinsics() const { return calib_.T_cam1_cam0; }       // row-major 4x4, p_c1 = R p_c0 + t
     double descriptorTime() const { return cam0_curr_time; }       // the time stamp of the frame they belong to
     // Keyframes of this stream, for a place-recognition caller (keyframes.h): copies of those getters' arrays, added and queried
     // only when the caller says so; empty, and nothing of it runs, otherwise.
@@ -221,6 +224,7 @@ class ImageProcessor {
     bool descriptors_ = false;
     std::vector<FeatureIDType> desc_ids_;
     std::vector<uint8_t> desc_, desc_valid_;
+    std::vector<double> desc_obs_;
     std::ofstream desc_out_;
     static int describeFrame(mskf_ctx *ctx, int n, ImageProcessor *const *ip, mskf_stream *const *streams, FrameScratch &scratch, std::string &err);
     void describePrepare(mskf_fe_describe_args &a);     // the published grid's cam0 pixels on the image that holds this frame

@@ -130,6 +130,20 @@ MATCH_MAX_N = 65535          # FM_MAX_N (csrc/hip/fe_match.h)
 MATCH_NONE = 0xFFFF          # FM_NONE: dist / second without a neighbour
 
 
+class FeVerifyArgs(C.Structure):
+    """mskf_fe_verify_args (include/mskf_hip.h): n pairs of stereo observations, the camera pair, the hypothesis count, seed and
+    thresholds in; the counts, the winning hypothesis, its inlier bytes, the refined pose, its information matrix and rms out."""
+    _fields_ = [("n", C.c_int32), ("n_hypotheses", C.c_int32), ("query_obs", C.c_void_p), ("train_obs", C.c_void_p), ("usable", C.c_void_p),
+                ("T_cam1_cam0", C.c_double * 16), ("seed", C.c_uint64), ("max_error", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double),
+                ("inlier", C.c_void_p), ("n_usable", C.c_int32), ("n_inliers", C.c_int32), ("best", C.c_int32), ("status", C.c_int32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("info", C.c_double * 36), ("rms", C.c_double)]
+
+
+assert C.sizeof(FeVerifyArgs) == 608
+VERIFY_MAX_N = 4096          # FV_MAX_N (csrc/hip/fe_verify.h)
+VERIFY_MAX_K = 1024          # FV_MAX_K
+
+
 def raw_raster(img, fmt):
     """An image in format number fmt as the contiguous array a push takes: (h, w) uint16 for gray16 (native byte order, which the
     device reads as little-endian), (h, w, 3 | 4) uint8 for the colour formats, (h, w) uint8 otherwise.  A wrong shape or a

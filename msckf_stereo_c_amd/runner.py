@@ -87,6 +87,28 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def pose_rotation(q):
+    """R (3, 3) of a POSE record's q = (x, y, z, w): the rotation IMU -> world, p_w = R p_i + p.  The filter's own quaternion is the
+    JPL one of world -> IMU (ekf_meas.h), which has the same four components."""
+    x, y, z, w = (float(v) for v in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def imu_position_from_verification(R, t, pose_k, calib):
+    """The world position of the IMU at the query frame, which is what fuse_position takes, from a verified motion p_k = R p_q + t
+    (query cam0 -> keyframe cam0: what verify_keyframes returns), the keyframe's published pose pose_k (the POSE record of
+    Runner.poses at the keyframe's time: p, q) and calib.T_cam0_imu (p_c = R_ci p_i + t_ci; T_imu_body is taken as the identity):
+        p_w = R_wi(q_k) R_ci^T (R t_ci + t - t_ci) + p_k        ("Geometric verification").
+    The query IMU's origin is t_ci in the query's cam0, R t_ci + t in the keyframe's cam0, R_ci^T (. - t_ci) in the keyframe's IMU
+    frame.  A pure function: it reads nothing of a runner."""
+    T = np.array(calib.T_cam0_imu, np.float64).reshape(4, 4)
+    R_ci, t_ci = T[:3, :3], T[:3, 3]
+    R, t = np.asarray(R, np.float64).reshape(3, 3), np.asarray(t, np.float64).reshape(3)
+    return pose_rotation(pose_k["q"]) @ (R_ci.T @ (R @ t_ci + t - t_ci)) + np.array(pose_k["p"], np.float64)
+
+
 def set_fe_books_on_host(on):
     """Process-wide: 1 = the front-end's bookkeeping stays on the host for every frame (the phased mskf_fe_track path), 0 = whole
     frames on the device wherever the configuration allows (default), -1 = back to the MSKF_FE_BOOKS environment variable."""
@@ -282,7 +304,8 @@ class Runner:
         """Match the stream's last-frame descriptors against every keyframe of that stream in one mskf_fe_match_batch (the query set
         is shared, one job per keyframe; DESIGN.md section 3, "Descriptor matching").  Returns [(k, time, n_matches, pairs)] of the
         keyframes with n_matches >= min_matches, pairs uint64[m, 2] of (query feature id, keyframe feature id) in query order.
-        Verifying a candidate and fusing it (fuse_position) stay with the caller.  Call between runs."""
+        verify_keyframes checks the hits geometrically; deciding on a candidate and fusing it (fuse_position) stay with the caller.
+        Call between runs."""
         self.L.mskfh_query_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
         self.L.mskfh_keyframe_hit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
         n = self.L.mskfh_query_keyframes(self.h, int(stream), int(max_distance), float(ratio), int(bool(cross_check)), int(min_matches))
@@ -296,6 +319,57 @@ class Runner:
             pairs = np.zeros((m.value, 2), np.uint64)
             self.L.mskfh_keyframe_hit(self.h, int(stream), i, C.byref(k), C.byref(t), C.byref(m), _p(pairs))
             out.append((k.value, t.value, m.value, pairs))
+        return out
+
+    def keyframe_obs(self, stream, k):
+        """float64[n, 4] of the stream's keyframe k: x0, y0, x1, y1 per feature, the undistorted normalised stereo coordinates the
+        keyframe's frame published (u0, v0, u1, v1 of msg) for the features of keyframe(stream, k), in their order."""
+        self.L.mskfh_keyframe_size.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self.L.mskfh_get_keyframe_obs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        n = self.L.mskfh_keyframe_size(self.h, int(stream), int(k))
+        if n < 0:
+            raise IndexError("keyframe %d of stream %d" % (k, stream))
+        obs = np.zeros((n, 4), np.float64)
+        self.L.mskfh_get_keyframe_obs(self.h, int(stream), int(k), _p(obs))
+        return obs
+
+    def verify_keyframes(self, stream=0, n_hypotheses=256, max_error=None, min_depth=0.1, max_depth=40.0, min_inliers=12, seed=0):
+        """The stereo RANSAC pose check ("Geometric verification") of every hit of the stream's last
+        query_keyframes, in one mskf_fe_verify_batch: a job per hit, its pairs the hit's matches as (the last frame's, the keyframe's)
+        stereo observations.  max_error is in normalised units, None = 2 px over cam0's fx; that, min_depth = 0.1 m and max_depth =
+        40 m are untuned starting values.  Returns [(k, time, n_matches, n_inliers, R, t, info, rms, inlier_pairs)] of the hits with
+        status 0 and n_inliers >= min_inliers: p_keyframe = R p_query + t in cam0 coordinates (imu_position_from_verification turns
+        that into what fuse_position takes), info (6, 6) = J^T J in the order [theta, t] (a covariance is sigma^2 info^-1), rms of the
+        residuals, inlier_pairs uint64[n_inliers, 2] the (query feature id, keyframe feature id) of the inliers.  min_inliers is this
+        method's filter, not the ABI's.  Raises when a newer frame has been described since the query: the hits are then not this
+        frame's.  The runner still decides nothing about keyframe policy and never calls fuse_position itself.  Call between runs."""
+        if max_error is None:
+            max_error = 2.0 / float(self.calib.cam0_intrinsics[0])
+        self.L.mskfh_verify_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double]
+        self.L.mskfh_keyframe_verification.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.L.mskfh_verify_refused.argtypes = [C.c_void_p, C.c_int]
+        self.L.mskfh_verify_refused.restype = C.c_char_p
+        n = self.L.mskfh_verify_keyframes(self.h, int(stream), int(n_hypotheses), int(seed) & 0xFFFFFFFFFFFFFFFF, float(max_error), float(min_depth), float(max_depth))
+        if n < 0:
+            from . import capi
+            why = self.L.mskfh_verify_refused(self.h, int(stream)).decode() if 0 <= int(stream) < self.n else ""
+            raise MskfError("verify_keyframes: mskf status %d: %s" % (n, why or capi.lib().mskf_last_error().decode()), n)
+        self.L.mskfh_keyframe_hit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
+        out = []
+        for i in range(n):
+            ints, dbl = np.zeros(6, np.int32), np.zeros(50, np.float64)
+            self.L.mskfh_keyframe_verification(self.h, int(stream), i, _p(ints), _p(dbl), None)
+            k, n_matches, _n_usable, n_inliers, _best, status = (int(v) for v in ints)
+            inl = np.zeros(max(n_matches, 1), np.uint8)
+            self.L.mskfh_keyframe_verification(self.h, int(stream), i, _p(ints), _p(dbl), _p(inl))
+            if status != 0 or n_inliers < min_inliers:
+                continue
+            hk, ht, hm = C.c_int(0), C.c_double(0), C.c_int(0)
+            pairs = np.zeros((n_matches, 2), np.uint64)          # record i belongs to hit i of the query
+            self.L.mskfh_keyframe_hit(self.h, int(stream), i, C.byref(hk), C.byref(ht), C.byref(hm), _p(pairs))
+            assert (hk.value, hm.value) == (k, n_matches)
+            out.append((k, float(dbl[0]), n_matches, n_inliers, dbl[2:11].reshape(3, 3).copy(), dbl[11:14].copy(), dbl[14:50].reshape(6, 6).copy(), float(dbl[1]),
+                        pairs[inl[:n_matches] != 0].copy()))
         return out
 
     def _raw(self, img, fmt):
