@@ -541,7 +541,8 @@ int mskf_ekf_remove_clone(mskf_stream *s, int clone_index);
 /* Remove up to two clones per stream in one launch: idx[2*i], idx[2*i+1] are clone indices in the CURRENT
  * state order (distinct; -1 = none).  Equivalent to mskf_ekf_remove_clone calls (msckf_vio.cpp:1161-1181). */
 int mskf_ekf_remove_clones_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, const int32_t *idx);
-/* Diagnostics for tests: raw work buffers of the stream's last update (0 Hs, 1 rowmask, 2 S, 3 T, 4 W, 5 act). */
+/* Diagnostics for tests: raw work buffers of the stream's last update (0 Hs, 1 rowmask, 2 S, 3 T, 4 W, 5 act);
+ * 6 is the current covariance plane itself, all ld x ld doubles, of which only [0,d) x [0,d) is live. */
 int mskf_ekf_debug_read(mskf_stream *s, int which, void *out, size_t capacity, int *ld_out);
 /* Change mskf_ekf_cfg.compression_mode of a live stream (0 auto, 1 Gram + Cholesky only, 2 Householder TSQR always, 3 the rule
  * of msckf_vio.cpp:795-821 as written); takes effect with the stream's next update.  Not while an update of the stream is pending. */

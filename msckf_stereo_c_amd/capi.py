@@ -726,6 +726,17 @@ class Stream:
         _chk(self.L.mskf_ekf_get_cov(self.h, _p(P), P.size))
         return P
 
+    def ekf_debug_plane(self):
+        """mskf_ekf_debug_read(which = 6): the whole current covariance plane, ld x ld doubles.  Only [0, d) x [0, d) is live;
+        the rest is what earlier calls left there.  For tests."""
+        ld = C.c_int()
+        probe = np.zeros(1)
+        self.L.mskf_ekf_debug_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        _chk(self.L.mskf_ekf_debug_read(self.h, 6, _p(probe), probe.nbytes, C.byref(ld)))
+        out = np.zeros((ld.value, ld.value))
+        _chk(self.L.mskf_ekf_debug_read(self.h, 6, _p(out), out.nbytes, C.byref(ld)))
+        return out
+
     def ekf_propagate(self, Phi, Q):
         Phi = np.ascontiguousarray(Phi, dtype=np.float64).reshape(-1, 21, 21)
         Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, 21, 21)

@@ -853,7 +853,8 @@ extern "C" int mskf_ekf_update_direct(mskf_stream *s, mskf_ekf_direct_args *args
 }
 
 // Test / diagnostic access to the work buffers of the last update of a stream (not used by the product path):
-// which = 0 Hs (max_rows x ld), 1 rowmask (max_rows, 8-byte), 2 S (ld x ld), 3 T (ld x ld), 4 W (ld x ld), 5 act (ld ints).
+// which = 0 Hs (max_rows x ld), 1 rowmask (max_rows, 8-byte), 2 S (ld x ld), 3 T (ld x ld), 4 W (ld x ld), 5 act (ld ints),
+// 6 the current covariance plane P, all ld x ld doubles (only [0,d) x [0,d) is live; the rest is what earlier calls left).
 // Copies min(capacity, size) bytes; *ld_out = row stride in doubles.
 extern "C" int mskf_ekf_debug_read(mskf_stream *s, int which, void *out, size_t capacity, int *ld_out) {
     if (!s || !out) return MSKF_ERR_INVALID;
@@ -870,6 +871,7 @@ extern "C" int mskf_ekf_debug_read(mskf_stream *s, int which, void *out, size_t 
         case 3: src = E.T; bytes = pl; break;
         case 4: src = E.W; bytes = pl; break;
         case 5: src = E.act; bytes = sizeof(int) * (size_t)E.ld; break;
+        case 6: src = E.P; bytes = pl; break;
         default: return MSKF_ERR_INVALID;
     }
     if (!src) return MSKF_ERR_INVALID;
