@@ -27,7 +27,9 @@ HIP_SRCS = [
     "hip/fe_describe.hip",
     "hip/fe_match.hip",
     "hip/fe_verify.hip",
+    "abi/mskf_capi_ctx.cpp",
     "abi/mskf_capi_fe.cpp",
+    "abi/mskf_capi_kf.cpp",
     "abi/mskf_capi_ekf.cpp",
 ]
 HOST_SRCS = [

@@ -299,7 +299,6 @@ static int readout_end(mskf_ctx *ctx, int rec) {
     mskf_ctx::PendingReadOut &V = ctx->pend_ro;
     if (!V.active) return MSKF_OK;
     if (V.rec != rec) return mskf_refuse_if_owned(ctx, MSKF_ARENAS_PRED);      // the other kind is pending: names it and its _end
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
     const int rc = mskf_batch_finish(ctx, V);
     if (rc != MSKF_OK) return rc;
     mskf_t_collect(ctx);

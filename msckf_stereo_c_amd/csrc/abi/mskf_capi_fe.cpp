@@ -1,308 +1,11 @@
-// mskf_capi_fe.cpp — C-ABI: contexts, streams and the front-end entry points (include/mskf_hip.h).
-#include <sys/prctl.h>
-#include <time.h>
+// mskf_capi_fe.cpp — C-ABI: the per-frame front end: stream settings, push, cell maxima, track and the device frame (include/mskf_hip.h).
+#include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <chrono>
-#include <atomic>
-#include <map>
-#include <type_traits>
+#include <initializer_list>
 #include <vector>
 #include "mskf_internal.h"
-
-static thread_local std::string g_last_error;
-void mskf_set_error(const std::string &s) { g_last_error = s; }
-
-extern "C" const char *mskf_last_error(void) { return g_last_error.c_str(); }
-extern "C" int mskf_abi_version(void) { return 4; }   // 4: round 4 (2-point RANSAC inside the device frame: mskf_fe_frame_args.R_p_c / ransac_draws, mskf_fe_set_grid's draw counter)
-
-extern "C" int mskf_ctx_create(int device, mskf_ctx **out) { return mskf_ctx_create_prio(device, 0, out); }
-
-extern "C" int mskf_ctx_create_prio(int device, int high_priority, mskf_ctx **out) {
-    if (!out) return MSKF_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        mskf_set_error("no HIP device visible (this library has no CPU fallback)");
-        return MSKF_ERR_NO_DEVICE;
-    }
-    if (device < 0 || device >= n) { mskf_set_error("device index out of range"); return MSKF_ERR_INVALID; }
-    MSKF_HIPCHK(hipSetDevice(device));
-    mskf_ctx *c = new mskf_ctx();
-    c->device = device;
-    hipError_t e;
-    if (high_priority) {
-        int lo = 0, hi = 0;   // numerically lower = more urgent
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi);
-    } else {
-        e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    }
-    if (e != hipSuccess) { delete c; mskf_set_error(hipGetErrorString(e)); return MSKF_ERR_HIP; }
-    { const char *w = std::getenv("MSKF_WAIT"); c->wait_block = w && std::strcmp(w, "block") == 0; }
-    *out = c;
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ctx_create_shared(mskf_ctx *parent, mskf_ctx **out) {
-    if (!parent || !out) return MSKF_ERR_INVALID;
-    mskf_ctx *c = new mskf_ctx();
-    c->device = parent->device;
-    c->stream = parent->stream;
-    c->owns_stream = false;
-    c->wait_block = parent->wait_block;
-    *out = c;
-    return MSKF_OK;
-}
-
-extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    mskf_t_collect(c);
-    for (auto &e : c->t_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (int i = 0; i < 3; ++i) c->desc[i].release();
-    for (int i = 0; i < 2; ++i) c->mask_desc[i].release();
-    c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
-    c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
-    c->book_desc.release(); c->book_out.release(); c->grid_in.release();
-    if (c->pend_frame.done) (void)hipEventDestroy(c->pend_frame.done);
-    c->dsc_jobs.release(); c->dsc_in.release(); c->dsc_out.release();
-    if (c->pend_dsc.done) (void)hipEventDestroy(c->pend_dsc.done);
-    c->mch_jobs.release(); c->mch_in.release(); c->mch_out.release();
-    if (c->pend_mch.done) (void)hipEventDestroy(c->pend_mch.done);
-    c->vfy_jobs.release(); c->vfy_in.release(); c->vfy_out.release();
-    if (c->pend_vfy.done) (void)hipEventDestroy(c->pend_vfy.done);
-    c->ekf_desc.release();
-    c->pred_arena.release();
-    if (c->wait_ev) (void)hipEventDestroy(c->wait_ev);
-    if (c->flag_h) (void)hipHostFree((void *)c->flag_h);
-    if (c->cell_ev) (void)hipEventDestroy(c->cell_ev);
-    if (c->pend_trk.done) (void)hipEventDestroy(c->pend_trk.done);
-    if (c->pend_upd.done) (void)hipEventDestroy(c->pend_upd.done);
-    if (c->pend_ro.done) (void)hipEventDestroy(c->pend_ro.done);
-    if (c->owns_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-extern "C" void fe_launch_mark(volatile unsigned int *flag, unsigned int seq, hipStream_t st);
-extern "C" size_t fe_book_lds_budget(void);
-
-extern "C" void fe_launch_copy(void *const *dst, const void *const *src, const size_t *bytes, int n_segs, hipStream_t st);
-int mskf_copy_async(mskf_ctx *c, const MskfCopy *segs, int n) {
-    for (int i0 = 0; i0 < n; i0 += MSKF_COPY_SEGS) {
-        void *dst[MSKF_COPY_SEGS]; const void *src[MSKF_COPY_SEGS]; size_t bytes[MSKF_COPY_SEGS];
-        int m = 0;
-        for (int i = i0; i < n && i < i0 + MSKF_COPY_SEGS; ++i) {
-            if (!segs[i].bytes) continue;
-            if (((uintptr_t)segs[i].dst | (uintptr_t)segs[i].src) & 15) { mskf_set_error("staging copy with an unaligned end"); return MSKF_ERR_INVALID; }
-            dst[m] = segs[i].dst; src[m] = segs[i].src; bytes[m] = segs[i].bytes; ++m;
-        }
-        if (m) fe_launch_copy(dst, src, bytes, m, c->stream);
-    }
-    MSKF_HIPCHK(hipGetLastError());
-    return MSKF_OK;
-}
-
-int mskf_wait_event(mskf_ctx *c, hipEvent_t *ev_slot, bool record) {
-    if (c->wait_block) {
-        if (!*ev_slot) MSKF_HIPCHK(hipEventCreateWithFlags(ev_slot, hipEventDisableTiming | hipEventBlockingSync));
-        if (record) { MSKF_HIPCHK(hipEventRecord(*ev_slot, c->stream)); return MSKF_OK; }
-        MSKF_HIPCHK(hipEventSynchronize(*ev_slot));
-        return MSKF_OK;
-    }
-    if (!c->flag_h) {
-        unsigned int *p = nullptr;
-        MSKF_HIPCHK(hipHostMalloc((void **)&p, mskf_ctx::kMarkSlots * 64, hipHostMallocCoherent | hipHostMallocMapped));      // one cache line per slot
-        std::memset(p, 0, mskf_ctx::kMarkSlots * 64);
-        c->flag_h = p;
-    }
-    int k = 0;
-    while (k < mskf_ctx::kMarkSlots && c->flag_slot[k] && c->flag_slot[k] != ev_slot) ++k;
-    if (k == mskf_ctx::kMarkSlots) { mskf_set_error("too many completion marks"); return MSKF_ERR_INVALID; }
-    if (record) c->flag_slot[k] = ev_slot;       // a slot is claimed when its first mark is recorded; waiting only reads the context
-    else if (c->flag_slot[k] != ev_slot) { mskf_set_error("waiting for a completion mark that was never recorded"); return MSKF_ERR_INVALID; }
-    volatile unsigned int *w = c->flag_h + 16 * k;
-    if (record) {
-        // the mark is a stream write-value command (no dispatch: a one-thread kernel waits 37 us for a CU slot on a busy
-        // device, profiles/r02_kernel_stats.csv of the kernel-mark build); a runtime that refuses the command on pinned host
-        // memory falls back to the one-thread kernel k_mark
-        static std::atomic<bool> use_write{true};   // (contexts are driven from several host threads)
-        ++c->flag_seq[k];
-        if (use_write.load(std::memory_order_relaxed)) {
-            if (hipStreamWriteValue32(c->stream, (void *)w, c->flag_seq[k], 0) == hipSuccess) return MSKF_OK;
-            (void)hipGetLastError();
-            use_write.store(false, std::memory_order_relaxed);
-        }
-        fe_launch_mark(w, c->flag_seq[k], c->stream);
-        MSKF_HIPCHK(hipGetLastError());
-        return MSKF_OK;
-    }
-    const unsigned int want = c->flag_seq[k];
-    // a mark that never arrives (device fault, lost queue) must not hang the caller for ever: after MSKF_WAIT_TIMEOUT_S
-    // seconds (default 120) the stream is asked for its error state and the wait fails
-    static const double limit_s = [] { const char *e = std::getenv("MSKF_WAIT_TIMEOUT_S"); const double v = e ? std::atof(e) : 120.0; return v > 0 ? v : 120.0; }();
-    // MSKF_WAIT=nap[:us]: the same mark, polled between short sleeps (default 40 us) instead of spun on: a wait of some
-    // milliseconds then costs the core a few per cent of its time and the waiter at most one sleep of latency, which leaves a
-    // host that runs under a CPU quota its cores for the other groups' host phases
-    static const long nap_ns = [] {
-        const char *e = std::getenv("MSKF_WAIT");
-        if (!e || std::strncmp(e, "nap", 3) != 0) return 0L;
-        const long us = e[3] == ':' ? std::atol(e + 4) : 40L;
-        return 1000L * (us > 0 ? us : 40L);
-    }();
-    if (nap_ns) {
-        static thread_local bool slack_set = false;
-        if (!slack_set) { (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL); slack_set = true; }     // (the default slack of 50 us would double every sleep)
-    }
-    unsigned long long spins = 0, naps = 0;
-    bool timing = false;
-    std::chrono::steady_clock::time_point t0;
-    while ((int)(__atomic_load_n((const unsigned int *)w, __ATOMIC_ACQUIRE) - want) < 0) {
-        bool check;
-        if (nap_ns && spins >= 64) { const struct timespec ts = {0, nap_ns}; (void)nanosleep(&ts, nullptr); check = (++naps & 0xFFULL) == 0; }
-        else { __builtin_ia32_pause(); check = (++spins & 0xFFFFFULL) == 0; }
-        if (check) {                                             // about every 10 ms
-            const auto now = std::chrono::steady_clock::now();
-            if (!timing) { t0 = now; timing = true; }
-            else if (std::chrono::duration<double>(now - t0).count() > limit_s) {
-                const hipError_t e = hipStreamQuery(c->stream);
-                mskf_set_error(e != hipSuccess && e != hipErrorNotReady ? hipGetErrorString(e) : "completion mark not written within the wait limit");
-                std::fprintf(stderr, "mskf_wait_event: ctx %p slot %d mark %u wanted %u, stream query %d\n", (void *)c, k, *w, want, (int)e);
-                return MSKF_ERR_HIP;
-            }
-        }
-    }
-    return MSKF_OK;
-}
-
-int mskf_batch_arm(mskf_ctx *c, PendingBatch &b) {
-    const int rc = mskf_wait_event(c, &b.done, true);
-    if (rc == MSKF_OK) b.active = true;
-    return rc;
-}
-int mskf_batch_finish(mskf_ctx *c, PendingBatch &b) {
-    const int rc = mskf_wait_event(c, &b.done, false);
-    if (rc == MSKF_OK) b.active = false;
-    return rc;
-}
-
-int mskf_refuse_if_owned(const mskf_ctx *c, MskfArenas which) {
-    const char *owner = nullptr;
-    switch (which) {
-        case MSKF_ARENAS_FE:
-            if (c->pend_trk.active) owner = "a track batch of this context is still pending (call mskf_fe_track_batch_end)";
-            else if (c->pend_frame.active) owner = "a device frame of this context is still pending (call mskf_fe_frame_batch_end)";
-            break;
-        case MSKF_ARENAS_UPDATE:
-            if (c->pend_upd.active)
-                owner = c->pend_upd.direct ? "a direct update batch of this context is still pending (call mskf_ekf_update_direct_batch_end)"
-                                           : "an update batch of this context is still pending (call mskf_ekf_update_batch_end)";
-            break;
-        case MSKF_ARENAS_PRED:
-            if (c->pend_ro.active)
-                owner = c->pend_ro.rec == 3 ? "a position-variance read-out of this context is still pending (call mskf_ekf_get_pos_var_batch_end)"
-                                            : "an odometry-covariance read-out of this context is still pending (call mskf_ekf_get_odom_cov_batch_end)";
-            break;
-    }
-    if (!owner) return MSKF_OK;
-    mskf_set_error(owner);
-    return MSKF_ERR_INVALID;
-}
-
-int mskf_wait(mskf_ctx *c) {
-    int rc = mskf_wait_event(c, &c->wait_ev, true);
-    if (rc != MSKF_OK) return rc;
-    return mskf_wait_event(c, &c->wait_ev, false);
-}
-
-extern "C" int mskf_ctx_sync(mskf_ctx *c) {
-    if (!c) return MSKF_ERR_INVALID;
-    { const int rc = mskf_wait(c); if (rc != MSKF_OK) return rc; }
-    mskf_t_collect(c);
-    return MSKF_OK;
-}
-
-int mskf_t_begin(mskf_ctx *c, int kind) {
-    if (!c->timing || !c->t_gate) return -1;
-    if ((c->t_all[kind]++ % c->timing_period) != 0) return -1;      // sampled: the events themselves cost device and host time
-    TimingSlot t;
-    if (!c->t_pool.empty()) { t.a = c->t_pool.back().first; t.b = c->t_pool.back().second; c->t_pool.pop_back(); }
-    else {
-        if (hipEventCreate(&t.a) != hipSuccess || hipEventCreate(&t.b) != hipSuccess) return -1;
-    }
-    t.kind = kind; t.units = 0;
-    (void)hipEventRecord(t.a, c->stream);
-    c->t_pending.push_back(t);
-    return (int)c->t_pending.size() - 1;
-}
-void mskf_t_end(mskf_ctx *c, int slot, long long units) {
-    if (slot < 0) return;
-    (void)hipEventRecord(c->t_pending[slot].b, c->stream);
-    c->t_pending[slot].units = units;
-}
-// Units of a slot that was begun earlier: the slot index is only valid until the next mskf_t_collect (any synchronising
-// call of the context collects), so it is checked against the pending list and the kind it was begun with.
-void mskf_t_set_units(mskf_ctx *c, int slot, int kind, long long units) {
-    if (slot < 0 || (size_t)slot >= c->t_pending.size() || c->t_pending[slot].kind != kind) return;
-    c->t_pending[slot].units = units;
-}
-void mskf_t_collect(mskf_ctx *c) {
-    for (auto &t : c->t_pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, t.a, t.b) == hipSuccess) {
-            c->t_ms[t.kind] += ms; c->t_launches[t.kind] += 1; c->t_units[t.kind] += t.units;
-        }
-        c->t_pool.push_back({t.a, t.b});
-    }
-    c->t_pending.clear();
-}
-
-extern "C" int mskf_ctx_set_timing(mskf_ctx *c, int enable) {
-    if (!c) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(c->device));
-    MSKF_HIPCHK(hipStreamSynchronize(c->stream));
-    mskf_t_collect(c);
-    c->timing = enable != 0;
-    c->timing_period = enable > 1 ? enable : 1;
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ctx_set_wait_mode(mskf_ctx *c, int block) {
-    if (!c) return MSKF_ERR_INVALID;
-    if (c->pend_trk.active || c->pend_upd.active || c->pend_ro.active || c->pend_frame.active || c->pend_dsc.active || c->pend_mch.active || c->pend_vfy.active) { mskf_set_error("a batch of this context is pending"); return MSKF_ERR_INVALID; }
-    c->wait_block = block != 0;
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ctx_timing_gate(mskf_ctx *c, int on) {
-    if (!c) return MSKF_ERR_INVALID;
-    c->t_gate = on != 0;          // no synchronisation: launches already begun keep the state they were begun with
-    return MSKF_OK;
-}
-
-extern "C" int mskf_ctx_get_timing(mskf_ctx *c, double *ms, long long *launches, long long *units, int reset) {
-    if (!c || !ms || !launches || !units) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(c->device));
-    MSKF_HIPCHK(hipStreamSynchronize(c->stream));
-    mskf_t_collect(c);
-    for (int k = 0; k < MSKF_K_COUNT; ++k) {
-        // sampled timing: the sums are scaled from the timed launches to all launches of the kind
-        const double sc = c->t_launches[k] > 0 ? (double)c->t_all[k] / (double)c->t_launches[k] : 0.0;
-        ms[k] = c->t_ms[k] * sc; launches[k] = c->t_launches[k] > 0 ? c->t_all[k] : 0; units[k] = (long long)((double)c->t_units[k] * sc);
-        if (reset) { c->t_ms[k] = 0; c->t_launches[k] = 0; c->t_units[k] = 0; c->t_all[k] = 0; }
-    }
-    return MSKF_OK;
-}
-
-extern "C" void *mskf_ctx_hip_stream(mskf_ctx *c) { return c ? (void *)c->stream : nullptr; }
-
-extern "C" int mskf_ctx_get_host_time(mskf_ctx *c, double out[4], int reset) {
-    if (!c || !out) return MSKF_ERR_INVALID;
-    for (int k = 0; k < 4; ++k) { out[k] = c->host_s[k]; if (reset) c->host_s[k] = 0; }
-    return MSKF_OK;
-}
 
 void fill_pyr(const mskf_stream *s, int idx, PyrDev &p) {
     for (int l = 0; l < MSKF_LEVELS; ++l) {
@@ -310,190 +13,7 @@ void fill_pyr(const mskf_stream *s, int idx, PyrDev &p) {
         p.w[l] = s->lw[l];
         p.h[l] = s->lh[l];
     }
-    if (s->lvl0[idx]) p.lvl[0] = s->lvl0[idx];
-}
-
-// The stream's book allocation: ONE sequence of take()s, run on a null base to obtain the size and on the allocation to
-// set the pointers (every region rounded up to 256 bytes).  D holds the capacities on entry.
-static size_t book_carve(char *base, FeBookDev &D, FeGridArr grid[3]) {
-    size_t off = 0;
-    auto take = [&](auto *&p, size_t count) {
-        p = (std::remove_reference_t<decltype(p)>)((uintptr_t)base + off);
-        off += (sizeof(*p) * count + 255) & ~(size_t)255;
-    };
-    const size_t cap = (size_t)D.cap, cand_cap = (size_t)D.cand_cap, det_cap = (size_t)D.det_cap;
-    take(D.st, 1);
-    for (int g = 0; g < 3; ++g) {
-        FeGridArr &G = grid[g];
-        take(G.id, cap); take(G.lifetime, cap); take(G.code, cap); take(G.response, cap);
-        take(G.cam0, cap); take(G.cam1, cap); take(G.und0, cap); take(G.und1, cap);
-    }
-    D.tracked = grid[2];
-    take(D.det_pt, det_cap); take(D.det_score, det_cap);
-    take(D.cand_pt, cand_cap); take(D.cand_index, cand_cap); take(D.cand_score, cand_cap);
-    take(D.cand_off, (size_t)D.n_cells + 1); take(D.cand_cnt, (size_t)D.n_cells + 1); take(D.cell_count, (size_t)D.n_codes + 1);
-    take(D.t_out0, cap); take(D.t_out1, cap); take(D.t_und0, cap); take(D.t_und1, cap); take(D.t_status, cap);
-    take(D.c_out0, cand_cap); take(D.c_out1, cand_cap); take(D.c_und0, cand_cap); take(D.c_und1, cand_cap); take(D.c_status, cand_cap);
-    take(D.rs_pair, 4 * cap); take(D.rs_pt, 4 * cap); take(D.rs_scalar, 48);       // fe_book.h: the scratch of the 2-point RANSAC
-    return off;
-}
-
-// Device-side books of a stream (fe_book.h): the three feature lists, detection / candidate lists and the results of the two
-// track calls, in ONE allocation, and the descriptor of everything about them that never changes (Book::dev).  Streams whose
-// grid_min / grid_max exceed the short-list bound of the kernels keep their books on the host (dev.cap stays 0).
-static int book_alloc(mskf_stream *s) {
-    mskf_stream::Book &K = s->book;
-    const mskf_fe_cfg &fe = s->fe;
-    if (fe.grid_min_feature_num > FB_MAXK || fe.grid_max_feature_num > FB_MAXK || fe.grid_min_feature_num < 0 ||
-        fe.grid_max_feature_num < fe.grid_min_feature_num) return MSKF_OK;
-    FeBookDev D{};
-    D.grid_row = fe.grid_row; D.grid_col = fe.grid_col; D.grid_min = fe.grid_min_feature_num; D.grid_max = fe.grid_max_feature_num;
-    D.grid_h = s->h / fe.grid_row; D.grid_w = s->w / fe.grid_col;                 // image_processor.cpp:250-251
-    if (D.grid_h <= 0 || D.grid_w <= 0) return MSKF_OK;
-    D.n_cells = fe.grid_row * fe.grid_col;
-    D.n_codes = std::max(((s->h - 1) / D.grid_h) * fe.grid_col + (s->w - 1) / D.grid_w + 1, D.n_cells);   // Q7: partial rows / columns
-    D.cap = D.n_codes * std::max(fe.grid_max_feature_num, 1) + 8;
-    D.cand_cap = D.n_cells * std::max(fe.grid_max_feature_num, 1) + 8;
-    D.det_cap = fe.det_rows * fe.det_cols;
-    // the bookkeeping kernel keeps its lists in LDS: a configuration whose lists do not fit the budget the kernel can get
-    // (a very fine detector grid) keeps its books on the host
-    if (4 * fe_book_scratch_ints(D.cap, D.cand_cap, D.det_cap, D.n_codes, D.det_cap) > fe_book_lds_budget()) return MSKF_OK;
-    D.det_rows = fe.det_rows; D.det_cols = fe.det_cols; D.det_cw = s->det_cw; D.det_ch = s->det_ch;
-    D.thr_score = fe.fast_threshold * 256;
-    D.q4 = (fe.compat_flags & MSKF_COMPAT_Q4_RESPONSE_INDEX) ? 1 : 0;
-    // twoPointRansac between the tracks (:482-500; commented out in the reference, Q5): iterations as :920-921
-    D.ransac = (fe.compat_flags & MSKF_COMPAT_Q5_NO_RANSAC) ? 0 : 1;
-    D.ransac_iters = static_cast<int>(std::ceil(std::log(1 - 0.99) / std::log(1 - 0.7 * 0.7)));
-    D.ransac_thr = fe.ransac_threshold;
-    D.ransac_npu[0] = 2.0 / (s->cam0.K[0] + s->cam0.K[1]); D.ransac_npu[1] = 2.0 / (s->cam1.K[0] + s->cam1.K[1]);
-    const size_t bytes = book_carve(nullptr, D, K.grid);
-    MSKF_HIPCHK(hipMalloc((void **)&K.mem, bytes));
-    MSKF_HIPCHK(hipMemsetAsync(K.mem, 0, bytes, s->ctx->stream));
-    MSKF_HIPCHK(hipStreamSynchronize(s->ctx->stream));
-    book_carve(K.mem, D, K.grid);
-    K.dev = D;
-    return MSKF_OK;
-}
-
-extern "C" int mskf_stream_create(mskf_ctx *ctx, const mskf_calib *calib, const mskf_fe_cfg *fe, const mskf_ekf_cfg *ekf,
-                                  mskf_stream **out) {
-    if (!ctx || !calib || !fe || !ekf || !out) return MSKF_ERR_INVALID;
-    for (int m : {calib->cam0_model, calib->cam1_model})
-        if (m != MSKF_MODEL_RADTAN && m != MSKF_MODEL_EQUIDISTANT) {
-            mskf_set_error("unknown distortion model (radtan and equidistant are implemented)");
-            return MSKF_ERR_UNSUPPORTED;
-        }
-    if (calib->width < 64 || calib->height < 64 || fe->det_rows <= 0 || fe->det_cols <= 0 || fe->grid_row <= 0 || fe->grid_col <= 0)
-        return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    mskf_stream *s = new mskf_stream();
-    s->ctx = ctx;
-    s->ctx_ekf = ctx;
-    s->home_ctx = ctx;
-    s->calib = *calib; s->fe = *fe; s->ekf = *ekf;
-    s->w = calib->width; s->h = calib->height;
-    size_t off = 0;
-    int w = s->w, h = s->h;
-    for (int l = 0; l < MSKF_LEVELS; ++l) {
-        s->lw[l] = w; s->lh[l] = h; s->lvl_off[l] = off;
-        off += ((size_t)w * h + 255) & ~(size_t)255;
-        w = (w + 1) / 2; h = (h + 1) / 2;
-    }
-    s->pyr_bytes = off;
-    int rc = MSKF_OK;
-    for (int i = 0; i < 3 && rc == MSKF_OK; ++i) {
-        hipError_t e = hipMalloc((void **)&s->pyr[i], s->pyr_bytes);
-        if (e != hipSuccess) { mskf_set_error(hipGetErrorString(e)); rc = MSKF_ERR_HIP; }
-    }
-    // point capacity: every live grid slot plus every detector cell
-    const int det_cells = fe->det_rows * fe->det_cols;
-    s->pt_cap = (fe->grid_row + 1) * (fe->grid_col + 1) * (fe->grid_max_feature_num + 1) + det_cells + 64;
-    if (rc == MSKF_OK) rc = mskf_ekf_stream_init(s);
-    if (rc != MSKF_OK) { mskf_stream_destroy(s); return rc; }
-
-    for (int i = 0; i < 4; ++i) {
-        s->cam0.K[i] = calib->cam0_intrinsics[i]; s->cam0.D[i] = calib->cam0_distortion[i];
-        s->cam0.model = calib->cam0_model; s->cam1.model = calib->cam1_model;
-        s->cam1.K[i] = calib->cam1_intrinsics[i]; s->cam1.D[i] = calib->cam1_distortion[i];
-    }
-    // image_processor.cpp:63-72 (loadParameters) and :544,:587-591 (stereoMatch)
-    using namespace hm;
-    Rigid m4_cam0_imu = Rigid::from_rowmajor16(calib->T_cam0_imu);
-    Mat3 R_cam0_imu = m4_cam0_imu.R.transpose();
-    Vec3 t_cam0_imu = -(R_cam0_imu * m4_cam0_imu.t);
-    Rigid m4_cam1_cam0 = Rigid::from_rowmajor16(calib->T_cam1_cam0);
-    Rigid T_cam1_imu = m4_cam1_cam0 * m4_cam0_imu;
-    Mat3 R_cam1_imu = T_cam1_imu.R.transpose();
-    Vec3 t_cam1_imu = -(R_cam1_imu * T_cam1_imu.t);
-    Mat3 R_cam0_cam1 = R_cam1_imu.transpose() * R_cam0_imu;
-    Vec3 t_cam0_cam1 = R_cam1_imu.transpose() * (t_cam0_imu - t_cam1_imu);
-    Mat3 E = skew(t_cam0_cam1) * R_cam0_cam1;
-    std::memcpy(s->R01, R_cam0_cam1.m, sizeof(s->R01));
-    std::memcpy(s->E, E.m, sizeof(s->E));
-    const double norm_pixel_unit = 4.0 / (s->cam0.K[0] + s->cam0.K[1] + s->cam1.K[0] + s->cam1.K[1]);
-    s->epi_thresh = fe->stereo_threshold * norm_pixel_unit;
-    s->det_ch = (s->h + fe->det_rows - 1) / fe->det_rows;
-    s->det_cw = (s->w + fe->det_cols - 1) / fe->det_cols;
-    rc = book_alloc(s);
-    if (rc != MSKF_OK) { mskf_stream_destroy(s); return rc; }
-    ctx->streams.push_back(s);
-    *out = s;
-    return MSKF_OK;
-}
-
-extern "C" mskf_ctx *mskf_stream_ctx(mskf_stream *s) { return s ? s->ctx : nullptr; }
-extern "C" mskf_ctx *mskf_stream_ekf_ctx(mskf_stream *s) { return s ? s->ctx_ekf : nullptr; }
-extern "C" int mskf_stream_set_ekf_ctx(mskf_stream *s, mskf_ctx *c) {
-    if (!s || !c || c->device != s->ctx->device) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(c->device));
-    MSKF_HIPCHK(hipStreamSynchronize(s->ctx_ekf->stream));
-    MSKF_HIPCHK(hipStreamSynchronize(c->stream));
-    s->ctx_ekf = c;
-    return MSKF_OK;
-}
-
-extern "C" int mskf_stream_rebind(mskf_stream *s, mskf_ctx *fe_ctx, mskf_ctx *ekf_ctx) {
-    if (!s) return MSKF_ERR_INVALID;
-    if ((fe_ctx && fe_ctx->device != s->home_ctx->device) || (ekf_ctx && ekf_ctx->device != s->home_ctx->device)) return MSKF_ERR_INVALID;
-    if (fe_ctx) s->ctx = fe_ctx;
-    if (ekf_ctx) s->ctx_ekf = ekf_ctx;
-    return MSKF_OK;
-}
-
-struct mskf_point { hipEvent_t ev = nullptr; };
-extern "C" int mskf_ctx_record_point(mskf_ctx *ctx, mskf_point **point) {
-    if (!ctx || !point) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    if (!*point) { *point = new mskf_point(); MSKF_HIPCHK(hipEventCreateWithFlags(&(*point)->ev, hipEventDisableTiming)); }
-    MSKF_HIPCHK(hipEventRecord((*point)->ev, ctx->stream));
-    return MSKF_OK;
-}
-extern "C" int mskf_ctx_wait_point(mskf_ctx *ctx, mskf_point *point) {
-    if (!ctx || !point || !point->ev) return MSKF_ERR_INVALID;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    MSKF_HIPCHK(hipStreamWaitEvent(ctx->stream, point->ev, 0));
-    return MSKF_OK;
-}
-extern "C" void mskf_point_destroy(mskf_point *point) {
-    if (!point) return;
-    if (point->ev) (void)hipEventDestroy(point->ev);
-    delete point;
-}
-
-extern "C" void mskf_stream_destroy(mskf_stream *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->ctx->device);
-    (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->ctx_ekf && s->ctx_ekf != s->ctx) (void)hipStreamSynchronize(s->ctx_ekf->stream);
-    for (int i = 0; i < 3; ++i) if (s->pyr[i]) (void)hipFree(s->pyr[i]);
-    if (s->book.mem) (void)hipFree(s->book.mem);
-    if (s->eq.mem) (void)hipFree(s->eq.mem);
-    if (s->px.raw) (void)hipFree(s->px.raw);
-    for (int c = 0; c < 2; ++c) if (s->mask.dev[c]) (void)hipFree(s->mask.dev[c]);
-    mskf_ekf_stream_free(s);
-    auto &v = s->home_ctx->streams;
-    for (size_t i = 0; i < v.size(); ++i) if (v[i] == s) { v.erase(v.begin() + i); break; }
-    delete s;
+    p.lvl[0] = level0(s, idx);
 }
 
 static void fill_fe_desc(const mskf_stream *s, FeStreamDev &d) {
@@ -513,6 +33,20 @@ static void fill_fe_desc(const mskf_stream *s, FeStreamDev &d) {
 // The push generation as the 8-bit tag the cell keys carry in their top byte (1 .. 255; 0 is "never written").
 static inline unsigned int push_gen_tag(unsigned long long push_gen) { return (unsigned int)((push_gen - 1) % 255ULL) + 1U; }
 static inline size_t cell_key_bytes(const mskf_stream *s) { return sizeof(unsigned long long) * (size_t)s->fe.det_rows * s->fe.det_cols; }
+
+// The last step of a setter that replaces device blocks of a stream (the opt-in settings below: cold paths, called outside a run).
+// Launches that still read old blocks finish first -- the whole device, since the stream may have been pushed on another context
+// before a rebind (mskf_stream_rebind) -- then the old blocks are freed; if that wait fails, the fresh ones are, and the stream stays.
+static int replace_blocks(std::initializer_list<void *> old, std::initializer_list<void *> fresh) {
+    bool any = false;
+    for (void *p : old) any = any || p;
+    if (!any) return MSKF_OK;
+    const hipError_t e = hipDeviceSynchronize();
+    for (void *p : e == hipSuccess ? old : fresh) if (p) (void)hipFree(p);
+    if (e == hipSuccess) return MSKF_OK;
+    mskf_set_error(hipGetErrorString(e));
+    return MSKF_ERR_HIP;
+}
 
 // ---- opt-in equalisation of pushed images (include/mskf_hip.h; arithmetic and job layout: fe_equalize.h)
 static int eq_validate(const mskf_stream *s, const mskf_fe_equalize *cfg) {
@@ -547,13 +81,7 @@ extern "C" int mskf_fe_set_equalize(mskf_stream *s, const mskf_fe_equalize *cfg)
             E.part[c] = part_bytes ? (int *)(E.mem + 2 * lut_bytes + c * part_bytes) : nullptr;
         }
     }
-    if (s->eq.mem) {
-        // pushes that still read the old scratch finish first: the whole device, since the stream may have been pushed on another
-        // context before a rebind (mskf_stream_rebind); the call is made outside a run, so the wait costs nothing that matters
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) { if (E.mem) (void)hipFree(E.mem); mskf_set_error(hipGetErrorString(e)); return MSKF_ERR_HIP; }
-        (void)hipFree(s->eq.mem);
-    }
+    if (const int rc = replace_blocks({s->eq.mem}, {E.mem})) return rc;
     s->eq = E;
     return MSKF_OK;
 }
@@ -601,12 +129,7 @@ extern "C" int mskf_fe_set_input_format(mskf_stream *s, const mskf_fe_input_form
     X.cfg = *cfg; X.bpp = px_bpp(cfg->format);
     MSKF_HIPCHK(hipSetDevice(s->ctx->device));
     if (cfg->format != PX_GRAY8) MSKF_HIPCHK(hipMalloc((void **)&X.raw, 2 * (size_t)s->w * s->h * X.bpp));
-    if (s->px.raw) {
-        // pushes that still read the old staging finish first (the whole device: mskf_fe_set_equalize has the reason)
-        const hipError_t e = hipDeviceSynchronize();
-        if (e != hipSuccess) { if (X.raw) (void)hipFree(X.raw); mskf_set_error(hipGetErrorString(e)); return MSKF_ERR_HIP; }
-        (void)hipFree(s->px.raw);
-    }
+    if (const int rc = replace_blocks({s->px.raw}, {X.raw})) return rc;
     s->px = X;
     return MSKF_OK;
 }
@@ -635,11 +158,6 @@ extern "C" int mskf_fe_set_mask(mskf_stream *s, const mskf_fe_mask *cfg) {
     const uint8_t *const src[2] = {cfg->cam0, cfg->cam1};
     const size_t words = (size_t)s->h * fm_pitch_words(s->w);
     MSKF_HIPCHK(hipSetDevice(s->ctx->device));
-    auto give_up = [&M](hipError_t e) {
-        for (int c = 0; c < 2; ++c) if (M.dev[c]) (void)hipFree(M.dev[c]);
-        mskf_set_error(hipGetErrorString(e));
-        return MSKF_ERR_HIP;
-    };
     if (src[0] || src[1]) {
         M.margin = cfg->margin;
         std::vector<uint8_t> usable((size_t)s->w * s->h);
@@ -650,15 +168,14 @@ extern "C" int mskf_fe_set_mask(mskf_stream *s, const mskf_fe_mask *cfg) {
             fm_pack(usable.data(), s->w, s->h, M.host[c].data());
             hipError_t e = hipMalloc((void **)&M.dev[c], sizeof(uint32_t) * words);
             if (e == hipSuccess) e = hipMemcpy(M.dev[c], M.host[c].data(), sizeof(uint32_t) * words, hipMemcpyHostToDevice);     // (caller memory's image: as set_cov)
-            if (e != hipSuccess) return give_up(e);
+            if (e != hipSuccess) {
+                for (int k = 0; k < 2; ++k) if (M.dev[k]) (void)hipFree(M.dev[k]);
+                mskf_set_error(hipGetErrorString(e));
+                return MSKF_ERR_HIP;
+            }
         }
     }
-    if (s->mask.any()) {
-        // launches that still read the old planes finish first (a cold path: call it outside a run)
-        const hipError_t e = hipStreamSynchronize(s->ctx->stream);
-        if (e != hipSuccess) return give_up(e);
-        for (int c = 0; c < 2; ++c) if (s->mask.dev[c]) (void)hipFree(s->mask.dev[c]);
-    }
+    if (const int rc = replace_blocks({s->mask.dev[0], s->mask.dev[1]}, {M.dev[0], M.dev[1]})) return rc;
     s->mask = std::move(M);
     return MSKF_OK;
 }
@@ -809,7 +326,7 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
         // an equalising stream reads a device image where the caller has it (on_device 1 and 2 alike) and writes its own plane
         const bool eq_from_caller = eq && !cv && (on_device == 1 || on_device == 2);
         for (int c = 0; c < 2; ++c) {
-            const int pi = c == 0 ? s->i_curr0 : s->i_curr1;
+            const int pi = pyr_of_role(s, 1 + c);
             uint8_t *base = s->pyr[pi];
             if (cv) {
                 const uint8_t *raw = img[c];
@@ -824,7 +341,7 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
             }
             if (eq) eql.add(ctx->eq_jobs.h, s, c, eq_from_caller ? img[c] : base, base + s->lvl_off[0]);
             Pyr3Job &j = ctx->jobs.h[2 * (size_t)i + c];
-            j.src = s->lvl0[pi] ? s->lvl0[pi] : base + s->lvl_off[0];
+            j.src = level0(s, pi);
             j.d1 = base + s->lvl_off[1]; j.d2 = base + s->lvl_off[2]; j.d3 = base + s->lvl_off[3];
             j.w0 = s->lw[0]; j.h0 = s->lh[0];
         }
@@ -989,7 +506,7 @@ static size_t track_out_block(char *base, size_t np, TrackOut &o) {       // (a 
     const size_t pts = sizeof(mskf_point2f) * np;
     o.out0 = (mskf_point2f *)b; o.out1 = (mskf_point2f *)(b + pts); o.und0 = (mskf_point2f *)(b + 2 * pts); o.und1 = (mskf_point2f *)(b + 3 * pts);
     o.status = (uint8_t *)(b + 4 * pts);
-    return (4 * pts + np + 63) & ~(size_t)63;
+    return round_up(4 * pts + np, 64);
 }
 
 extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, const mskf_fe_track_args *args) {
@@ -1014,7 +531,7 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         if (!s->has_curr) { mskf_set_error("no stereo pair pushed yet"); return MSKF_ERR_INVALID; }
         in_off[i] = in_bytes; out_off[i] = out_bytes;
         TrackOut o;
-        in_bytes += (sizeof(mskf_point2f) * (size_t)a.n + 63) & ~(size_t)63;
+        in_bytes += round_up(sizeof(mskf_point2f) * (size_t)a.n, 64);
         out_bytes += track_out_block(nullptr, (size_t)a.n, o);
         max_pts = std::max(max_pts, a.n);
     }
@@ -1038,22 +555,17 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    DrainOnError drain{st};
-    {
-        drain.armed = true;
-        const MskfCopy cp[3] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, mask_cp};
-        if ((rc = mskf_copy_async(ctx, cp, masked ? 3 : 2)) != MSKF_OK) return rc;
-    }
-    // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
-    const int ts = mskf_t_begin(ctx, MSKF_K_LK);
-    fe_launch_track(ctx->desc[1].d, n, max_pts, st);
-    mskf_t_end(ctx, ts, 0);
-    if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
-    { const MskfCopy cp = {ctx->trk_out.h, ctx->trk_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &cp, 1)) != MSKF_OK) return rc; }
-    MSKF_HIPCHK(hipGetLastError());
-    ctx->pend_trk.n = n; ctx->pend_trk.args = args; ctx->pend_trk.ts = ts;
-    if ((rc = mskf_batch_arm(ctx, ctx->pend_trk)) != MSKF_OK) return rc;
-    drain.armed = false;
+    const MskfCopy cp[3] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, mask_cp};
+    mskf_ctx::PendingTrack &T = ctx->pend_trk;
+    T.n = n; T.args = args;
+    rc = mskf_enqueue_staged(ctx, T, cp, masked ? 3 : 2, [&] {
+        // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
+        T.ts = mskf_t_begin(ctx, MSKF_K_LK);
+        fe_launch_track(ctx->desc[1].d, n, max_pts, st);
+        mskf_t_end(ctx, T.ts, 0);
+        if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
+    }, MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
+    if (rc != MSKF_OK) return rc;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
 }
@@ -1063,7 +575,6 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
 extern "C" int mskf_fe_track_batch_end(mskf_ctx *ctx) {
     if (!ctx) return MSKF_ERR_INVALID;
     if (!ctx->pend_trk.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
     const int rc = mskf_batch_finish(ctx, ctx->pend_trk);
     if (rc != MSKF_OK) return rc;
     const mskf_ctx::PendingTrack &T = ctx->pend_trk;
@@ -1123,7 +634,7 @@ extern "C" int mskf_fe_set_grid(mskf_stream *s, int n, const uint64_t *id, const
     MSKF_HIPCHK(hipStreamSynchronize(st));      // (also: the previous set_grid's copy has read grid_in)
     // the seven arrays through the context's pinned grid_in, one staging copy
     const FeGridArr &G = K.grid[K.parity];
-    const size_t n8 = (8 * (size_t)n + 63) & ~(size_t)63, n4 = (4 * (size_t)n + 63) & ~(size_t)63;
+    const size_t n8 = round_up(8 * (size_t)n, 64), n4 = round_up(4 * (size_t)n, 64);
     const size_t o_st = 5 * n8 + n4;
     const int rc = ctx->grid_in.ensure(o_st + sizeof(FeBookState));
     if (rc != MSKF_OK) return rc;
@@ -1182,7 +693,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         const FeBookDev &D = K.dev;
         FeExport x;
         out_off[i] = out_bytes;
-        out_bytes += (fe_book_export(nullptr, D.cap, x) + 255) & ~(size_t)255;
+        out_bytes += round_up(fe_book_export(nullptr, D.cap, x), 256);
         scratch_bytes = std::max(scratch_bytes, 4 * fe_book_scratch_ints(D.cap, D.cand_cap, D.det_cap, D.n_codes, D.det_cap));
         max_prev = std::max(max_prev, K.n_prev);
         // candidates are counted on the device: the launch is sized from the last frame's count, a block takes several point
@@ -1263,7 +774,6 @@ extern "C" int mskf_fe_frame_batch_end(mskf_ctx *ctx) {
     if (!ctx) return MSKF_ERR_INVALID;
     mskf_ctx::PendingFrame &F = ctx->pend_frame;
     if (!F.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
     const int rc = mskf_batch_finish(ctx, F);
     if (rc != MSKF_OK) return rc;
     const auto t_h1 = std::chrono::steady_clock::now();
@@ -1299,346 +809,14 @@ extern "C" int mskf_fe_frame_batch_end(mskf_ctx *ctx) {
 
 extern "C" int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h) {
     if (!s || !out || role < 0 || role > 2 || level < 0 || level >= MSKF_LEVELS) return MSKF_ERR_INVALID;
-    const int idx = role == 0 ? s->i_prev0 : (role == 1 ? s->i_curr0 : s->i_curr1);
+    const int idx = pyr_of_role(s, role);
     const size_t bytes = (size_t)s->lw[level] * s->lh[level];
     if ((size_t)capacity < bytes) return MSKF_ERR_CAPACITY;
     MSKF_HIPCHK(hipSetDevice(s->ctx->device));
     MSKF_HIPCHK(hipStreamSynchronize(s->ctx->stream));
-    const uint8_t *src = (level == 0 && s->lvl0[idx]) ? s->lvl0[idx] : s->pyr[idx] + s->lvl_off[level];
+    const uint8_t *src = level == 0 ? level0(s, idx) : s->pyr[idx] + s->lvl_off[level];
     MSKF_HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
     if (w) *w = s->lw[level];
     if (h) *h = s->lh[level];
     return MSKF_OK;
 }
-
-// ------------------------------------------------------------------------------------------ descriptors (fe_brief.h)
-extern "C" void mskf_fe_descriptor_pattern(int8_t out[4 * FB_TESTS]) {
-    static constexpr FbPattern pat = fb_make_pattern();
-    if (out) std::memcpy(out, pat.t, sizeof(pat.t));
-}
-
-static int refuse_describe(const char *why) { mskf_set_error(std::string("describe: ") + why); return MSKF_ERR_INVALID; }
-
-// One stream's block of a describe batch: np points in dsc_in, FB_BYTES * np descriptor bytes and np validity bytes in dsc_out.
-static inline size_t describe_in_bytes(size_t np) { return (sizeof(mskf_point2f) * np + 63) & ~(size_t)63; }
-static inline size_t describe_out_bytes(size_t np) { return ((FB_BYTES + 1) * np + 63) & ~(size_t)63; }
-
-extern "C" int mskf_fe_describe_batch_begin(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args) {
-    // ---- plan: every refusal comes from here, before anything is touched
-    if (!ctx || !streams || !args) return refuse_describe("null argument");
-    if (n <= 0) return refuse_describe("a batch has at least one stream");
-    if (const int rc = mskf_refuse_if_owned(ctx, MSKF_ARENAS_FE)) return rc;
-    if (ctx->pend_dsc.active) return refuse_describe("a describe batch of this context is still pending (call mskf_fe_describe_batch_end)");
-    size_t in_bytes = 0, out_bytes = 0;
-    int max_pts = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_stream *s = streams[i];
-        const mskf_fe_describe_args &a = args[i];
-        if (!s) return refuse_describe("null stream");
-        if (s->ctx != ctx) return refuse_describe("a stream of another context");
-        if (a.role < 0 || a.role > 2) return refuse_describe("role must be 0 (prev cam0), 1 (curr cam0) or 2 (curr cam1)");
-        if (a.n < 0) return refuse_describe("negative point count");
-        if (a.n > 0 && (!a.pts || !a.desc || !a.valid)) return refuse_describe("null pts, desc or valid with n > 0");
-        const int idx = a.role == 0 ? s->i_prev0 : (a.role == 1 ? s->i_curr0 : s->i_curr1);
-        if (!s->held[idx]) return refuse_describe(a.role == 0 ? "the stream holds no previous image yet" : "no stereo pair pushed yet");
-        in_bytes += describe_in_bytes((size_t)a.n);
-        out_bytes += describe_out_bytes((size_t)a.n);
-        max_pts = std::max(max_pts, a.n);
-    }
-    if (max_pts <= 0) return MSKF_OK;      // nothing to describe: no batch pending, _end is a no-op
-    // ---- grow
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ctx->dsc_jobs.ensure(n)) != MSKF_OK || (rc = ctx->dsc_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->dsc_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    std::vector<size_t> &out_off = ctx->pend_dsc.out_off;      // (no batch is pending: nobody reads it)
-    out_off.resize(n);
-    size_t in_off = 0, o_off = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_stream *s = streams[i];
-        const mskf_fe_describe_args &a = args[i];
-        const size_t np = (size_t)a.n;
-        const int idx = a.role == 0 ? s->i_prev0 : (a.role == 1 ? s->i_curr0 : s->i_curr1);
-        FeDescribeDev &j = ctx->dsc_jobs.h[i];
-        j.img = s->lvl0[idx] ? s->lvl0[idx] : s->pyr[idx] + s->lvl_off[0];
-        j.w = s->w; j.h = s->h; j.pitch = s->w;
-        if (np) std::memcpy(ctx->dsc_in.h + in_off, a.pts, sizeof(mskf_point2f) * np);
-        j.pts = (const float *)(ctx->dsc_in.d + in_off);
-        j.n = a.n; j.pad_ = 0;
-        j.desc = (uint8_t *)(ctx->dsc_out.d + o_off);
-        j.valid = j.desc + FB_BYTES * np;
-        out_off[i] = o_off;
-        in_off += describe_in_bytes(np); o_off += describe_out_bytes(np);
-    }
-    // ---- enqueue: one copy in, one launch, one copy out
-    DrainOnError drain{ctx->stream, true};
-    const MskfCopy cp[2] = {{ctx->dsc_in.d, ctx->dsc_in.h, in_bytes}, {ctx->dsc_jobs.d, ctx->dsc_jobs.h, sizeof(FeDescribeDev) * (size_t)n}};
-    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
-    fe_launch_describe(ctx->dsc_jobs.d, n, max_pts, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
-    { const MskfCopy out = {ctx->dsc_out.h, ctx->dsc_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
-    MSKF_HIPCHK(hipGetLastError());
-    ctx->pend_dsc.n = n; ctx->pend_dsc.args = args;
-    if ((rc = mskf_batch_arm(ctx, ctx->pend_dsc)) != MSKF_OK) return rc;
-    drain.armed = false;
-    return MSKF_OK;
-}
-
-// Wait for the batch started by mskf_fe_describe_batch_begin and copy its results into the args given there.  No-op when nothing
-// is pending.
-extern "C" int mskf_fe_describe_batch_end(mskf_ctx *ctx) {
-    if (!ctx) return MSKF_ERR_INVALID;
-    mskf_ctx::PendingDescribe &D = ctx->pend_dsc;
-    if (!D.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    if (const int rc = mskf_batch_finish(ctx, D)) return rc;
-    for (int i = 0; i < D.n; ++i) {
-        const mskf_fe_describe_args &a = D.args[i];
-        const size_t np = (size_t)a.n;
-        if (!np) continue;
-        const char *src = ctx->dsc_out.h + D.out_off[i];
-        std::memcpy(a.desc, src, FB_BYTES * np);
-        std::memcpy(a.valid, src + FB_BYTES * np, np);
-    }
-    return MSKF_OK;
-}
-
-extern "C" int mskf_fe_describe_batch(mskf_ctx *ctx, int n, mskf_stream *const *streams, mskf_fe_describe_args *args) {
-    const int rc = mskf_fe_describe_batch_begin(ctx, n, streams, args);
-    return rc != MSKF_OK ? rc : mskf_fe_describe_batch_end(ctx);
-}
-
-extern "C" int mskf_fe_describe(mskf_stream *s, mskf_fe_describe_args *args) {
-    if (!s || !args) return refuse_describe("null argument");
-    mskf_stream *ss[1] = {s};
-    return mskf_fe_describe_batch(s->ctx, 1, ss, args);
-}
-
-// ------------------------------------------------------------------------------------------ descriptor matching (fe_match.h)
-static int refuse_match(const char *why) { mskf_set_error(std::string("match: ") + why); return MSKF_ERR_INVALID; }
-
-static inline size_t match_block(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
-
-// The distinct host arrays of a match batch, by (pointer, bytes), and where the one copy of each lies in mch_in.
-struct MatchSets {
-    std::map<std::pair<const uint8_t *, size_t>, size_t> off;
-    size_t bytes = 0;
-    size_t place(const uint8_t *p, size_t n) {
-        const auto it = off.find({p, n});
-        if (it != off.end()) return it->second;
-        const size_t o = bytes;
-        off[{p, n}] = o;
-        bytes += match_block(n);
-        return o;
-    }
-};
-
-extern "C" int mskf_fe_match_batch_begin(mskf_ctx *ctx, int n, mskf_fe_match_args *args) {
-    // ---- plan: every refusal comes from here, before anything is touched
-    if (!ctx || !args) return refuse_match("null argument");
-    if (n <= 0) return refuse_match("a batch has at least one job");
-    if (ctx->pend_mch.active) return refuse_match("a match batch of this context is still pending (call mskf_fe_match_batch_end)");
-    int max_nq = 0, max_nt = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_match_args &a = args[i];
-        if (a.nq < 0 || a.nt < 0) return refuse_match("negative descriptor count");
-        if (a.nq > FM_MAX_N || a.nt > FM_MAX_N) return refuse_match("more than 65535 descriptors in a set");
-        if (a.nq > 0 && !a.query) return refuse_match("null query with nq > 0");
-        if (a.nt > 0 && !a.train) return refuse_match("null train with nt > 0");
-        if (a.nq > 0 && !a.matches) return refuse_match("null matches with nq > 0");
-        if (a.max_distance < 0 || a.max_distance > FM_MAX_DISTANCE) return refuse_match("max_distance must be 0 .. 256");
-        if (!(a.ratio >= 0.f && a.ratio <= 1.f)) return refuse_match("ratio must be 0 (off) or in (0, 1]");
-        max_nq = std::max(max_nq, a.nq);
-        max_nt = std::max(max_nt, a.nt);
-    }
-    if (max_nq <= 0) {                     // nothing to match: no batch pending, _end is a no-op
-        for (int i = 0; i < n; ++i) args[i].n_matches = 0;
-        return MSKF_OK;
-    }
-    MatchSets sets;
-    std::vector<size_t> &out_off = ctx->pend_mch.out_off;      // (no batch is pending: nobody reads it)
-    out_off.resize(n);
-    size_t out_bytes = 0;
-    struct Placed { size_t q, qv, t, tv; };
-    std::vector<Placed> placed(n);
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_match_args &a = args[i];
-        out_off[i] = out_bytes;
-        if (a.nq <= 0) continue;
-        placed[i].q = sets.place(a.query, (size_t)FM_BYTES * a.nq);
-        placed[i].qv = a.query_valid ? sets.place(a.query_valid, (size_t)a.nq) : 0;
-        placed[i].t = a.nt > 0 ? sets.place(a.train, (size_t)FM_BYTES * a.nt) : 0;
-        placed[i].tv = a.nt > 0 && a.train_valid ? sets.place(a.train_valid, (size_t)a.nt) : 0;
-        out_bytes += match_block(sizeof(mskf_match) * (size_t)a.nq);
-    }
-    // ---- grow
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ctx->mch_jobs.ensure(n)) != MSKF_OK || (rc = ctx->mch_in.ensure(sets.bytes)) != MSKF_OK || (rc = ctx->mch_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    for (const auto &s : sets.off) std::memcpy(ctx->mch_in.h + s.second, s.first.first, s.first.second);      // each distinct array once
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_match_args &a = args[i];
-        FeMatchDev &j = ctx->mch_jobs.h[i];
-        std::memset(&j, 0, sizeof(j));
-        if (a.nq <= 0) continue;           // (nq = 0: the launch skips it)
-        const uint8_t *base = (const uint8_t *)ctx->mch_in.d;
-        j.query = base + placed[i].q;
-        j.query_valid = a.query_valid ? base + placed[i].qv : nullptr;
-        j.train = a.nt > 0 ? base + placed[i].t : nullptr;
-        j.train_valid = a.nt > 0 && a.train_valid ? base + placed[i].tv : nullptr;
-        j.nq = a.nq; j.nt = a.nt;
-        j.max_distance = a.max_distance; j.ratio = a.ratio; j.cross_check = a.cross_check != 0;
-        j.matches = (mskf_match *)(ctx->mch_out.d + out_off[i]);
-    }
-    // ---- enqueue: one copy in, one launch, one copy out
-    DrainOnError drain{ctx->stream, true};
-    const MskfCopy cp[2] = {{ctx->mch_in.d, ctx->mch_in.h, sets.bytes}, {ctx->mch_jobs.d, ctx->mch_jobs.h, sizeof(FeMatchDev) * (size_t)n}};
-    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
-    fe_launch_match(ctx->mch_jobs.d, n, max_nq, max_nt, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
-    { const MskfCopy out = {ctx->mch_out.h, ctx->mch_out.d, out_bytes}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
-    MSKF_HIPCHK(hipGetLastError());
-    ctx->pend_mch.n = n; ctx->pend_mch.args = args;
-    if ((rc = mskf_batch_arm(ctx, ctx->pend_mch)) != MSKF_OK) return rc;
-    drain.armed = false;
-    return MSKF_OK;
-}
-
-// Wait for the batch started by mskf_fe_match_batch_begin and copy its results into the args given there.  No-op when nothing
-// is pending.
-extern "C" int mskf_fe_match_batch_end(mskf_ctx *ctx) {
-    if (!ctx) return MSKF_ERR_INVALID;
-    mskf_ctx::PendingMatch &M = ctx->pend_mch;
-    if (!M.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    if (const int rc = mskf_batch_finish(ctx, M)) return rc;
-    for (int i = 0; i < M.n; ++i) {
-        mskf_fe_match_args &a = M.args[i];
-        const mskf_match *src = (const mskf_match *)(ctx->mch_out.h + M.out_off[i]);
-        if (a.nq > 0) std::memcpy(a.matches, src, sizeof(mskf_match) * (size_t)a.nq);
-        a.n_matches = a.nq > 0 ? fm_count_matches(src, a.nq) : 0;
-    }
-    return MSKF_OK;
-}
-
-extern "C" int mskf_fe_match_batch(mskf_ctx *ctx, int n, mskf_fe_match_args *args) {
-    const int rc = mskf_fe_match_batch_begin(ctx, n, args);
-    return rc != MSKF_OK ? rc : mskf_fe_match_batch_end(ctx);
-}
-
-extern "C" int mskf_fe_match(mskf_ctx *ctx, mskf_fe_match_args *args) { return mskf_fe_match_batch(ctx, 1, args); }
-
-// ------------------------------------------------------------------------------------------ geometric verification (fe_verify.h)
-static int refuse_verify(const char *why) { mskf_set_error(std::string("verify: ") + why); return MSKF_ERR_INVALID; }
-
-// the job record of args a over `pairs` (host or device side) with n_usable staged pairs
-static FeVerifyDev verify_job(const mskf_fe_verify_args &a, const double *pairs, int n_usable, unsigned long long *keys) {
-    FeVerifyDev j;
-    std::memset(&j, 0, sizeof(j));
-    j.pairs = pairs; j.keys = keys;
-    j.cam = fv_cam(a.T_cam1_cam0);
-    j.seed = a.seed;
-    j.max_error2 = a.max_error * a.max_error; j.min_depth = a.min_depth;
-    j.n = n_usable; j.K = a.n_hypotheses;
-    return j;
-}
-
-static void verify_write(mskf_fe_verify_args &a, const FvResult &r) {
-    a.n_usable = r.n_usable; a.n_inliers = r.n_inliers; a.best = r.best; a.status = r.status;
-    std::memcpy(a.R, r.R, sizeof(a.R)); std::memcpy(a.t, r.t, sizeof(a.t)); std::memcpy(a.info, r.info, sizeof(a.info));
-    a.rms = r.rms;
-}
-
-// Bytes of the verify arenas of a context (device side): 0 until the first verify call that launches.  NOT part of the C ABI
-// (declared in mskf_internal.h only, like the fe_launch_* functions): tests/test_gpu_verify.py reads it.
-extern "C" int fe_mark_slots_used(const mskf_ctx *ctx) {      // completion-mark slots claimed so far (spinning mode); internal, as below
-    int k = 0;
-    while (k < mskf_ctx::kMarkSlots && ctx->flag_slot[k]) ++k;
-    return k;
-}
-extern "C" size_t fe_verify_arena_bytes(const mskf_ctx *ctx) {
-    return ctx->vfy_jobs.cap * sizeof(FeVerifyDev) + ctx->vfy_in.cap * sizeof(double) + ctx->vfy_out.cap * sizeof(unsigned long long);
-}
-
-extern "C" int mskf_fe_verify_batch_begin(mskf_ctx *ctx, int n, mskf_fe_verify_args *args) {
-    // ---- plan: every refusal comes from here, before anything is touched
-    if (!ctx || !args) return refuse_verify("null argument");
-    if (n <= 0) return refuse_verify("a batch has at least one job");
-    if (ctx->pend_vfy.active) return refuse_verify("a verify batch of this context is still pending (call mskf_fe_verify_batch_end)");
-    int max_n = 0, max_K = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_verify_args &a = args[i];
-        if (a.n < 0) return refuse_verify("negative pair count");
-        if (a.n > FV_MAX_N) return refuse_verify("more than 4096 pairs in a job");
-        if (a.n > 0 && !a.query_obs) return refuse_verify("null query_obs with n > 0");
-        if (a.n > 0 && !a.train_obs) return refuse_verify("null train_obs with n > 0");
-        if (a.n_hypotheses < 1 || a.n_hypotheses > FV_MAX_K) return refuse_verify("n_hypotheses must be 1 .. 1024");
-        if (!(a.max_error > 0.0) || !std::isfinite(a.max_error)) return refuse_verify("max_error must be > 0 and finite");
-        if (!(a.min_depth > 0.0) || !(a.min_depth < a.max_depth) || !std::isfinite(a.max_depth)) return refuse_verify("depths must be 0 < min_depth < max_depth, finite");
-        for (int k = 0; k < 12; ++k) if (!std::isfinite(a.T_cam1_cam0[k])) return refuse_verify("T_cam1_cam0 is not finite");
-        max_n = std::max(max_n, a.n);
-        max_K = std::max(max_K, a.n_hypotheses);
-    }
-    // ---- stage (host memory of the call's own): triangulate, compact the usable pairs in order, keep the map back
-    mskf_ctx::PendingVerify &V = ctx->pend_vfy;                // (no batch is pending: nobody reads it)
-    V.in_off.assign(n, 0); V.orig.assign(n, {});
-    std::vector<std::vector<double>> staged(n);
-    size_t in_doubles = 0;
-    int max_usable = 0;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_verify_args &a = args[i];
-        V.in_off[i] = in_doubles;
-        const int nu = fv_stage_host(fv_cam(a.T_cam1_cam0), a.n, a.query_obs, a.train_obs, a.usable, a.min_depth, a.max_depth, staged[i], V.orig[i]);
-        in_doubles += (size_t)FV_PAIR * nu;
-        max_usable = std::max(max_usable, nu);
-    }
-    if (max_usable < 3) {                  // no job can form a hypothesis: no launch, no batch pending, _end is a no-op
-        for (int i = 0; i < n; ++i) {
-            const FeVerifyDev j = verify_job(args[i], staged[i].data(), (int)V.orig[i].size(), nullptr);
-            verify_write(args[i], fv_finish_host(j, V.orig[i].data(), args[i].n, FV_KEY_NONE, args[i].inlier));
-        }
-        return MSKF_OK;
-    }
-    // ---- grow
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ctx->vfy_jobs.ensure(n)) != MSKF_OK || (rc = ctx->vfy_in.ensure(in_doubles)) != MSKF_OK || (rc = ctx->vfy_out.ensure((size_t)FV_MAX_BLOCKS * n)) != MSKF_OK) return rc;
-    for (int i = 0; i < n; ++i) {
-        if (!staged[i].empty()) std::memcpy(ctx->vfy_in.h + V.in_off[i], staged[i].data(), sizeof(double) * staged[i].size());
-        ctx->vfy_jobs.h[i] = verify_job(args[i], ctx->vfy_in.d + V.in_off[i], (int)V.orig[i].size(), ctx->vfy_out.d + (size_t)FV_MAX_BLOCKS * i);
-    }
-    // ---- enqueue: one copy in, one launch, one copy out
-    DrainOnError drain{ctx->stream, true};
-    const MskfCopy cp[2] = {{ctx->vfy_in.d, ctx->vfy_in.h, sizeof(double) * in_doubles}, {ctx->vfy_jobs.d, ctx->vfy_jobs.h, sizeof(FeVerifyDev) * (size_t)n}};
-    if ((rc = mskf_copy_async(ctx, cp, 2)) != MSKF_OK) return rc;
-    fe_launch_verify(ctx->vfy_jobs.d, n, max_K, ctx->stream);      // untimed: there is no MSKF_K_* kind for it
-    { const MskfCopy out = {ctx->vfy_out.h, ctx->vfy_out.d, sizeof(unsigned long long) * FV_MAX_BLOCKS * (size_t)n}; if ((rc = mskf_copy_async(ctx, &out, 1)) != MSKF_OK) return rc; }
-    MSKF_HIPCHK(hipGetLastError());
-    V.n = n; V.args = args;
-    if ((rc = mskf_batch_arm(ctx, V)) != MSKF_OK) return rc;
-    drain.armed = false;
-    return MSKF_OK;
-}
-
-// Wait for the batch started by mskf_fe_verify_batch_begin; merge every job's block keys, re-form the winner, mark its inliers
-// and refine it (all with fe_verify.h, on the staged pairs still in vfy_in's host side).  No-op when nothing is pending.
-extern "C" int mskf_fe_verify_batch_end(mskf_ctx *ctx) {
-    if (!ctx) return MSKF_ERR_INVALID;
-    mskf_ctx::PendingVerify &V = ctx->pend_vfy;
-    if (!V.active) return MSKF_OK;
-    MSKF_HIPCHK(hipSetDevice(ctx->device));
-    if (const int rc = mskf_batch_finish(ctx, V)) return rc;
-    for (int i = 0; i < V.n; ++i) {
-        mskf_fe_verify_args &a = V.args[i];
-        const FeVerifyDev j = verify_job(a, ctx->vfy_in.h + V.in_off[i], (int)V.orig[i].size(), nullptr);
-        unsigned long long key = FV_KEY_NONE;
-        const int blocks = (a.n_hypotheses + FV_HYP_BLOCK - 1) / FV_HYP_BLOCK;
-        for (int b = 0; b < blocks; ++b) key = fv_merge(key, ctx->vfy_out.h[(size_t)FV_MAX_BLOCKS * i + b]);
-        verify_write(a, fv_finish_host(j, V.orig[i].data(), a.n, key, a.inlier));
-    }
-    return MSKF_OK;
-}
-
-extern "C" int mskf_fe_verify_batch(mskf_ctx *ctx, int n, mskf_fe_verify_args *args) {
-    const int rc = mskf_fe_verify_batch_begin(ctx, n, args);
-    return rc != MSKF_OK ? rc : mskf_fe_verify_batch_end(ctx);
-}
-
-extern "C" int mskf_fe_verify(mskf_ctx *ctx, mskf_fe_verify_args *args) { return mskf_fe_verify_batch(ctx, 1, args); }

@@ -1,4 +1,5 @@
-// mskf_internal.h — private definitions of the C-ABI handles (mskf_ctx / mskf_stream).
+// mskf_internal.h — private definitions of the C-ABI handles (mskf_ctx / mskf_stream) and what its files share: mskf_capi_ctx.cpp (contexts,
+// marks, waits, staging copies, timing, streams), _fe.cpp (settings, push, track, device frame), _kf.cpp (describe, match, verify), _ekf.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -52,6 +53,8 @@ void mskf_set_error(const std::string &s);
         }                                                                                            \
     } while (0)
 
+static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) & ~(a - 1); }      // a: a power of two
+
 template <typename T>
 struct PinnedDev {  // a pinned host array with a device twin
     T *h = nullptr, *d = nullptr;
@@ -102,9 +105,10 @@ struct PinnedDev {  // a pinned host array with a device twin
 
 // A batch between its _begin and its _end (one of each kind per context).  Each kind keeps its own fields around it.
 //   mskf_batch_arm:    record the completion mark behind everything the _begin enqueued, then set `active`.
-//   mskf_batch_finish: wait for the mark; `active` is cleared only once the wait succeeded.  A failed _end (timeout, stream
-//                      error) leaves the batch pending, since its kernels may still be using the arenas it owns: _end may
-//                      be called again, a _begin that needs those arenas is refused, mskf_ctx_destroy drains the stream.
+//   mskf_batch_finish: make the context's device current and wait for the mark; `active` is cleared only once the wait
+//                      succeeded.  A failed _end (timeout, stream error) leaves the batch pending, since its kernels may still be
+//                      using the arenas it owns: _end may be called again, a _begin that needs those arenas is refused,
+//                      mskf_ctx_destroy drains the stream.
 //                      Timing is collected by the caller (the LK units are known only from the unpacked results).
 // A _begin that fails after it has enqueued anything (copy, memset, stream-ordered allocation, launch) synchronises the
 // context's stream before it returns the error (DrainOnError): no staged work outlives it, and nothing is left pending.
@@ -115,15 +119,24 @@ struct PendingBatch {
 int mskf_batch_arm(mskf_ctx *c, PendingBatch &b);
 int mskf_batch_finish(mskf_ctx *c, PendingBatch &b);
 
-// Which pending batch owns which arenas of the context:
-//   a pending track or frame batch owns the front-end arenas (desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out);
-//   a pending describe batch owns dsc_jobs, dsc_in and dsc_out, which nothing else touches: only a describe call refuses for it;
-//   a pending match batch owns mch_jobs, mch_in and mch_out, which nothing else touches: only a match call refuses for it (it
-//   reads no image and no stream, so pushes, frames, describe batches and updates may run between its _begin and its _end);
-//   a pending verify batch owns vfy_jobs, vfy_in and vfy_out in the same way: only a verify call refuses for it;
-//   a pending update (a feature update or a direct update: one slot for both kinds) owns ekf_desc, upd_in and upd_out;
-//   a pending read-out (position variances or odometry covariance: one slot for both kinds) owns pred_arena (its kernel reads
-//   descriptors from and writes results into the host side).
+// A batch that stages through arenas of its own: one job array, one input block and one result block, empty until the first
+// call that launches, written by its _begin and read by its _end only (mskf_enqueue_staged below).
+template <typename Job, typename In, typename Out>
+struct StagedBatch : PendingBatch {
+    PinnedDev<Job> jobs;
+    PinnedDev<In> in;
+    PinnedDev<Out> out;
+    int n = 0;
+    void release() { jobs.release(); in.release(); out.release(); }      // (the mark's event goes with the other kinds': mskf_ctx_destroy)
+};
+
+// Which pending batch owns which arenas of the context (mskf_ctx::pending lists the records):
+//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
+//   pend_upd               ekf_desc, upd_in, upd_out (a feature update or a direct update: one record for both kinds);
+//   pend_ro                pred_arena, whose host side its kernel reads and writes (position variances or odometry covariance: one record);
+//   pend_dsc, pend_mch,    the jobs / in / out arenas inside the record itself (StagedBatch), which nothing else touches: only a call
+//   pend_vfy               of the same kind refuses for it.  A match or verify batch reads no image and no stream, so pushes, frames,
+//                          describe batches and updates may run between its _begin and its _end.
 // Every _begin and every batch call that writes an arena refuses while the owner is pending: MSKF_ERR_INVALID, and the
 // error message names the pending batch.  What each step of such a call may touch:
 //   plan    (plan_push, plan_update, a _begin's own checks): reads the context and the streams, makes no HIP call; every
@@ -181,7 +194,7 @@ struct mskf_ctx {
     hipEvent_t wait_ev = nullptr;     // mark of mskf_wait
     bool wait_block = false;
     volatile unsigned int *flag_h = nullptr;   // pinned host words the mark kernels write (spinning mode), one per mark slot
-    static constexpr int kMarkSlots = 16;      // completion-mark slots: every kind of pending batch and wait_ev claims one at its first use (nine kinds today)
+    static constexpr int kMarkSlots = 16;      // completion-mark slots: every kind of pending batch and wait_ev claims one at its first use (counted below, beside `pending`)
     unsigned int flag_seq[kMarkSlots] = {0};
     hipEvent_t *flag_slot[kMarkSlots] = {nullptr};
     PinnedDev<char> cell_arena;       // per-cell maximum keys of every stream of the last push batch (one D2H copy)
@@ -209,31 +222,29 @@ struct mskf_ctx {
         bool direct = false; struct mskf_ekf_direct_args *dargs = nullptr;
         std::vector<size_t> d_out;             // direct: byte offset of each stream's results in upd_out
     } pend_upd;
-    // descriptors (mskf_fe_describe_batch_*; fe_brief.h): arenas of the call's own, empty until the first call, owned by pend_dsc
-    PinnedDev<FeDescribeDev> dsc_jobs;
-    PinnedDev<char> dsc_in, dsc_out;     // the points / desc + valid of every stream of a describe batch (one copy each way)
-    struct PendingDescribe : PendingBatch {
-        int n = 0; struct mskf_fe_describe_args *args = nullptr;
-        std::vector<size_t> out_off;           // per stream: byte offset of its results in dsc_out
+    // descriptors (mskf_fe_describe_batch_*; fe_brief.h): in = the points, out = desc + valid of every stream
+    struct PendingDescribe : StagedBatch<FeDescribeDev, char, char> {
+        struct mskf_fe_describe_args *args = nullptr;
+        std::vector<size_t> out_off;           // per stream: byte offset of its results in out
     } pend_dsc;
-    // descriptor matching (mskf_fe_match_batch_*; fe_match.h): arenas of the call's own, empty until the first call, owned by pend_mch
-    PinnedDev<FeMatchDev> mch_jobs;
-    PinnedDev<char> mch_in, mch_out;     // every distinct descriptor set and validity array / the matches of every job of a match batch (one copy each way)
-    struct PendingMatch : PendingBatch {
-        int n = 0; struct mskf_fe_match_args *args = nullptr;
-        std::vector<size_t> out_off;           // per job: byte offset of its matches in mch_out
+    // descriptor matching (mskf_fe_match_batch_*; fe_match.h): in = every distinct descriptor set and validity array, out = the matches of every job
+    struct PendingMatch : StagedBatch<FeMatchDev, char, char> {
+        struct mskf_fe_match_args *args = nullptr;
+        std::vector<size_t> out_off;           // per job: byte offset of its matches in out
     } pend_mch;
-    // geometric verification (mskf_fe_verify_batch_*; fe_verify.h): arenas of the call's own, empty until the first call, owned by pend_vfy
-    PinnedDev<FeVerifyDev> vfy_jobs;
-    PinnedDev<double> vfy_in;                      // the staged usable pairs of every job of a verify batch (one copy in)
-    PinnedDev<unsigned long long> vfy_out;         // FV_MAX_BLOCKS keys per job (one copy out)
-    struct PendingVerify : PendingBatch {
-        int n = 0; struct mskf_fe_verify_args *args = nullptr;
-        std::vector<size_t> in_off;            // per job: where its staged pairs start in vfy_in, in doubles
+    // geometric verification (mskf_fe_verify_batch_*; fe_verify.h): in = the staged usable pairs of every job, out = FV_MAX_BLOCKS keys per job
+    struct PendingVerify : StagedBatch<FeVerifyDev, double, unsigned long long> {
+        struct mskf_fe_verify_args *args = nullptr;
+        std::vector<size_t> in_off;            // per job: where its staged pairs start in `in`, in doubles
         std::vector<std::vector<int>> orig;    // per job: the original index of every staged pair
     } pend_vfy;
     // a read-out of `rec` doubles per stream: 3 = position variances, 48 = odometry covariance (mskf_odom_cov)
     struct PendingReadOut : PendingBatch { int n = 0, rec = 0; double *out = nullptr; size_t desc_bytes = 0; } pend_ro;
+    // Every kind of pending batch, once: mskf_ctx_destroy and mskf_ctx_set_wait_mode walk this list, so a new kind is added here
+    // and nowhere else (mskf_refuse_if_owned names the owners it knows in messages of their own).
+    static constexpr int kPendingKinds = 7;
+    PendingBatch *const pending[kPendingKinds] = {&pend_trk, &pend_frame, &pend_upd, &pend_ro, &pend_dsc, &pend_mch, &pend_vfy};
+    static_assert(kPendingKinds + 2 <= kMarkSlots, "every kind of pending batch, wait_ev and cell_ev claim a completion-mark slot each");
 };
 // Completion marks.  mskf_wait_event(c, slot, true) marks the point the context's stream has reached, (.., false) waits
 // for that mark.  Spinning mode (default): the mark is a sequence number written into pinned host memory by a stream
@@ -248,6 +259,22 @@ struct mskf_ctx {
 struct MskfCopy { void *dst; const void *src; size_t bytes; };
 int mskf_copy_async(mskf_ctx *c, const MskfCopy *segs, int n);
 int mskf_wait_event(mskf_ctx *c, hipEvent_t *ev_slot, bool record);
+
+// The enqueue step of a batch whose _begin has planned, grown and packed: the input copies, launch() (the kernels, on c->stream),
+// the result copy, and last the mark.  The order is the protocol: nothing is pending before everything is enqueued, and a failure
+// on the way drains the stream.  What the _end reads of the record (n, args, offsets) the _begin writes before it calls this.
+template <typename Launch>
+int mskf_enqueue_staged(mskf_ctx *c, PendingBatch &b, const MskfCopy *in, int n_in, Launch launch, const MskfCopy &out) {
+    DrainOnError drain{c->stream, true};
+    int rc;
+    if ((rc = mskf_copy_async(c, in, n_in)) != MSKF_OK) return rc;
+    launch();
+    if ((rc = mskf_copy_async(c, &out, 1)) != MSKF_OK) return rc;
+    MSKF_HIPCHK(hipGetLastError());
+    if ((rc = mskf_batch_arm(c, b)) != MSKF_OK) return rc;
+    drain.armed = false;
+    return MSKF_OK;
+}
 
 struct mskf_stream {
     mskf_ctx *ctx = nullptr;
@@ -316,6 +343,10 @@ int mskf_t_begin(mskf_ctx *c, int kind);
 void mskf_t_end(mskf_ctx *c, int slot, long long units);
 void mskf_t_collect(mskf_ctx *c);   // call after the stream has been synchronised
 void mskf_t_set_units(mskf_ctx *c, int slot, int kind, long long units);   // units of a slot begun earlier (bounds- and kind-checked)
+// the pyramid (index into pyr / lvl0 / held) that plays a role: 0 prev cam0, 1 curr cam0, 2 curr cam1
+static inline int pyr_of_role(const mskf_stream *s, int role) { return role == 0 ? s->i_prev0 : (role == 1 ? s->i_curr0 : s->i_curr1); }
+// level 0 of a pyramid: the borrowed device image if there is one, else the stream's own plane
+static inline const uint8_t *level0(const mskf_stream *s, int idx) { return s->lvl0[idx] ? s->lvl0[idx] : s->pyr[idx] + s->lvl_off[0]; }
 void fill_pyr(const mskf_stream *s, int idx, PyrDev &p);
 int mskf_ekf_stream_init(mskf_stream *s);
 void mskf_ekf_stream_free(mskf_stream *s);

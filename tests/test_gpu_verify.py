@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import brief_cases as BC
+import match_cases as MC
 import verify_cases as VC
 import verify_reference as VR
 from msckf_stereo_c_amd import capi
@@ -299,6 +300,47 @@ def test_every_kind_of_batch_on_one_context_then_verify(oracle):
     c = BY_NAME["noisy 48"]
     _same(ctx.verify(**VC.options(c)), reference(c), "the ninth kind")
     assert (before, L.fe_mark_slots_used(ctx.h)) == (8, 9)
+    s.close()
+    ctx.close()
+
+
+def test_wait_mode_is_refused_while_any_kind_is_pending(oracle):
+    """A completion mark recorded in one wait mode cannot be awaited in the other, so mskf_ctx_set_wait_mode refuses between the
+    _begin and the _end of every kind of batch: each of the seven in turn, with the smallest job that launches, on the context and
+    stream of the test above."""
+    ctx = capi.Context(0)
+    L = ctx.L
+    L.mskf_ctx_set_wait_mode.argtypes = [C.c_void_p, C.c_int]
+    assert L.mskf_ctx_set_wait_mode(ctx.h, 0) == 0
+    w, h = 752, 480                                         # (a size at which whole frames run on the device)
+    s = capi.Stream(ctx, oracle.euroc_calib(w, h), default_fe_cfg(), default_ekf_cfg())
+    a, b = BC.image("blocks", w, h, seed=20), BC.image("smooth", w, h, seed=21)
+    s.push_stereo(a, b)
+    ctx.sync()
+    cm = s.cell_maxima()
+    pts = np.stack([cm["x"], cm["y"]], 1)[:20].astype(np.float32)
+    assert len(pts) == 20 and s.grid_capacity() > 0
+
+    def pending(kind, begin, end):
+        begin()
+        assert L.mskf_ctx_set_wait_mode(ctx.h, 1) == -1 and b"pending" in L.mskf_last_error(), kind
+        end()
+        assert L.mskf_ctx_set_wait_mode(ctx.h, 0) == 0, kind
+
+    pending("track", lambda: ctx.track_batch_begin([s], [dict(pts=pts, do_temporal=0)]), ctx.track_batch_end)
+    s.swap()
+    und = (pts - np.float32([w / 2, h / 2])) / np.float32(VC.FX)
+    s.set_grid(id=np.arange(20), lifetime=np.ones(20), cam0=pts, cam1=pts, und0=und, und1=und, next_feature_id=20)
+    pending("device frame", lambda: ctx.frame_batch_begin([s], [(a, b)], [{}]), ctx.frame_batch_end)
+    s.push_stereo(a, b)
+    pending("describe", lambda: ctx.describe_batch_begin([s], [1], [pts]), ctx.describe_batch_end)
+    mc = next(c for c in MC.CASES if c["name"] == "size 1x1")
+    pending("match", lambda: ctx.match_batch_begin([MC.options(mc)]), ctx.match_batch_end)
+    pending("verify", lambda: ctx.verify_batch_begin([VC.options(BY_NAME["size 3x1"])]), ctx.verify_batch_end)
+    H = np.zeros((1, 21))
+    H[0, 12] = 1.0
+    pending("direct update", lambda: ctx.ekf_update_direct_batch_begin([s], [dict(H=H, r=[0.01], R=[[0.25]])]), ctx.ekf_update_direct_batch_end)
+    pending("position-variance read-out", lambda: ctx.ekf_pos_var_batch_begin([s]), ctx.ekf_pos_var_batch_end)
     s.close()
     ctx.close()
 
