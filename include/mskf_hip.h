@@ -48,7 +48,9 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  slot MSKF_K_PT_GEOM left empty (MSKF_K_COUNT is unchanged);
                                  mskf_fe_describe, _batch, _batch_begin, _batch_end (with their own mskf_fe_describe_args), mskf_fe_descriptor_pattern;
                                  mskf_fe_match, _batch, _batch_begin, _batch_end (with their own mskf_fe_match_args and mskf_match);
-                                 mskf_fe_verify, _batch, _batch_begin, _batch_end (with their own mskf_fe_verify_args) */
+                                 mskf_fe_verify, _batch, _batch_begin, _batch_end (with their own mskf_fe_verify_args);
+                                 mskf_fe_set_patch_check, mskf_fe_get_patch_check (with their own mskf_fe_patch_check) and the alias MSKF_K_FE_PATCH of
+                                 the timing slot the mask gate borrowed */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -70,7 +72,7 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
 
 /* Optional per-kernel timing with HIP events recorded on the context's own stream (bench / roofline).
  * `units` are the algorithmic work units of a launch (LK: point tracks, temporal + stereo of one track call in one launch — MSKF_K_PT_GEOM
- * is kept for ABI stability, counts no geometry since that moved into that launch, and carries MSKF_K_FE_MASK instead; pyramid: output pixels;
+ * is kept for ABI stability, counts no geometry since that moved into that launch, and carries the point gates behind a track launch instead (MSKF_K_FE_MASK, MSKF_K_FE_PATCH); pyramid: output pixels;
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
  * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
@@ -82,7 +84,11 @@ enum {
     /* k_mask_points, the point gate of the image masks (mskf_fe_set_mask), launched behind a track launch only when a stream of that batch
        has a mask; units: streams.  It takes the slot of MSKF_K_PT_GEOM, which nothing else fills (see above), so MSKF_K_COUNT and the
        arrays of mskf_ctx_get_timing keep their size. */
-    MSKF_K_FE_MASK = MSKF_K_PT_GEOM
+    MSKF_K_FE_MASK = MSKF_K_PT_GEOM,
+    /* k_patch_points, the point gate of the patch check (mskf_fe_set_patch_check), launched behind a track launch only when a stream of
+       that batch checks; units: streams.  The same slot: it counts the point gates behind a track launch, of either kind, and with both
+       features off its counts are exactly as before. */
+    MSKF_K_FE_PATCH = MSKF_K_PT_GEOM
 };
 int mskf_ctx_set_timing(mskf_ctx *ctx, int enable);
 /* Accounting gate (default on): while it is off, launches are not timed and host seconds not accumulated.  Unlike
@@ -309,6 +315,33 @@ int mskf_fe_set_mask(mskf_stream *s, const mskf_fe_mask *cfg);
 /* The mask of camera `cam` (0 / 1) as the stream holds it, eroded, one byte per pixel (0 masked out, 255 usable), dense;
  * *w = *h = 0 when that camera has none (nothing is written to out, which may then be NULL).  No device call. */
 int mskf_fe_get_mask(mskf_stream *s, int cam, uint8_t *out, int capacity, int *w, int *h, int *margin);
+
+/* ---- opt-in ZNCC patch check of temporal tracks and stereo matches: is it still the same piece of scene?
+ * Off by default, and then nothing new runs or is allocated.  One more launch (k_patch_points, MSKF_K_FE_PATCH) behind every track
+ * launch of a batch that has a checking stream: both track launches of a device frame, and mskf_fe_track*; behind the mask gate where
+ * both are on (the two only remove points, so the result does not depend on the order).  It is a pure function of the track's
+ * outputs and the level-0 images, a pixel rule and a threshold ("Patch check", has the arithmetic, which is exact):
+ * a (2 half + 1)^2 patch of bilinear samples (fractions in 32nds, replicated border) around a point in each of two images, and
+ * their zero-mean normalised cross-correlation against a threshold.
+ *   temporal (mode bit 1; track calls with do_temporal = 1, points with status bit 0): in_pts[pt] in the previous cam0 image against
+ *           out0[pt] in the current one.  A failing point is lost as a track loses one: status 0, out1 = und0 = und1 = 0, out0 kept.
+ *   stereo  (mode bit 2; points with status bit 1 of any track call): out0[pt] in the current cam0 image against out1[pt] in the
+ *           current cam1 image.  A failing point loses bit 1 and nothing else (as behind the epipolar gate).
+ * The temporal comparison runs first; a point lost there is not compared again.  Two flat patches pass (nothing to judge), a flat one
+ * against a textured one fails.  ZNCC ignores gain and offset.  The bookkeeping drops what the status bits say, so the TrackingInfo
+ * counts of a device frame count these losses as tracking and matching losses.  The temporal comparison is frame to frame: it sees
+ * jumps and occlusions, not slow drift (that would need a stored template per feature).
+ * mskf_fe_set_patch_check validates before it touches anything: MSKF_ERR_INVALID for a null cfg, an unknown mode bit, `half` outside
+ * 2 .. 7 with mode != 0, a threshold outside [0, 1] or not finite, and while a track or device-frame batch of the stream's context is
+ * pending (mskf_last_error names it); the previous setting then stays in force.  mode = 0 = off.  A new setting applies from the
+ * stream's next track or frame call.  No device call. */
+enum { MSKF_PATCH_TEMPORAL = 1, MSKF_PATCH_STEREO = 2 };
+typedef struct mskf_fe_patch_check {
+    int32_t mode, half;                        /* mode: MSKF_PATCH_* bits, 0 = off; half: 2 .. 7 */
+    float min_zncc_temporal, min_zncc_stereo;  /* in [0, 1] */
+} mskf_fe_patch_check;
+int mskf_fe_set_patch_check(mskf_stream *s, const mskf_fe_patch_check *cfg);
+int mskf_fe_get_patch_check(mskf_stream *s, mskf_fe_patch_check *out);      /* a stream never set: {0, 4, 0.8, 0.8} */
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);

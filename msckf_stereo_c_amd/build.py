@@ -27,6 +27,7 @@ HIP_SRCS = [
     "hip/fe_describe.hip",
     "hip/fe_match.hip",
     "hip/fe_verify.hip",
+    "hip/fe_patch.hip",
     "abi/mskf_capi_ctx.cpp",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_kf.cpp",

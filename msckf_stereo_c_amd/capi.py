@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, FeVerifyArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
-                           FeInputFormat, FeMask, ImuStep, raw_raster)
+                           FeInputFormat, FeMask, FePatchCheck, ImuStep, PATCH_CHECK_MODES, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -64,7 +64,7 @@ EXPORTS = [
     "mskf_ekf_get_odom_cov", "mskf_ekf_get_odom_cov_batch", "mskf_ekf_get_odom_cov_batch_begin", "mskf_ekf_get_odom_cov_batch_end",
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
-    "mskf_fe_set_mask", "mskf_fe_get_mask",
+    "mskf_fe_set_mask", "mskf_fe_get_mask", "mskf_fe_set_patch_check", "mskf_fe_get_patch_check",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
     "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
     "mskf_fe_verify", "mskf_fe_verify_batch", "mskf_fe_verify_batch_begin", "mskf_fe_verify_batch_end",
@@ -651,6 +651,22 @@ class Stream:
             return None, margin.value
         assert (h.value, w.value) == out.shape
         return out, margin.value
+
+    def set_patch_check(self, mode="both", half=4, min_zncc_temporal=0.8, min_zncc_stereo=0.8):
+        """mskf_fe_set_patch_check: the ZNCC patch check behind every track launch; mode "both" / "temporal" / "stereo" / "off" (or
+        the bits 1 | 2), half 2 .. 7 (a patch is (2 half + 1)^2 samples), thresholds in [0, 1].  From the next track or frame call on."""
+        if isinstance(mode, str) and mode not in PATCH_CHECK_MODES:
+            raise MskfError("unknown patch check mode %r" % (mode,), -1)
+        cfg = FePatchCheck(int(PATCH_CHECK_MODES.get(mode, mode)), int(half), float(min_zncc_temporal), float(min_zncc_stereo))
+        self.L.mskf_fe_set_patch_check.argtypes = [C.c_void_p, C.POINTER(FePatchCheck)]
+        _chk(self.L.mskf_fe_set_patch_check(self.h, C.byref(cfg)))
+
+    def get_patch_check(self):
+        """(mode bits, half, min_zncc_temporal, min_zncc_stereo) as the stream holds them."""
+        cfg = FePatchCheck()
+        self.L.mskf_fe_get_patch_check.argtypes = [C.c_void_p, C.POINTER(FePatchCheck)]
+        _chk(self.L.mskf_fe_get_patch_check(self.h, C.byref(cfg)))
+        return cfg.mode, cfg.half, cfg.min_zncc_temporal, cfg.min_zncc_stereo
 
     def describe(self, role, pts):
         """mskf_fe_describe: the 256-bit descriptors of pts (n x 2, level-0 pixels) on the image `role` (0 prev cam0, 1 curr cam0,

@@ -214,6 +214,52 @@ static void mask_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max
     mskf_t_end(ctx, ts, n);
 }
 
+// ---- opt-in ZNCC patch check of tracks and stereo matches (include/mskf_hip.h; arithmetic and the gate: fe_patch.h)
+static int patch_validate(const mskf_stream *s, const mskf_fe_patch_check *cfg) {
+    if (!s) return MSKF_ERR_INVALID;
+    if (!cfg) { mskf_set_error("patch check: null configuration"); return MSKF_ERR_INVALID; }
+    if (cfg->mode & ~(FP_TEMPORAL | FP_STEREO)) { mskf_set_error("patch check: unknown mode bit (1 temporal, 2 stereo)"); return MSKF_ERR_INVALID; }
+    if (cfg->mode != 0 && (cfg->half < FP_MIN_HALF || cfg->half > FP_MAX_HALF)) { mskf_set_error("patch check: half must be 2 .. 7"); return MSKF_ERR_INVALID; }
+    for (const float t : {cfg->min_zncc_temporal, cfg->min_zncc_stereo})
+        if (!std::isfinite(t) || t < 0.f || t > 1.f) { mskf_set_error("patch check: a threshold must lie in [0, 1]"); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_patch_check(mskf_stream *s, const mskf_fe_patch_check *cfg) {
+    if (const int rc = patch_validate(s, cfg)) return rc;
+    s->patch = *cfg;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_patch_check(mskf_stream *s, mskf_fe_patch_check *out) {
+    if (!s || !out) return MSKF_ERR_INVALID;
+    *out = s->patch;
+    return MSKF_OK;
+}
+
+// The patch checks of the streams of a track launch, element for element beside its descriptors: 0 when no stream checks and
+// nothing was touched, else the array is staged in patch_desc and *cp is its copy.
+static int stage_patch(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) *any = *any || streams[i]->patch.mode != 0;
+    if (!*any) return MSKF_OK;
+    PinnedDev<FePatchDev> &A = ctx->patch_desc;
+    if (const int rc = A.ensure(n)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_patch_check &c = streams[i]->patch;
+        A.h[i] = FePatchDev{fp_thr2(c.min_zncc_temporal), fp_thr2(c.min_zncc_stereo), c.half, c.mode};
+    }
+    *cp = MskfCopy{A.d, A.h, sizeof(FePatchDev) * (size_t)n};
+    return MSKF_OK;
+}
+
+// The patch gate behind a track launch over `desc_dev` (the checks staged in patch_desc), timed as MSKF_K_FE_PATCH.
+static void patch_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
+    const int ts = mskf_t_begin(ctx, MSKF_K_FE_PATCH);
+    fe_launch_patch_points(desc_dev, ctx->patch_desc.d, n, max_pts, ctx->stream);
+    mskf_t_end(ctx, ts, n);
+}
+
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
 // 16-bit pixels on 2-byte boundaries.
 static int px_check_images(const mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, long long pitch) {
@@ -540,6 +586,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy mask_cp{};
     bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind the track
     if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
+    MskfCopy patch_cp{};
+    bool checked = false;                   // ... or a patch check: its gate runs behind the track and the mask gate
+    if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -555,15 +604,19 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    const MskfCopy cp[3] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, mask_cp};
+    MskfCopy cp[4] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
+    int n_cp = 2;
+    if (masked) cp[n_cp++] = mask_cp;
+    if (checked) cp[n_cp++] = patch_cp;
     mskf_ctx::PendingTrack &T = ctx->pend_trk;
     T.n = n; T.args = args;
-    rc = mskf_enqueue_staged(ctx, T, cp, masked ? 3 : 2, [&] {
+    rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] {
         // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
         T.ts = mskf_t_begin(ctx, MSKF_K_LK);
         fe_launch_track(ctx->desc[1].d, n, max_pts, st);
         mskf_t_end(ctx, T.ts, 0);
         if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
+        if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_pts);
     }, MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
     if (rc != MSKF_OK) return rc;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
@@ -705,6 +758,9 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy mask_cp{};
     bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind both track launches
     if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
+    MskfCopy patch_cp{};
+    bool checked = false;                   // ... or a patch check: its gate runs behind both track launches, and the mask gate
+    if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -735,14 +791,18 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         B.x_info = x.info; B.x_id = x.id; B.x_lifetime = x.lifetime; B.x_cam0 = x.cam0; B.x_cam1 = x.cam1; B.x_und0 = x.und0; B.x_und1 = x.und1;
     }
     {
-        const MskfCopy cp[4] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
-                                {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}, mask_cp};
-        if ((rc = mskf_copy_async(ctx, cp, masked ? 4 : 3)) != MSKF_OK) return rc;
+        MskfCopy cp[5] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
+                          {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}};
+        int n_cp = 3;
+        if (masked) cp[n_cp++] = mask_cp;
+        if (checked) cp[n_cp++] = patch_cp;
+        if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
     }
     const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
     fe_launch_track(ctx->desc[1].d, n, max_prev, st);
     mskf_t_end(ctx, ts1, 0);
     if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
+    if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_prev);
     int tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
@@ -750,6 +810,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     fe_launch_track(ctx->desc[2].d, n, std::max(max_cand_est, 4), st);
     mskf_t_end(ctx, ts2, 0);
     if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
+    if (checked) patch_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 1, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);

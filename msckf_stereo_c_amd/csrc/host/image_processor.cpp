@@ -105,6 +105,27 @@ int ImageProcessor::setEqualize(const mskf_fe_equalize &cfg) {
     return rc;
 }
 
+mskf_fe_patch_check patch_check_from_yaml(const YAML::Node &y) {
+    mskf_fe_patch_check c{0, 4, 0.8f, 0.8f};
+    if (y["patch_check"].IsDefined()) {
+        const std::string m = y["patch_check"].as<std::string>();
+        if (m == "off") c.mode = 0; else if (m == "temporal") c.mode = 1; else if (m == "stereo") c.mode = 2; else if (m == "both") c.mode = 3;
+        else throw YAML::Exception("yaml: patch_check must be off, temporal, stereo or both, not " + m);
+    }
+    if (y["patch_check_half"].IsDefined()) c.half = y["patch_check_half"].as<int>();
+    if (y["patch_check_min_zncc_temporal"].IsDefined()) c.min_zncc_temporal = (float)y["patch_check_min_zncc_temporal"].as<double>();
+    if (y["patch_check_min_zncc_stereo"].IsDefined()) c.min_zncc_stereo = (float)y["patch_check_min_zncc_stereo"].as<double>();
+    return c;
+}
+
+int ImageProcessor::setPatchCheck(const mskf_fe_patch_check &cfg) {
+    if (!initialized_ || !stream_) { patch_cfg_ = cfg; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
+    const int rc = mskf_fe_set_patch_check(stream_, &cfg);
+    if (rc != MSKF_OK) { fail("mskf_fe_set_patch_check", rc); return rc; }   // refused: patchCheck() keeps reporting what the stream holds
+    patch_cfg_ = cfg;
+    return rc;
+}
+
 MaskFiles mask_files_from_yaml(const YAML::Node &y) {
     MaskFiles m;
     if (y["mask_cam0"].IsDefined()) m.cam0 = y["mask_cam0"].as<std::string>();
@@ -229,7 +250,8 @@ bool ImageProcessor::loadParameters() {
         cfg_ = fe_cfg_from_yaml(cfg_imgproc);
         eq_cfg_ = equalize_from_yaml(cfg_imgproc);
         px_cfg_ = input_format_from_yaml(cfg_imgproc);
-        descriptors_ = descriptors_from_yaml(cfg_imgproc);
+        patch_cfg_ = patch_check_from_yaml(cfg_imgproc);
+        descriptors_ =descriptors_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
     processor_config.grid_col = cfg_.grid_col;
@@ -265,6 +287,8 @@ bool ImageProcessor::initialize() {
     if (stream_ && (px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return false;
     // ... and the opt-in image masks, likewise
     if (stream_ && applyKeptMask() != MSKF_OK) return false;
+    // ... and the opt-in patch check, likewise
+    if (stream_ && patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
     return true;
 }
 
@@ -309,6 +333,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return;
         if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return;
         if (applyKeptMask() != MSKF_OK) return;
+        if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
     if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {

@@ -33,6 +33,10 @@ const char *input_format_name(int format);      // nullptr: no such format
 // paths are used as given; whoever has an image reader (the app) loads the files and hands the planes to ImageProcessor::setMask.
 struct MaskFiles { std::string cam0, cam1; int margin = 0; bool any() const { return !cam0.empty() || !cam1.empty(); } };
 MaskFiles mask_files_from_yaml(const YAML::Node &cfg_imgproc);
+// ... and the ZNCC patch check of tracks and stereo matches: patch_check: off | temporal | stereo | both, patch_check_half: 2 .. 7,
+// patch_check_min_zncc_temporal, patch_check_min_zncc_stereo: 0 .. 1 (mskf_fe_set_patch_check; absent = off, 4, 0.8, 0.8).  Throws
+// YAML::Exception on an unknown patch_check value.
+mskf_fe_patch_check patch_check_from_yaml(const YAML::Node &cfg_imgproc);
 // ... and descriptors: off | brief256 (absent = off): 256-bit binary descriptors of the published features (mskf_fe_describe_batch),
 // with descriptors_out: <file> for their text output (which turns them on).  Throws YAML::Exception on an unknown value.
 bool descriptors_from_yaml(const YAML::Node &cfg_imgproc);
@@ -116,6 +120,10 @@ class ImageProcessor {
     int setMask(const uint8_t *cam0, const uint8_t *cam1, int width, int height, int pitch, int margin);
     // the eroded mask of a camera as the stream holds it (0 / 255 per pixel, dense); false = none.  After the stream exists.
     bool mask(int cam, std::vector<uint8_t> &out, int &width, int &height, int &margin) const;
+    // opt-in ZNCC patch check of temporal tracks and stereo matches (mskf_fe_set_patch_check): kept and set like setEqualize; a
+    // refusal leaves the previous setting in force.  mode 0 = off.
+    int setPatchCheck(const mskf_fe_patch_check &cfg);
+    const mskf_fe_patch_check &patchCheck() const { return patch_cfg_; }
     // opt-in 256-bit descriptors (mskf_fe_describe_batch; DESIGN.md section 3, "Descriptors") of the features a frame publishes:
     // frame k's cam0 level 0 at the cam0 pixels of the features of frame k's message, in message order.  Off by default; takes
     // effect with the next frame.  descriptorIds() / descriptors() (32 bytes each) / descriptorValid() are those of the last frame.
@@ -219,6 +227,7 @@ class ImageProcessor {
     bool have_yaml_ = false;
     mskf_fe_equalize eq_cfg_{0, 8, 8, 0, 40.0};
     mskf_fe_input_format px_cfg_{0, 0};
+    mskf_fe_patch_check patch_cfg_{0, 4, 0.8f, 0.8f};
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
     int applyKeptMask();
     bool descriptors_ = false;

@@ -107,6 +107,15 @@ assert C.sizeof(FeMask) == 32
 MASK_MAX_MARGIN = 64         # FM_MAX_MARGIN (csrc/hip/fe_mask.h)
 
 
+class FePatchCheck(C.Structure):
+    """mskf_fe_patch_check (include/mskf_hip.h): the ZNCC patch check of temporal tracks (mode bit 1) and stereo matches (bit 2)."""
+    _fields_ = [("mode", C.c_int32), ("half", C.c_int32), ("min_zncc_temporal", C.c_float), ("min_zncc_stereo", C.c_float)]
+
+
+assert C.sizeof(FePatchCheck) == 16
+PATCH_CHECK_MODES = {"off": 0, "temporal": 1, "stereo": 2, "both": 3}
+
+
 class FeDescribeArgs(C.Structure):
     """mskf_fe_describe_args (include/mskf_hip.h): n points of the image of `role` in, 32 n descriptor bytes and n validity bytes out."""
     _fields_ = [("role", C.c_int32), ("n", C.c_int32), ("pts", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p)]

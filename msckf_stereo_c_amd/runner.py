@@ -9,7 +9,7 @@ import numpy as np
 
 from .capi import MskfError
 from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat, FeMask,
-                           ImuSample, TrackingInfo, raw_raster)
+                           FePatchCheck, ImuSample, PATCH_CHECK_MODES, TrackingInfo, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -250,6 +250,19 @@ class Runner:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
 
+    def set_patch_check(self, mode="both", half=4, min_zncc_temporal=0.8, min_zncc_stereo=0.8, stream=None):
+        """Opt-in ZNCC patch check of one stream or of all (mskf_fe_set_patch_check): tracked points whose patch no longer
+        correlates with the previous frame's ("temporal") and stereo matches whose patches do not correlate ("stereo") are dropped
+        behind every track launch.  mode "both" / "temporal" / "stereo" / "off"; half 2 .. 7; thresholds in [0, 1].  Call between runs."""
+        if isinstance(mode, str) and mode not in PATCH_CHECK_MODES:
+            raise MskfError("unknown patch check mode %r" % (mode,), -1)
+        cfg = FePatchCheck(int(PATCH_CHECK_MODES.get(mode, mode)), int(half), float(min_zncc_temporal), float(min_zncc_stereo))
+        self.L.mskfh_runner_set_patch_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(FePatchCheck)]
+        rc = self.L.mskfh_runner_set_patch_check(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
     def set_descriptors(self, on, stream=None):
         """Opt-in 256-bit binary descriptors (upright BRIEF) of the features every frame publishes, of one stream
         or of all: one more batched device call per frame of a group with a describing stream.  Off by default; call between runs."""
@@ -443,7 +456,8 @@ class Runner:
     def get_timing(self, reset=True):
         """Per-kernel HIP-event timing accumulated on the groups' own streams: {kernel: (ms, launches, units)}.  The key
         "k_ekf_augment" carries the launches of k_ekf_direct_update (fused measurements, zero-velocity updates; units: streams with
-        rows) and nothing else: the augmentation itself runs inside k_ekf_propagate, and the slot keeps its name for the ABI."""
+        rows) and nothing else: the augmentation itself runs inside k_ekf_propagate, and the slot keeps its name for the ABI.
+        Likewise "k_pt_geom" carries the point gates behind a track launch (k_mask_points, k_patch_points; units: streams)."""
         k = len(self.KERNELS)
         ms = np.zeros(k)
         launches = np.zeros(k, np.int64)
