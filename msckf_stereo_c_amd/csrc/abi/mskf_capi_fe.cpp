@@ -30,6 +30,14 @@ static void fill_fe_desc(const mskf_stream *s, FeStreamDev &d) {
     d.cell_keys = (unsigned long long *)(s->ctx->cell_arena.d + s->cell_off);
 }
 
+// The descriptor of the stream's current pair as every launch of this file stages it: pyramids, camera models, R01, E, epi_thresh
+// and the detector's cells; Hpred and the point fields are zero (the caller's).  No HIP call, no state changed.
+extern "C" int fe_stream_desc(const mskf_stream *s, FeStreamDev *out) {
+    if (!s || !out || !s->has_curr) return MSKF_ERR_INVALID;
+    fill_fe_desc(s, *out);
+    return MSKF_OK;
+}
+
 // The push generation as the 8-bit tag the cell keys carry in their top byte (1 .. 255; 0 is "never written").
 static inline unsigned int push_gen_tag(unsigned long long push_gen) { return (unsigned int)((push_gen - 1) % 255ULL) + 1U; }
 static inline size_t cell_key_bytes(const mskf_stream *s) { return sizeof(unsigned long long) * (size_t)s->fe.det_rows * s->fe.det_cols; }

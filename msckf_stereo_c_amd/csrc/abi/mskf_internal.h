@@ -40,6 +40,7 @@ void fe_launch_match(const FeMatchDev *jobs_dev, int n_jobs, int max_nq, int max
 void fe_launch_verify(const FeVerifyDev *jobs_dev, int n_jobs, int max_K, hipStream_t st);
 extern "C" int fe_mark_slots_used(const struct mskf_ctx *ctx);               // internal, for the tests: not in include/mskf_hip.h
 extern "C" size_t fe_verify_arena_bytes(const struct mskf_ctx *ctx);      // internal, for the tests: not in include/mskf_hip.h
+extern "C" int fe_stream_desc(const struct mskf_stream *s, FeStreamDev *out);   // internal, for the tests: not in include/mskf_hip.h
 void fe_launch_book(const FeBookDev *books_dev, int n_streams, int which, size_t scratch_bytes, hipStream_t st);
 void fe_launch_equalize(const EqJob *jobs_dev, int n_jobs, int max_units, int any_global, int max_regions, int splits, hipStream_t st);
 void fe_launch_px_convert(const PxJob *jobs_dev, int n_jobs, int max_w, int max_h, hipStream_t st);

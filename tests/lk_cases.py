@@ -318,6 +318,49 @@ def sizes_cases(w, h, seed=4):
 CASE_SETS = dict(saturated=saturated_cases, displaced=displaced_cases, border=border_cases, sizes=sizes_cases)
 
 
+# ---------------------------------------------------------------------------------------------- a track result against the oracle
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def check_track(got, oracle, calib, fe, c, do_temporal, tag):
+    """One track result (out0, out1, und0, und1, status of the points of case c) against the oracle: LK, then the bounds gate,
+    then oracle.stereo_match and oracle.undistort; survivors bit-exact in every output, the rest zero.  Returns the numbers of
+    tracked points and of stereo inliers."""
+    h, w = c["B"].shape
+    pts = c["pts"]
+    n = len(pts)
+    K0, D0 = np.array(calib.cam0_intrinsics), np.array(calib.cam0_distortion)
+    K1, D1 = np.array(calib.cam1_intrinsics), np.array(calib.cam1_distortion)
+    if do_temporal:
+        ref_b, ref_st = oracle.lk_track(c["A"], c["B"], pts, hpred_guess(c["H"], pts))
+        ok = ref_st.astype(bool)
+        ok &= ~((ref_b[:, 1] < 0) | (ref_b[:, 1] > h - 1) | (ref_b[:, 0] < 0) | (ref_b[:, 0] > w - 1))
+    else:
+        ref_b, ok = pts, np.ones(n, bool)
+    assert np.array_equal((got["status"] & 1).astype(bool), ok), tag
+    assert same(got["out0"][ok], ref_b[ok]), tag
+    # a point that fails the temporal half: status 0 and out1 = und0 = und1 = 0 (include/mskf_hip.h)
+    lost = ~ok
+    assert (got["status"][lost] == 0).all(), tag
+    for k in ("out1", "und0", "und1"):
+        assert (bits(got[k][lost]) == 0).all(), (tag, k)
+    n_in = 0
+    if ok.any():
+        tracked = np.ascontiguousarray(ref_b[ok])
+        ref_c1, ref_in = oracle.stereo_match(calib, fe, c["B"], c["B1"], tracked)
+        assert np.array_equal((got["status"][ok] >> 1) & 1, ref_in), tag
+        assert same(got["out1"][ok], ref_c1), tag
+        assert same(got["und0"][ok], oracle.undistort(K0, D0, tracked, model=calib.cam0_model)), tag
+        assert same(got["und1"][ok], oracle.undistort(K1, D1, ref_c1, model=calib.cam1_model)), tag
+        n_in = int(ref_in.sum())
+    return int(ok.sum()), n_in
+
+
 # ---------------------------------------------------------------------------------------------- what the trace says
 def in_image(pts, w, h):
     return (pts[:, 0] >= 0) & (pts[:, 0] <= w - 1) & (pts[:, 1] >= 0) & (pts[:, 1] <= h - 1)

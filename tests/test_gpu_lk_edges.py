@@ -17,12 +17,7 @@ SIZE_IDS = ["%dx%d" % s for s in C.SIZES]
 FIELDS = ("out0", "out1", "und0", "und1", "status")
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32) if a.dtype == np.float32 else a
-
-
-def _same(a, b):
-    return np.array_equal(_bits(a), _bits(b))
+_bits, _same, _check = C.bits, C.same, C.check_track        # shared with tests/test_gpu_frame_counts.py
 
 
 def _load(s, c):
@@ -30,38 +25,6 @@ def _load(s, c):
     s.push_stereo(c["A"], c["A"])
     s.swap()
     s.push_stereo(c["B"], c["B1"])
-
-
-def _check(got, oracle, calib, fe, c, do_temporal, tag):
-    """One track result against the oracle: survivors bit-exact in every output, the rest zero."""
-    h, w = c["B"].shape
-    pts = c["pts"]
-    n = len(pts)
-    K0, D0 = np.array(calib.cam0_intrinsics), np.array(calib.cam0_distortion)
-    K1, D1 = np.array(calib.cam1_intrinsics), np.array(calib.cam1_distortion)
-    if do_temporal:
-        ref_b, ref_st = oracle.lk_track(c["A"], c["B"], pts, C.hpred_guess(c["H"], pts))
-        ok = ref_st.astype(bool)
-        ok &= ~((ref_b[:, 1] < 0) | (ref_b[:, 1] > h - 1) | (ref_b[:, 0] < 0) | (ref_b[:, 0] > w - 1))
-    else:
-        ref_b, ok = pts, np.ones(n, bool)
-    assert np.array_equal((got["status"] & 1).astype(bool), ok), tag
-    assert _same(got["out0"][ok], ref_b[ok]), tag
-    # a point that fails the temporal half: status 0 and out1 = und0 = und1 = 0 (include/mskf_hip.h)
-    lost = ~ok
-    assert (got["status"][lost] == 0).all(), tag
-    for k in ("out1", "und0", "und1"):
-        assert (_bits(got[k][lost]) == 0).all(), (tag, k)
-    n_in = 0
-    if ok.any():
-        tracked = np.ascontiguousarray(ref_b[ok])
-        ref_c1, ref_in = oracle.stereo_match(calib, fe, c["B"], c["B1"], tracked)
-        assert np.array_equal((got["status"][ok] >> 1) & 1, ref_in), tag
-        assert _same(got["out1"][ok], ref_c1), tag
-        assert _same(got["und0"][ok], oracle.undistort(K0, D0, tracked, model=calib.cam0_model)), tag
-        assert _same(got["und1"][ok], oracle.undistort(K1, D1, ref_c1, model=calib.cam1_model)), tag
-        n_in = int(ref_in.sum())
-    return int(ok.sum()), n_in
 
 
 @pytest.mark.parametrize("set_name", sorted(C.CASE_SETS))
