@@ -50,7 +50,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  mskf_fe_match, _batch, _batch_begin, _batch_end (with their own mskf_fe_match_args and mskf_match);
                                  mskf_fe_verify, _batch, _batch_begin, _batch_end (with their own mskf_fe_verify_args);
                                  mskf_fe_set_patch_check, mskf_fe_get_patch_check (with their own mskf_fe_patch_check) and the alias MSKF_K_FE_PATCH of
-                                 the timing slot the mask gate borrowed */
+                                 the timing slot the mask gate borrowed;
+                                 mskf_fe_set_fb_check, mskf_fe_get_fb_check (with their own mskf_fe_fb_check) and the alias MSKF_K_FE_FB of the same slot */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -72,7 +73,7 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
 
 /* Optional per-kernel timing with HIP events recorded on the context's own stream (bench / roofline).
  * `units` are the algorithmic work units of a launch (LK: point tracks, temporal + stereo of one track call in one launch — MSKF_K_PT_GEOM
- * is kept for ABI stability, counts no geometry since that moved into that launch, and carries the point gates behind a track launch instead (MSKF_K_FE_MASK, MSKF_K_FE_PATCH); pyramid: output pixels;
+ * is kept for ABI stability, counts no geometry since that moved into that launch, and carries the point gates behind a track launch instead (MSKF_K_FE_MASK, MSKF_K_FE_PATCH, MSKF_K_FE_FB); pyramid: output pixels;
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
  * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
@@ -88,7 +89,10 @@ enum {
     /* k_patch_points, the point gate of the patch check (mskf_fe_set_patch_check), launched behind a track launch only when a stream of
        that batch checks; units: streams.  The same slot: it counts the point gates behind a track launch, of either kind, and with both
        features off its counts are exactly as before. */
-    MSKF_K_FE_PATCH = MSKF_K_PT_GEOM
+    MSKF_K_FE_PATCH = MSKF_K_PT_GEOM,
+    /* k_fb_points, the point gate of the forward-backward check (mskf_fe_set_fb_check), launched behind a track launch only when a
+       stream of that batch checks; units: streams.  The same slot again: with the three features off its counts are exactly as before. */
+    MSKF_K_FE_FB = MSKF_K_PT_GEOM
 };
 int mskf_ctx_set_timing(mskf_ctx *ctx, int enable);
 /* Accounting gate (default on): while it is off, launches are not timed and host seconds not accumulated.  Unlike
@@ -342,6 +346,34 @@ typedef struct mskf_fe_patch_check {
 } mskf_fe_patch_check;
 int mskf_fe_set_patch_check(mskf_stream *s, const mskf_fe_patch_check *cfg);
 int mskf_fe_get_patch_check(mskf_stream *s, mskf_fe_patch_check *out);      /* a stream never set: {0, 4, 0.8, 0.8} */
+
+/* ---- opt-in forward-backward check of temporal tracks and stereo matches: does LK, run backwards, return to where it started?
+ * Off by default, and then nothing new runs or is allocated.  One more launch (k_fb_points, MSKF_K_FE_FB) behind every track launch
+ * of a batch that has a checking stream: both track launches of a device frame, and mskf_fe_track*; behind the mask gate and the
+ * patch gate, whose survivors it sees (it is the most expensive gate).  It is a pure function of the track's outputs and the resident
+ * pyramids ("Forward-backward check"): the backward track is the forward track's own code over all pyramid levels with
+ * the pyramids' roles swapped, started at the KNOWN ORIGIN (not at the tracked point: the lenient variant), and its result is
+ * compared with that origin: passes iff the backward track succeeded and dx * dx + dy * dy <= max_error * max_error (float32, each
+ * operation rounded; a NaN fails; threshold 0 passes only an exact return).
+ *   temporal (mode bit 1; track calls with do_temporal = 1, points with status bit 0): template at out0[pt] in the current cam0
+ *           image, searched in the previous one from in_pts[pt], compared with in_pts[pt].  A failing point is lost as a track loses
+ *           one: status 0, out1 = und0 = und1 = 0, out0 kept.
+ *   stereo  (mode bit 2; points with status bit 1 of any track call): template at out1[pt] in the current cam1 image, searched in
+ *           the current cam0 image from out0[pt], compared with out0[pt].  A failing point loses bit 1 and nothing else.
+ * The temporal half runs first; a point lost there is not tracked back again.  What it cannot see: a stereo match on the next
+ * period of a repetitive texture is consistent in both directions (that stays with the patch check and the epipolar gate).  The
+ * defaults are starting values nobody has tuned.
+ * mskf_fe_set_fb_check validates before it touches anything: MSKF_ERR_INVALID for a null cfg, an unknown mode bit, a threshold that is
+ * not finite or lies outside [0, 64], and while a track or device-frame batch of the stream's context is pending (mskf_last_error
+ * names it); the previous setting then stays in force.  mode = 0 = off.  A new setting applies from the stream's next track or frame
+ * call.  No device call. */
+enum { MSKF_FB_TEMPORAL = 1, MSKF_FB_STEREO = 2 };
+typedef struct mskf_fe_fb_check {
+    int32_t mode;                                /* MSKF_FB_* bits, 0 = off */
+    float max_error_temporal, max_error_stereo;  /* level-0 pixels, finite, 0 .. 64 */
+} mskf_fe_fb_check;
+int mskf_fe_set_fb_check(mskf_stream *s, const mskf_fe_fb_check *cfg);
+int mskf_fe_get_fb_check(mskf_stream *s, mskf_fe_fb_check *out);      /* a stream never set: {0, 1.0f, 1.0f} */
 
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);

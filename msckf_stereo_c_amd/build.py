@@ -28,6 +28,7 @@ HIP_SRCS = [
     "hip/fe_match.hip",
     "hip/fe_verify.hip",
     "hip/fe_patch.hip",
+    "hip/fe_fb.hip",
     "abi/mskf_capi_ctx.cpp",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_kf.cpp",

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, FeVerifyArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
-                           FeInputFormat, FeMask, FePatchCheck, ImuStep, PATCH_CHECK_MODES, raw_raster)
+                           FB_CHECK_MODES, FeFbCheck, FeInputFormat, FeMask, FePatchCheck, ImuStep, PATCH_CHECK_MODES, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -65,6 +65,7 @@ EXPORTS = [
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
     "mskf_fe_set_mask", "mskf_fe_get_mask", "mskf_fe_set_patch_check", "mskf_fe_get_patch_check",
+    "mskf_fe_set_fb_check", "mskf_fe_get_fb_check",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
     "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
     "mskf_fe_verify", "mskf_fe_verify_batch", "mskf_fe_verify_batch_begin", "mskf_fe_verify_batch_end",
@@ -667,6 +668,23 @@ class Stream:
         self.L.mskf_fe_get_patch_check.argtypes = [C.c_void_p, C.POINTER(FePatchCheck)]
         _chk(self.L.mskf_fe_get_patch_check(self.h, C.byref(cfg)))
         return cfg.mode, cfg.half, cfg.min_zncc_temporal, cfg.min_zncc_stereo
+
+    def set_fb_check(self, mode="both", max_error_temporal=1.0, max_error_stereo=1.0):
+        """mskf_fe_set_fb_check: the forward-backward check behind every track launch (the result is tracked back from the known
+        origin and must return to it); mode "both" / "temporal" / "stereo" / "off" (or the bits 1 | 2), thresholds in level-0
+        pixels, 0 .. 64.  From the next track or frame call on."""
+        if isinstance(mode, str) and mode not in FB_CHECK_MODES:
+            raise MskfError("unknown forward-backward check mode %r" % (mode,), -1)
+        cfg = FeFbCheck(int(FB_CHECK_MODES.get(mode, mode)), float(max_error_temporal), float(max_error_stereo))
+        self.L.mskf_fe_set_fb_check.argtypes = [C.c_void_p, C.POINTER(FeFbCheck)]
+        _chk(self.L.mskf_fe_set_fb_check(self.h, C.byref(cfg)))
+
+    def get_fb_check(self):
+        """(mode bits, max_error_temporal, max_error_stereo) as the stream holds them."""
+        cfg = FeFbCheck()
+        self.L.mskf_fe_get_fb_check.argtypes = [C.c_void_p, C.POINTER(FeFbCheck)]
+        _chk(self.L.mskf_fe_get_fb_check(self.h, C.byref(cfg)))
+        return cfg.mode, cfg.max_error_temporal, cfg.max_error_stereo
 
     def describe(self, role, pts):
         """mskf_fe_describe: the 256-bit descriptors of pts (n x 2, level-0 pixels) on the image `role` (0 prev cam0, 1 curr cam0,

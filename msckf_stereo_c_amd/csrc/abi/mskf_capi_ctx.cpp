@@ -64,6 +64,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     for (int i = 0; i < 3; ++i) c->desc[i].release();
     for (int i = 0; i < 2; ++i) c->mask_desc[i].release();
     c->patch_desc.release();
+    c->fb_desc.release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
     c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();

@@ -268,6 +268,52 @@ static void patch_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int ma
     mskf_t_end(ctx, ts, n);
 }
 
+// ---- opt-in forward-backward check of tracks and stereo matches (include/mskf_hip.h; the decision: fe_fb.h, the kernel: fe_fb.hip)
+static int fb_validate(const mskf_stream *s, const mskf_fe_fb_check *cfg) {
+    if (!s) return MSKF_ERR_INVALID;
+    if (!cfg) { mskf_set_error("forward-backward check: null configuration"); return MSKF_ERR_INVALID; }
+    if (cfg->mode & ~(FB_TEMPORAL | FB_STEREO)) { mskf_set_error("forward-backward check: unknown mode bit (1 temporal, 2 stereo)"); return MSKF_ERR_INVALID; }
+    for (const float t : {cfg->max_error_temporal, cfg->max_error_stereo})
+        if (!std::isfinite(t) || t < 0.f || t > FB_MAX_ERROR) { mskf_set_error("forward-backward check: a threshold must lie in [0, 64] pixels"); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_fb_check(mskf_stream *s, const mskf_fe_fb_check *cfg) {
+    if (const int rc = fb_validate(s, cfg)) return rc;
+    s->fb = *cfg;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_fb_check(mskf_stream *s, mskf_fe_fb_check *out) {
+    if (!s || !out) return MSKF_ERR_INVALID;
+    *out = s->fb;
+    return MSKF_OK;
+}
+
+// The forward-backward checks of the streams of a track launch, element for element beside its descriptors: 0 when no stream
+// checks and nothing was touched, else the array is staged in fb_desc and *cp is its copy.
+static int stage_fb(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) *any = *any || streams[i]->fb.mode != 0;
+    if (!*any) return MSKF_OK;
+    PinnedDev<FeFbDev> &A = ctx->fb_desc;
+    if (const int rc = A.ensure(n)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_fe_fb_check &c = streams[i]->fb;
+        A.h[i] = FeFbDev{fb_thr2(c.max_error_temporal), fb_thr2(c.max_error_stereo), c.mode};
+    }
+    *cp = MskfCopy{A.d, A.h, sizeof(FeFbDev) * (size_t)n};
+    return MSKF_OK;
+}
+
+// The forward-backward gate behind a track launch over `desc_dev` (the checks staged in fb_desc), behind the other two gates,
+// whose survivors it sees; timed as MSKF_K_FE_FB.
+static void fb_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
+    const int ts = mskf_t_begin(ctx, MSKF_K_FE_FB);
+    fe_launch_fb_points(desc_dev, ctx->fb_desc.d, n, max_pts, ctx->stream);
+    mskf_t_end(ctx, ts, n);
+}
+
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
 // 16-bit pixels on 2-byte boundaries.
 static int px_check_images(const mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, long long pitch) {
@@ -597,6 +643,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy patch_cp{};
     bool checked = false;                   // ... or a patch check: its gate runs behind the track and the mask gate
     if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
+    MskfCopy fb_cp{};
+    bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
+    if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -612,10 +661,11 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    MskfCopy cp[4] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
+    MskfCopy cp[5] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
     int n_cp = 2;
     if (masked) cp[n_cp++] = mask_cp;
     if (checked) cp[n_cp++] = patch_cp;
+    if (fb_checked) cp[n_cp++] = fb_cp;
     mskf_ctx::PendingTrack &T = ctx->pend_trk;
     T.n = n; T.args = args;
     rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] {
@@ -625,6 +675,7 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         mskf_t_end(ctx, T.ts, 0);
         if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
         if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_pts);
+        if (fb_checked) fb_gate(ctx, ctx->desc[1].d, n, max_pts);
     }, MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
     if (rc != MSKF_OK) return rc;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
@@ -769,6 +820,9 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy patch_cp{};
     bool checked = false;                   // ... or a patch check: its gate runs behind both track launches, and the mask gate
     if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
+    MskfCopy fb_cp{};
+    bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
+    if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -799,11 +853,12 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         B.x_info = x.info; B.x_id = x.id; B.x_lifetime = x.lifetime; B.x_cam0 = x.cam0; B.x_cam1 = x.cam1; B.x_und0 = x.und0; B.x_und1 = x.und1;
     }
     {
-        MskfCopy cp[5] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
+        MskfCopy cp[6] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
                           {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}};
         int n_cp = 3;
         if (masked) cp[n_cp++] = mask_cp;
         if (checked) cp[n_cp++] = patch_cp;
+        if (fb_checked) cp[n_cp++] = fb_cp;
         if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
     }
     const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
@@ -811,6 +866,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     mskf_t_end(ctx, ts1, 0);
     if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
     if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_prev);
+    if (fb_checked) fb_gate(ctx, ctx->desc[1].d, n, max_prev);
     int tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
@@ -819,6 +875,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     mskf_t_end(ctx, ts2, 0);
     if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     if (checked) patch_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
+    if (fb_checked) fb_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 1, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);

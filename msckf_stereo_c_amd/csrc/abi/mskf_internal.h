@@ -11,6 +11,7 @@
 #include "../hip/fe_pixfmt.h"
 #include "../hip/fe_mask.h"
 #include "../hip/fe_patch.h"
+#include "../hip/fe_fb.h"
 #include "../hip/fe_brief.h"
 #include "../hip/fe_match.h"
 #include "../hip/fe_verify.h"
@@ -32,6 +33,8 @@ void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *ma
 void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
 // patch check (fe_patch.h): patch_dev[i] goes with streams_dev[i]
 void fe_launch_patch_points(const FeStreamDev *streams_dev, const FePatchDev *patch_dev, int n_streams, int max_pts, hipStream_t st);
+// forward-backward check (fe_fb.h): fb_dev[i] goes with streams_dev[i]; the grid of fe_launch_track
+void fe_launch_fb_points(const FeStreamDev *streams_dev, const FeFbDev *fb_dev, int n_streams, int max_pts, hipStream_t st);
 // descriptors (fe_brief.h): jobs of any size and count in one launch; max_pts = the largest count
 void fe_launch_describe(const FeDescribeDev *jobs_dev, int n_jobs, int max_pts, hipStream_t st);
 // descriptor matching (fe_match.h): jobs of any size and count in one launch, cross-checked or not; max_nq / max_nt = the largest counts
@@ -135,7 +138,7 @@ struct StagedBatch : PendingBatch {
 };
 
 // Which pending batch owns which arenas of the context (mskf_ctx::pending lists the records):
-//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
+//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
 //   pend_upd               ekf_desc, upd_in, upd_out (a feature update or a direct update: one record for both kinds);
 //   pend_ro                pred_arena, whose host side its kernel reads and writes (position variances or odometry covariance: one record);
 //   pend_dsc, pend_mch,    the jobs / in / out arenas inside the record itself (StagedBatch), which nothing else touches: only a call
@@ -189,6 +192,7 @@ struct mskf_ctx {
     PinnedDev<FeMaskDev> mask_desc[2];   // the streams' image masks, element for element beside desc[0] (push) and beside desc[1] / desc[2] (track calls:
                                          // one array serves both launches of a device frame); front-end arenas, empty until a stream has a mask
     PinnedDev<FePatchDev> patch_desc;    // the streams' patch checks, element for element beside desc[1] / desc[2]; empty until a stream checks
+    PinnedDev<FeFbDev> fb_desc;          // the streams' forward-backward checks, likewise
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid
     PinnedDev<char> grid_in;          // staging of mskf_fe_set_grid (synchronous: no batch owns it)
@@ -330,6 +334,8 @@ struct mskf_stream {
     } mask;
     // ---- opt-in patch check (mskf_fe_set_patch_check; fe_patch.h): the setting is all there is
     mskf_fe_patch_check patch{0, 4, 0.8f, 0.8f};
+    // ---- opt-in forward-backward check (mskf_fe_set_fb_check; fe_fb.h): likewise
+    mskf_fe_fb_check fb{0, 1.0f, 1.0f};
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

@@ -264,6 +264,24 @@ int mskfh_load_patch_check(const char *yaml_path, mskf_fe_patch_check *out) {
         return -1;
     }
 }
+// ImageProcessor::setFbCheck (mskf_fe_set_fb_check) of one stream, or of all (stream < 0); between runs.  As mskfh_runner_set_patch_check.
+int mskfh_runner_set_fb_check(void *h, int stream, const mskf_fe_fb_check *cfg) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setFbCheck(*cfg); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
+// the optional fb_check keys of an app_imgproc.yaml (fb_check_from_yaml); 0 on success
+int mskfh_load_fb_check(const char *yaml_path, mskf_fe_fb_check *out) {
+    try {
+        *out = fb_check_from_yaml(YAML::LoadFile(yaml_path));
+        return 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "mskfh_load_fb_check: %s\n", e.what());
+        return -1;
+    }
+}
 // ImageProcessor::setDescriptors of one stream, or of all (stream < 0); between runs, from the next frame on
 int mskfh_runner_set_descriptors(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

@@ -126,6 +126,36 @@ int ImageProcessor::setPatchCheck(const mskf_fe_patch_check &cfg) {
     return rc;
 }
 
+mskf_fe_fb_check fb_check_from_yaml(const YAML::Node &y) {
+    mskf_fe_fb_check c{0, 1.0f, 1.0f};
+    if (y["fb_check"].IsDefined()) {
+        const std::string m = y["fb_check"].as<std::string>();
+        if (m == "off") c.mode = 0; else if (m == "temporal") c.mode = 1; else if (m == "stereo") c.mode = 2; else if (m == "both") c.mode = 3;
+        else throw YAML::Exception("yaml: fb_check must be off, temporal, stereo or both, not " + m);
+    }
+    // a threshold must be a number in [0, 64] (as<double>() reads text that is no number as 0, which is a legal and very strict threshold)
+    const auto pixels = [&](const char *key, float &out) {
+        if (!y[key].IsDefined()) return;
+        const std::string v = y[key].as<std::string>();
+        char *end = nullptr;
+        const double t = std::strtod(v.c_str(), &end);
+        if (end == v.c_str() || *end != '\0' || !std::isfinite(t) || t < 0.0 || t > 64.0)
+            throw YAML::Exception(std::string("yaml: ") + key + " must be a number of pixels in 0 .. 64, not " + v);
+        out = (float)t;
+    };
+    pixels("fb_check_max_error_temporal", c.max_error_temporal);
+    pixels("fb_check_max_error_stereo", c.max_error_stereo);
+    return c;
+}
+
+int ImageProcessor::setFbCheck(const mskf_fe_fb_check &cfg) {
+    if (!initialized_ || !stream_) { fb_cfg_ = cfg; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
+    const int rc = mskf_fe_set_fb_check(stream_, &cfg);
+    if (rc != MSKF_OK) { fail("mskf_fe_set_fb_check", rc); return rc; }   // refused: fbCheck() keeps reporting what the stream holds
+    fb_cfg_ = cfg;
+    return rc;
+}
+
 MaskFiles mask_files_from_yaml(const YAML::Node &y) {
     MaskFiles m;
     if (y["mask_cam0"].IsDefined()) m.cam0 = y["mask_cam0"].as<std::string>();
@@ -251,6 +281,7 @@ bool ImageProcessor::loadParameters() {
         eq_cfg_ = equalize_from_yaml(cfg_imgproc);
         px_cfg_ = input_format_from_yaml(cfg_imgproc);
         patch_cfg_ = patch_check_from_yaml(cfg_imgproc);
+        fb_cfg_ = fb_check_from_yaml(cfg_imgproc);
         descriptors_ =descriptors_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
@@ -289,6 +320,8 @@ bool ImageProcessor::initialize() {
     if (stream_ && applyKeptMask() != MSKF_OK) return false;
     // ... and the opt-in patch check, likewise
     if (stream_ && patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
+    // ... and the opt-in forward-backward check, likewise
+    if (stream_ && fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return false;
     return true;
 }
 
@@ -334,6 +367,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return;
         if (applyKeptMask() != MSKF_OK) return;
         if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return;
+        if (fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
     if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {

@@ -37,6 +37,10 @@ MaskFiles mask_files_from_yaml(const YAML::Node &cfg_imgproc);
 // patch_check_min_zncc_temporal, patch_check_min_zncc_stereo: 0 .. 1 (mskf_fe_set_patch_check; absent = off, 4, 0.8, 0.8).  Throws
 // YAML::Exception on an unknown patch_check value.
 mskf_fe_patch_check patch_check_from_yaml(const YAML::Node &cfg_imgproc);
+// ... and the forward-backward check of tracks and stereo matches: fb_check: off | temporal | stereo | both,
+// fb_check_max_error_temporal, fb_check_max_error_stereo: level-0 pixels, 0 .. 64 (mskf_fe_set_fb_check; absent = off, 1.0, 1.0).
+// Throws YAML::Exception on an unknown fb_check value.
+mskf_fe_fb_check fb_check_from_yaml(const YAML::Node &cfg_imgproc);
 // ... and descriptors: off | brief256 (absent = off): 256-bit binary descriptors of the published features (mskf_fe_describe_batch),
 // with descriptors_out: <file> for their text output (which turns them on).  Throws YAML::Exception on an unknown value.
 bool descriptors_from_yaml(const YAML::Node &cfg_imgproc);
@@ -124,6 +128,9 @@ class ImageProcessor {
     // refusal leaves the previous setting in force.  mode 0 = off.
     int setPatchCheck(const mskf_fe_patch_check &cfg);
     const mskf_fe_patch_check &patchCheck() const { return patch_cfg_; }
+    // opt-in forward-backward check of temporal tracks and stereo matches (mskf_fe_set_fb_check): kept and set like setPatchCheck.
+    int setFbCheck(const mskf_fe_fb_check &cfg);
+    const mskf_fe_fb_check &fbCheck() const { return fb_cfg_; }
     // opt-in 256-bit descriptors (mskf_fe_describe_batch; DESIGN.md section 3, "Descriptors") of the features a frame publishes:
     // frame k's cam0 level 0 at the cam0 pixels of the features of frame k's message, in message order.  Off by default; takes
     // effect with the next frame.  descriptorIds() / descriptors() (32 bytes each) / descriptorValid() are those of the last frame.
@@ -228,6 +235,7 @@ class ImageProcessor {
     mskf_fe_equalize eq_cfg_{0, 8, 8, 0, 40.0};
     mskf_fe_input_format px_cfg_{0, 0};
     mskf_fe_patch_check patch_cfg_{0, 4, 0.8f, 0.8f};
+    mskf_fe_fb_check fb_cfg_{0, 1.0f, 1.0f};
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
     int applyKeptMask();
     bool descriptors_ = false;

@@ -44,6 +44,7 @@ class System {
     mskf_fe_equalize equalize_{0, 8, 8, 0, 40.0};      // the YAML constructor reads it from app_imgproc.yaml (equalize_from_yaml)
     MaskFiles mask_files_;
     mskf_fe_patch_check patch_check_{0, 4, 0.8f, 0.8f};  // likewise (patch_check_from_yaml)
+    mskf_fe_fb_check fb_check_{0, 1.0f, 1.0f};          // likewise (fb_check_from_yaml)
     bool descriptors_ = false;                         // likewise (descriptors_from_yaml)
     std::shared_ptr<CameraMeasurement> feature_msg_ptr_;
     cg::MsckfVioPtr msckfvio_ptr_;

@@ -116,6 +116,16 @@ assert C.sizeof(FePatchCheck) == 16
 PATCH_CHECK_MODES = {"off": 0, "temporal": 1, "stereo": 2, "both": 3}
 
 
+class FeFbCheck(C.Structure):
+    """mskf_fe_fb_check (include/mskf_hip.h): the forward-backward check of temporal tracks (mode bit 1) and stereo matches (bit 2)."""
+    _fields_ = [("mode", C.c_int32), ("max_error_temporal", C.c_float), ("max_error_stereo", C.c_float)]
+
+
+assert C.sizeof(FeFbCheck) == 12
+FB_CHECK_MODES = {"off": 0, "temporal": 1, "stereo": 2, "both": 3}
+FB_MAX_ERROR = 64.0          # FB_MAX_ERROR (csrc/hip/fe_fb.h)
+
+
 class FeDescribeArgs(C.Structure):
     """mskf_fe_describe_args (include/mskf_hip.h): n points of the image of `role` in, 32 n descriptor bytes and n validity bytes out."""
     _fields_ = [("role", C.c_int32), ("n", C.c_int32), ("pts", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p)]

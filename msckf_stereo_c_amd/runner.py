@@ -9,7 +9,7 @@ import numpy as np
 
 from .capi import MskfError
 from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat, FeMask,
-                           FePatchCheck, ImuSample, PATCH_CHECK_MODES, TrackingInfo, raw_raster)
+                           FB_CHECK_MODES, FeFbCheck, FePatchCheck, ImuSample, PATCH_CHECK_MODES, TrackingInfo, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -263,6 +263,20 @@ class Runner:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
 
+    def set_fb_check(self, mode="both", max_error_temporal=1.0, max_error_stereo=1.0, stream=None):
+        """Opt-in forward-backward check of one stream or of all (mskf_fe_set_fb_check): tracked points ("temporal") and stereo
+        matches ("stereo") that LK, run backwards from the known origin, does not bring back to within the threshold are dropped
+        behind every track launch.  mode "both" / "temporal" / "stereo" / "off"; thresholds in level-0 pixels, 0 .. 64.  Call
+        between runs."""
+        if isinstance(mode, str) and mode not in FB_CHECK_MODES:
+            raise MskfError("unknown forward-backward check mode %r" % (mode,), -1)
+        cfg = FeFbCheck(int(FB_CHECK_MODES.get(mode, mode)), float(max_error_temporal), float(max_error_stereo))
+        self.L.mskfh_runner_set_fb_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeFbCheck)]
+        rc = self.L.mskfh_runner_set_fb_check(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
     def set_descriptors(self, on, stream=None):
         """Opt-in 256-bit binary descriptors (upright BRIEF) of the features every frame publishes, of one stream
         or of all: one more batched device call per frame of a group with a describing stream.  Off by default; call between runs."""
@@ -457,7 +471,7 @@ class Runner:
         """Per-kernel HIP-event timing accumulated on the groups' own streams: {kernel: (ms, launches, units)}.  The key
         "k_ekf_augment" carries the launches of k_ekf_direct_update (fused measurements, zero-velocity updates; units: streams with
         rows) and nothing else: the augmentation itself runs inside k_ekf_propagate, and the slot keeps its name for the ABI.
-        Likewise "k_pt_geom" carries the point gates behind a track launch (k_mask_points, k_patch_points; units: streams)."""
+        Likewise "k_pt_geom" carries the point gates behind a track launch (k_mask_points, k_patch_points, k_fb_points; units: streams)."""
         k = len(self.KERNELS)
         ms = np.zeros(k)
         launches = np.zeros(k, np.int64)
