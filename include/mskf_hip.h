@@ -375,6 +375,32 @@ typedef struct mskf_fe_fb_check {
 int mskf_fe_set_fb_check(mskf_stream *s, const mskf_fe_fb_check *cfg);
 int mskf_fe_get_fb_check(mskf_stream *s, mskf_fe_fb_check *out);      /* a stream never set: {0, 1.0f, 1.0f} */
 
+/* ---- opt-in camera models beyond the two of mskf_calib: OpenCV's rational radtan, Kalibr's fov distortion, the double-sphere camera.
+ * Off by default, and then nothing new runs or is allocated.  The intrinsics fx fy cx cy stay those of mskf_calib; each camera of
+ * a stream takes a model of its own ("Extended camera models", has the formulas and their operation order):
+ *   MSKF_MODEL_RADTAN8  k1 k2 p1 p2 k3 k4 k5 k6, OpenCV's order (cv::projectPoints / cv::undistortPoints, five fixed-point steps).  A
+ *                       five-coefficient calibration is k4 = k5 = k6 = 0; with k3 .. k6 = 0 it gives the bits of MSKF_MODEL_RADTAN.
+ *   MSKF_MODEL_FOV      w (radians, 0 < w < pi): rd = atan(2 ru tan(w / 2)) / w.  A pixel with rd w >= pi/2 is outside the domain.
+ *   MSKF_MODEL_DS       xi, alpha (-1 < xi <= 1, 0 <= alpha <= 1), Usenko et al. 2018, rays on the z = 1 plane.  Outside the domain:
+ *                       the paper's projection condition fails or the denominator is not positive; alpha > 0.5 and
+ *                       r2 > 1 / (2 alpha - 1); an un-projected ray with z <= 0 (fields of view that reach 90 degrees off axis).
+ *   MSKF_MODEL_RADTAN / MSKF_MODEL_EQUIDISTANT with four coefficients are accepted too and put the camera back on the base path.
+ * A point outside the domain (the base models never refuse one): where the stereo guess cannot be formed the point takes no stereo
+ * trip (out1 = 0, status bit 1 clear); a point whose und0 or und1 cannot be computed loses status bit 1 as behind the epipolar gate,
+ * and the coordinates that could not be computed are 0.  Status bit 0, out0 and the temporal result are untouched.
+ * A track or device-frame batch in which a stream has an extended model on either camera launches the extended instantiation of the
+ * track kernel (k_track4_ext, timed as MSKF_K_LK) in place of k_track4, for both track launches of a device frame and for
+ * mskf_fe_track*; base-model streams of such a batch get the bits they get from k_track4.  The gates run behind it as before.
+ * mskf_fe_set_camera_model validates before it touches anything: MSKF_ERR_INVALID for a null pointer, cam not 0 or 1, an unknown
+ * model, a coefficient that is not finite (all eight are looked at; those past the model's own are kept and ignored), w outside
+ * (0, pi), xi or alpha outside their ranges, and while a track or device-frame batch of the stream's context is pending
+ * (mskf_last_error names the reason); the previous setting then stays in force.  A new setting applies from the stream's next track
+ * or frame call.  No device call: the coefficients travel with the staged descriptors. */
+enum { MSKF_MODEL_RADTAN8 = 2, MSKF_MODEL_FOV = 3, MSKF_MODEL_DS = 4 };      /* continue MSKF_MODEL_* */
+typedef struct mskf_fe_camera_model { int32_t cam, model; double coeffs[8]; } mskf_fe_camera_model;
+int mskf_fe_set_camera_model(mskf_stream *s, const mskf_fe_camera_model *cfg);
+int mskf_fe_get_camera_model(mskf_stream *s, int cam, mskf_fe_camera_model *out);      /* a stream never set: what mskf_calib gave it */
+
 /* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);
 

@@ -6,7 +6,7 @@ import os
 import numpy as np
 
 from .ctypes_types import (CORNER, DESCRIPTOR_BYTES, EQUALIZE_MODES, EkfDirectArgs, FeDescribeArgs, FeMatchArgs, FeVerifyArgs, IMU_STEP, MATCH, INPUT_FORMAT_BPP, INPUT_FORMATS, ODOM_COV, POINT2F, Calib, EkfCfg, FeCfg, FeEqualize,
-                           FB_CHECK_MODES, FeFbCheck, FeInputFormat, FeMask, FePatchCheck, ImuStep, PATCH_CHECK_MODES, raw_raster)
+                           CAMERA_MODELS, FB_CHECK_MODES, FeCameraModel, FeFbCheck, FeInputFormat, FeMask, FePatchCheck, ImuStep, PATCH_CHECK_MODES, camera_model_cfg, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -65,7 +65,7 @@ EXPORTS = [
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
     "mskf_fe_set_mask", "mskf_fe_get_mask", "mskf_fe_set_patch_check", "mskf_fe_get_patch_check",
-    "mskf_fe_set_fb_check", "mskf_fe_get_fb_check",
+    "mskf_fe_set_fb_check", "mskf_fe_get_fb_check", "mskf_fe_set_camera_model", "mskf_fe_get_camera_model",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
     "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
     "mskf_fe_verify", "mskf_fe_verify_batch", "mskf_fe_verify_batch_begin", "mskf_fe_verify_batch_end",
@@ -685,6 +685,25 @@ class Stream:
         self.L.mskf_fe_get_fb_check.argtypes = [C.c_void_p, C.POINTER(FeFbCheck)]
         _chk(self.L.mskf_fe_get_fb_check(self.h, C.byref(cfg)))
         return cfg.mode, cfg.max_error_temporal, cfg.max_error_stereo
+
+    def set_camera_model(self, cam, model, coeffs):
+        """mskf_fe_set_camera_model: camera `cam` (0 / 1) takes the model "radtan" | "equidistant" (4 coefficients: back on the base
+        path) | "radtan8" (OpenCV's 5 or 8: k1 k2 p1 p2 k3 [k4 k5 k6]) | "fov" (w) | "ds" (xi, alpha); the intrinsics stay the
+        calibration's.  From the next track or frame call on."""
+        try:
+            cfg = camera_model_cfg(cam, model, coeffs)
+        except ValueError as e:
+            raise MskfError(str(e), -1)
+        self.L.mskf_fe_set_camera_model.argtypes = [C.c_void_p, C.POINTER(FeCameraModel)]
+        _chk(self.L.mskf_fe_set_camera_model(self.h, C.byref(cfg)))
+
+    def get_camera_model(self, cam):
+        """(model name, the eight coefficients as the stream holds them) of camera `cam`."""
+        cfg = FeCameraModel()
+        self.L.mskf_fe_get_camera_model.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeCameraModel)]
+        _chk(self.L.mskf_fe_get_camera_model(self.h, int(cam), C.byref(cfg)))
+        names = {v: k for k, v in CAMERA_MODELS.items()}
+        return names.get(cfg.model, cfg.model), [float(v) for v in cfg.coeffs]
 
     def describe(self, role, pts):
         """mskf_fe_describe: the 256-bit descriptors of pts (n x 2, level-0 pixels) on the image `role` (0 prev cam0, 1 curr cam0,

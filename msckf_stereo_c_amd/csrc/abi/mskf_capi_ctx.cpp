@@ -65,6 +65,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     for (int i = 0; i < 2; ++i) c->mask_desc[i].release();
     c->patch_desc.release();
     c->fb_desc.release();
+    c->cam_desc.release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
     c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
@@ -401,7 +402,9 @@ extern "C" int mskf_stream_create(mskf_ctx *ctx, const mskf_calib *calib, const 
         s->cam0.K[i] = calib->cam0_intrinsics[i]; s->cam0.D[i] = calib->cam0_distortion[i];
         s->cam0.model = calib->cam0_model; s->cam1.model = calib->cam1_model;
         s->cam1.K[i] = calib->cam1_intrinsics[i]; s->cam1.D[i] = calib->cam1_distortion[i];
+        s->cam_ext.coef[0][i] = calib->cam0_distortion[i]; s->cam_ext.coef[1][i] = calib->cam1_distortion[i];
     }
+    s->cam_ext.model[0] = calib->cam0_model; s->cam_ext.model[1] = calib->cam1_model;      // (mskf_fe_set_camera_model may change it)
     // image_processor.cpp:63-72 (loadParameters) and :544,:587-591 (stereoMatch)
     using namespace hm;
     Rigid m4_cam0_imu = Rigid::from_rowmajor16(calib->T_cam0_imu);

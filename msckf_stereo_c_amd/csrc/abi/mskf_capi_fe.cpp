@@ -314,6 +314,60 @@ static void fb_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_p
     mskf_t_end(ctx, ts, n);
 }
 
+// ---- opt-in camera models (include/mskf_hip.h; arithmetic, domains and the coefficient check: fe_cam_models.h)
+static int cam_validate(const mskf_stream *s, const mskf_fe_camera_model *cfg) {
+    if (!s) return MSKF_ERR_INVALID;
+    if (!cfg) { mskf_set_error("camera model: null configuration"); return MSKF_ERR_INVALID; }
+    if (cfg->cam != 0 && cfg->cam != 1) { mskf_set_error("camera model: cam must be 0 or 1"); return MSKF_ERR_INVALID; }
+    static const char *const why[] = {nullptr, "camera model: unknown model (0 radtan, 1 equidistant, 2 radtan8, 3 fov, 4 ds)", "camera model: a coefficient is not finite",
+                                      "camera model: fov's w must lie in (0, pi)", "camera model: ds's xi must lie in (-1, 1]", "camera model: ds's alpha must lie in [0, 1]"};
+    if (const int bad = fcm_validate(cfg->model, cfg->coeffs)) { mskf_set_error(why[bad]); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_camera_model(mskf_stream *s, const mskf_fe_camera_model *cfg) {
+    if (const int rc = cam_validate(s, cfg)) return rc;
+    const int c = cfg->cam;
+    s->cam_ext.model[c] = cfg->model;
+    std::memcpy(s->cam_ext.coef[c], cfg->coeffs, sizeof(cfg->coeffs));
+    if (cfg->model < FCM_RADTAN8) {      // back on the base path: CamDev is what k_track4 reads
+        CamDev &cam = c ? s->cam1 : s->cam0;
+        cam.model = cfg->model;
+        std::memcpy(cam.D, cfg->coeffs, sizeof(cam.D));
+    }
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_camera_model(mskf_stream *s, int cam, mskf_fe_camera_model *out) {
+    if (!s || !out || (cam != 0 && cam != 1)) return MSKF_ERR_INVALID;
+    out->cam = cam; out->model = s->cam_ext.model[cam];
+    std::memcpy(out->coeffs, s->cam_ext.coef[cam], sizeof(out->coeffs));
+    return MSKF_OK;
+}
+
+// The camera models of the streams of a track launch, element for element beside its descriptors: 0 when no stream has an
+// extended model and nothing was touched, else the array is staged in cam_desc and *cp is its copy.
+static int stage_cams(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) *any = *any || streams[i]->cam_ext.any();
+    if (!*any) return MSKF_OK;
+    PinnedDev<FeCamExtDev> &A = ctx->cam_desc;
+    if (const int rc = A.ensure(n)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream::CamExt &c = streams[i]->cam_ext;
+        A.h[i].model[0] = c.model[0]; A.h[i].model[1] = c.model[1];
+        std::memcpy(A.h[i].coef, c.coef, sizeof(c.coef));
+    }
+    *cp = MskfCopy{A.d, A.h, sizeof(FeCamExtDev) * (size_t)n};
+    return MSKF_OK;
+}
+
+// A track launch over `desc_dev`: k_track4, or its extended instantiation over the models staged in cam_desc.
+static void track_launch(mskf_ctx *ctx, bool extended, const FeStreamDev *desc_dev, int n, int max_pts) {
+    if (extended) fe_launch_track_ext(desc_dev, ctx->cam_desc.d, n, max_pts, ctx->stream);
+    else fe_launch_track(desc_dev, n, max_pts, ctx->stream);
+}
+
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
 // 16-bit pixels on 2-byte boundaries.
 static int px_check_images(const mskf_stream *s, const uint8_t *cam0, const uint8_t *cam1, long long pitch) {
@@ -615,7 +669,6 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     if (rc != MSKF_OK) return rc;
     MSKF_HIPCHK(hipSetDevice(ctx->device));
     const auto t_h0 = std::chrono::steady_clock::now();
-    hipStream_t st = ctx->stream;
     rc = ctx->desc[1].ensure(n);
     if (rc != MSKF_OK) return rc;
     int max_pts = 0;
@@ -646,6 +699,9 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy fb_cp{};
     bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
     if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
+    MskfCopy cam_cp{};
+    bool extended = false;                  // ... or an extended camera model: the extended instantiation of the track kernel runs
+    if ((rc = stage_cams(ctx, n, streams, &cam_cp, &extended)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -661,17 +717,18 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    MskfCopy cp[5] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
+    MskfCopy cp[MSKF_COPY_SEGS] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
     int n_cp = 2;
     if (masked) cp[n_cp++] = mask_cp;
     if (checked) cp[n_cp++] = patch_cp;
     if (fb_checked) cp[n_cp++] = fb_cp;
+    if (extended) cp[n_cp++] = cam_cp;
     mskf_ctx::PendingTrack &T = ctx->pend_trk;
     T.n = n; T.args = args;
     rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] {
         // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
         T.ts = mskf_t_begin(ctx, MSKF_K_LK);
-        fe_launch_track(ctx->desc[1].d, n, max_pts, st);
+        track_launch(ctx, extended, ctx->desc[1].d, n, max_pts);
         mskf_t_end(ctx, T.ts, 0);
         if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
         if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_pts);
@@ -823,6 +880,9 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy fb_cp{};
     bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
     if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
+    MskfCopy cam_cp{};
+    bool extended = false;                  // ... or an extended camera model: both track launches run the extended instantiation
+    if ((rc = stage_cams(ctx, n, streams, &cam_cp, &extended)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -860,9 +920,10 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         if (checked) cp[n_cp++] = patch_cp;
         if (fb_checked) cp[n_cp++] = fb_cp;
         if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
+        if (extended && (rc = mskf_copy_async(ctx, &cam_cp, 1)) != MSKF_OK) return rc;      // (a copy of its own: cp may already hold MSKF_COPY_SEGS segments)
     }
     const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
-    fe_launch_track(ctx->desc[1].d, n, max_prev, st);
+    track_launch(ctx, extended, ctx->desc[1].d, n, max_prev);
     mskf_t_end(ctx, ts1, 0);
     if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
     if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_prev);
@@ -871,7 +932,7 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
     const int ts2 = mskf_t_begin(ctx, MSKF_K_LK);
-    fe_launch_track(ctx->desc[2].d, n, std::max(max_cand_est, 4), st);
+    track_launch(ctx, extended, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     mskf_t_end(ctx, ts2, 0);
     if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     if (checked) patch_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));

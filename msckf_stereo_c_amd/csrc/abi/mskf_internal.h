@@ -12,6 +12,7 @@
 #include "../hip/fe_mask.h"
 #include "../hip/fe_patch.h"
 #include "../hip/fe_fb.h"
+#include "../hip/fe_cam_models.h"
 #include "../hip/fe_brief.h"
 #include "../hip/fe_match.h"
 #include "../hip/fe_verify.h"
@@ -28,6 +29,8 @@ void fe_launch_pyr_down3(const Pyr3Job *jobs_dev, int n_jobs, int max_w0, int ma
 int mskf_wait(mskf_ctx *c);
 void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts, hipStream_t st);
+// extended camera models (fe_cam_models.h): cams_dev[i] goes with streams_dev[i]; the extended instantiation of the track kernel
+void fe_launch_track_ext(const FeStreamDev *streams_dev, const FeCamExtDev *cams_dev, int n_streams, int max_pts, hipStream_t st);
 // image masks (fe_mask.h): masks_dev[i] goes with streams_dev[i]
 void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
@@ -138,7 +141,7 @@ struct StagedBatch : PendingBatch {
 };
 
 // Which pending batch owns which arenas of the context (mskf_ctx::pending lists the records):
-//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
+//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, cam_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
 //   pend_upd               ekf_desc, upd_in, upd_out (a feature update or a direct update: one record for both kinds);
 //   pend_ro                pred_arena, whose host side its kernel reads and writes (position variances or odometry covariance: one record);
 //   pend_dsc, pend_mch,    the jobs / in / out arenas inside the record itself (StagedBatch), which nothing else touches: only a call
@@ -193,6 +196,7 @@ struct mskf_ctx {
                                          // one array serves both launches of a device frame); front-end arenas, empty until a stream has a mask
     PinnedDev<FePatchDev> patch_desc;    // the streams' patch checks, element for element beside desc[1] / desc[2]; empty until a stream checks
     PinnedDev<FeFbDev> fb_desc;          // the streams' forward-backward checks, likewise
+    PinnedDev<FeCamExtDev> cam_desc;     // the streams' camera models, likewise; empty until a stream has an extended model
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid
     PinnedDev<char> grid_in;          // staging of mskf_fe_set_grid (synchronous: no batch owns it)
@@ -336,6 +340,13 @@ struct mskf_stream {
     mskf_fe_patch_check patch{0, 4, 0.8f, 0.8f};
     // ---- opt-in forward-backward check (mskf_fe_set_fb_check; fe_fb.h): likewise
     mskf_fe_fb_check fb{0, 1.0f, 1.0f};
+    // ---- opt-in camera models (mskf_fe_set_camera_model; fe_cam_models.h): per camera the model and all eight coefficients as set
+    // (a base model's first four are also CamDev::D).  A stream never set holds what mskf_calib gave it.
+    struct CamExt {
+        int model[2] = {0, 0};
+        double coef[2][FCM_COEFFS] = {{0}, {0}};
+        bool any() const { return model[0] >= FCM_RADTAN8 || model[1] >= FCM_RADTAN8; }
+    } cam_ext;
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

@@ -5,6 +5,8 @@
 //  k_track4       : cg::optical_flow_multi_level (:410 temporal, :569 stereo) with the prediction (:321-350), the
 //                   image-bounds gates (:416-424, :575-583), the stereo initial guess (:542-548), undistortion and
 //                   the epipolar gate (:587-617): one launch per track call, four points per wavefront.
+//  k_track4_ext   : — (opt-in camera models radtan8 / fov / ds, fe_cam_models.h): the second instantiation of k_track4's body,
+//                   launched in its place for a batch in which a stream has an extended model.
 //  k_mask_points  : — (opt-in image masks, fe_mask.h): the point gate behind a track launch; k_detect_cells<true> is the
 //                   detector of a push that has a masked stream.
 //
@@ -504,70 +506,9 @@ extern "C" void fe_launch_detect_masked(const FeStreamDev *streams_dev, const Fe
 }
 
 // ------------------------------------------------------------------------------------------ point math
-// Deterministic atan / tan for the equidistant (fisheye) camera model.  cv::fisheye::distortPoints needs atan(r),
-// cv::fisheye::undistortPoints needs tan(theta); libm and the GPU math library do not round them identically, so both
-// sides evaluate the SAME sequence of IEEE double operations (+ - * / only, no contraction): argument reduction to a
-// small interval and an odd Taylor polynomial.  Accuracy as doubles: within 8 * 2^-53 = 8.9e-16 relative of tanl on
-// (0, pi/2] and of atanl on (0, 1e300) (observed 4.5e-16 / 4.1e-16; tests/test_camera_reference.py sweeps oracle/o_math.h's
-// copy); through the camera models the float32 outputs equal the rounded long-double model
-// (tests/test_gpu_camera_geometry.py on the device).
-
-// atan(x), x >= 0:  x > 1 -> pi/2 - atan(1/x);  then atan(x) = atan(c) + atan((x - c) / (1 + x c)) with the nearest
-// c in {0, 1/4, 1/2, 3/4, 1} (|z| <= 1/8 -> 11 odd terms leave < 1e-21)
-__device__ __forceinline__ double det_atan(double x) {
-    const bool inv = x > 1.0;
-    if (inv) x = 1.0 / x;
-    double c = 0.0, ac = 0.0;
-    if (x > 0.875)      { c = 1.0;  ac = 0.78539816339744830962; }
-    else if (x > 0.625) { c = 0.75; ac = 0.64350110879328438680; }
-    else if (x > 0.375) { c = 0.5;  ac = 0.46364760900080611621; }
-    else if (x > 0.125) { c = 0.25; ac = 0.24497866312686415417; }
-    const double z = (x - c) / (1.0 + x * c);
-    const double z2 = z * z;
-    double p = 1.0 / 21.0;
-    p = 1.0 / 19.0 - z2 * p;
-    p = 1.0 / 17.0 - z2 * p;
-    p = 1.0 / 15.0 - z2 * p;
-    p = 1.0 / 13.0 - z2 * p;
-    p = 1.0 / 11.0 - z2 * p;
-    p = 1.0 / 9.0 - z2 * p;
-    p = 1.0 / 7.0 - z2 * p;
-    p = 1.0 / 5.0 - z2 * p;
-    p = 1.0 / 3.0 - z2 * p;
-    p = 1.0 - z2 * p;
-    const double a = ac + z * p;
-    return inv ? 1.5707963267948966192 - a : a;
-}
-// tan(t), 0 <= t <= pi/2:  t > pi/4 -> 1 / tan(pi/2 - t);  tan = sin / cos with Taylor series on [0, pi/4].  pi/2 is taken
-// in two parts (the double nearest it, whose difference with t is exact for t >= pi/4, plus the 6.1e-17 that double lacks):
-// with one part the reduced argument is 0 at the double pi/2, where undistort_pt clamps theta_d, and tan there is inf.
-__device__ __forceinline__ double det_tan(double t) {
-    const bool inv = t > 0.78539816339744830962;
-    if (inv) t = (1.5707963267948966192 - t) + 6.123233995736766e-17;
-    const double t2 = t * t;
-    double s = 1.0 / 121645100408832000.0;              // 1/19!
-    s = 1.0 / 355687428096000.0 - t2 * s;                // 1/17!
-    s = 1.0 / 1307674368000.0 - t2 * s;                  // 1/15!
-    s = 1.0 / 6227020800.0 - t2 * s;                     // 1/13!
-    s = 1.0 / 39916800.0 - t2 * s;                       // 1/11!
-    s = 1.0 / 362880.0 - t2 * s;                         // 1/9!
-    s = 1.0 / 5040.0 - t2 * s;                           // 1/7!
-    s = 1.0 / 120.0 - t2 * s;                            // 1/5!
-    s = 1.0 / 6.0 - t2 * s;                              // 1/3!
-    s = t * (1.0 - t2 * s);
-    double c = 1.0 / 6402373705728000.0;                 // 1/18!
-    c = 1.0 / 20922789888000.0 - t2 * c;                 // 1/16!
-    c = 1.0 / 87178291200.0 - t2 * c;                    // 1/14!
-    c = 1.0 / 479001600.0 - t2 * c;                      // 1/12!
-    c = 1.0 / 3628800.0 - t2 * c;                        // 1/10!
-    c = 1.0 / 40320.0 - t2 * c;                          // 1/8!
-    c = 1.0 / 720.0 - t2 * c;                            // 1/6!
-    c = 1.0 / 24.0 - t2 * c;                             // 1/4!
-    c = 0.5 - t2 * c;                                    // 1/2!
-    c = 1.0 - t2 * c;
-    return inv ? c / s : s / c;
-}
-
+// det_atan / det_tan, the deterministic atan / tan of the equidistant model, live in fe_cam_models.h with the opt-in camera
+// models that also need them (one source for the kernel and the g++ harnesses).
+#include "fe_cam_models.h"
 
 // cv::undistortPoints (radtan: 5 fixed-point iterations; equidistant: cv::fisheye::undistortPoints, Newton on theta,
 // <= 10 iterations), then R, then P = {1,1,0,0}.  Same operation sequence as oracle/o_image.cpp undistort_point.
@@ -643,6 +584,19 @@ __device__ __forceinline__ void distort_pt(const CamDev &cam, float xf, float yf
     vo = (float)(yd * fy + cy);
 }
 
+// The opt-in camera models (fe_cam_models.h, which puts the same pixel step, rotation and rounding around them): what the extended
+// instantiation of the track kernel calls.  A camera on a base model goes through undistort_pt / distort_pt themselves (the old operation
+// sequence: a mixed batch runs base-model streams through the extended launch).  false = outside the model's domain, and
+// then the outputs are 0.  `model` is uniform over a stream, so the switch is a scalar branch.
+__device__ __forceinline__ bool undistort_pt_ext(const CamDev &cam, int model, const double *coef, const double *R, float u, float v, float &xo, float &yo) {
+    if (model < FCM_RADTAN8) { undistort_pt(cam, R, u, v, xo, yo); return true; }
+    return fcm_undistort_px(cam.K, model, coef, R, u, v, xo, yo);
+}
+__device__ __forceinline__ bool distort_pt_ext(const CamDev &cam, int model, const double *coef, float xf, float yf, float &uo, float &vo) {
+    if (model < FCM_RADTAN8) { distort_pt(cam, xf, yf, uo, vo); return true; }
+    return fcm_distort_px(cam.K, model, coef, xf, yf, uo, vo);
+}
+
 // ------------------------------------------------------------------------------------------ LK (l4_track and its parts: fe_lk.h)
 #include "fe_lk.h"
 
@@ -661,7 +615,14 @@ __device__ __forceinline__ void distort_pt(const CamDev &cam, float xf, float yf
 // stereo match accepted; a point that fails the temporal half gets out1 = und0 = und1 = 0 and status 0.
 // Block -> (stream, point group): the blocks b and b + 8 share an XCD (round-robin dispatch, speed only), so the point
 // groups of ONE stream are given ids that are congruent modulo 8: a stream's pyramid levels then travel through one L2.
-__global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n_streams, int groups_per_stream) {
+// The body is written once and instantiated twice: k_track4 (EXT = false: the two base models, the code object every default
+// launch runs) and k_track4_ext (EXT = true: it also reads the streams' FeCamExtDev records, fe_cam_models.h; launched only for
+// a batch in which a stream has an extended model).  Under EXT a point outside a model's domain takes no stereo trip (out1 = 0,
+// stereo status 0) when its guess cannot be formed, and loses status bit 1 when und0 or und1 cannot; what could not be computed
+// is written as 0.
+template <bool EXT>
+__device__ __forceinline__ void track4_body(const FeStreamDev *streams, const FeCamExtDev *exts, int n_streams, int groups_per_stream,
+                                            uint32_t (*s_T)[L4_TROWS * L4_DW + 2], uint32_t (*s_S)[L4_SROWS * L4_DW + 4]) {
     const int x = blockIdx.x & 7, qb = blockIdx.x >> 3;
     const int si = x + 8 * (qb / groups_per_stream), gi = qb - (qb / groups_per_stream) * groups_per_stream;
     if (si >= n_streams) return;
@@ -670,8 +631,6 @@ __global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n
     // a block takes several point groups if there are more
     const int n_pts = S.n_pts_dev ? *S.n_pts_dev : S.n_pts;
     const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
-    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
     uint32_t *sT = s_T[g], *sS = s_S[g];
 #pragma nounroll
     for (int gq = gi; 4 * gq < n_pts; gq += groups_per_stream) {
@@ -704,12 +663,20 @@ __global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n
         if (ph == 1) {
             // stereo initial guess (:542-548) of the points that are still there
             gx = 0.f; gy = 0.f;
+            bool guessed = ok;
             if (ok) {
                 float rx, ry;
-                undistort_pt(S.cam0, S.R01, c0x, c0y, rx, ry);
-                distort_pt(S.cam1, rx, ry, gx, gy);
+                if (EXT) {
+                    const FeCamExtDev &X = exts[si];
+                    guessed = undistort_pt_ext(S.cam0, X.model[0], X.coef[0], S.R01, c0x, c0y, rx, ry);
+                    if (guessed) guessed = distort_pt_ext(S.cam1, X.model[1], X.coef[1], rx, ry, gx, gy);
+                    if (!guessed) { gx = 0.f; gy = 0.f; }
+                } else {
+                    undistort_pt(S.cam0, S.R01, c0x, c0y, rx, ry);
+                    distort_pt(S.cam1, rx, ry, gx, gy);
+                }
             }
-            tx = c0x; ty = c0y; alive = ok;
+            tx = c0x; ty = c0y; alive = guessed;
         }
         float nx = 0.f, ny = 0.f;
         int st = 0;
@@ -730,8 +697,15 @@ __global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n
     if (ok) {
         const int W1 = S.curr1.w[0], H1 = S.curr1.h[0];
         if (sst && (c1y < 0 || c1y > (float)(H1 - 1) || c1x < 0 || c1x > (float)(W1 - 1))) sst = 0;
-        undistort_pt(S.cam0, nullptr, c0x, c0y, u0x, u0y);
-        undistort_pt(S.cam1, nullptr, c1x, c1y, u1x, u1y);
+        if (EXT) {
+            const FeCamExtDev &X = exts[si];
+            const bool in0 = undistort_pt_ext(S.cam0, X.model[0], X.coef[0], nullptr, c0x, c0y, u0x, u0y);
+            const bool in1 = undistort_pt_ext(S.cam1, X.model[1], X.coef[1], nullptr, c1x, c1y, u1x, u1y);
+            if (!in0 || !in1) sst = 0;
+        } else {
+            undistort_pt(S.cam0, nullptr, c0x, c0y, u0x, u0y);
+            undistort_pt(S.cam1, nullptr, c1x, c1y, u1x, u1y);
+        }
         if (sst) {
             const double *E = S.E;
             const double x0 = (double)u0x, y0 = (double)u0y, x1 = (double)u1x, y1 = (double)u1y;
@@ -755,6 +729,16 @@ __global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n
         S.status[pt] = (uint8_t)(ok ? (1 | (sst ? 2 : 0)) : 0);
     }
     }
+}
+__global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n_streams, int groups_per_stream) {
+    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
+    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
+    track4_body<false>(streams, nullptr, n_streams, groups_per_stream, s_T, s_S);
+}
+__global__ __launch_bounds__(64) void k_track4_ext(const FeStreamDev *streams, const FeCamExtDev *exts, int n_streams, int groups_per_stream) {
+    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];      // (each kernel owns its staging: an array two kernels share is laid out by
+    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];      // another rule, and k_track4's code object would no longer be the parent's)
+    track4_body<true>(streams, exts, n_streams, groups_per_stream, s_T, s_S);
 }
 
 // ------------------------------------------------------------------------------------------ bookkeeping (fe_book.h)
@@ -1122,6 +1106,12 @@ extern "C" void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, i
     if (max_pts <= 0) return;
     const int gps = (max_pts + 3) / 4;
     hipLaunchKernelGGL(k_track4, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, n_streams, gps);
+}
+// the extended instantiation over the same grid: cams_dev[i] goes with streams_dev[i]
+extern "C" void fe_launch_track_ext(const FeStreamDev *streams_dev, const FeCamExtDev *cams_dev, int n_streams, int max_pts, hipStream_t st) {
+    if (max_pts <= 0) return;
+    const int gps = (max_pts + 3) / 4;
+    hipLaunchKernelGGL(k_track4_ext, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, cams_dev, n_streams, gps);
 }
 
 // ------------------------------------------------------------------------------------------ image masks: the point gate (fe_mask.h)

@@ -282,6 +282,27 @@ int mskfh_load_fb_check(const char *yaml_path, mskf_fe_fb_check *out) {
         return -1;
     }
 }
+// ImageProcessor::setCameraModel (mskf_fe_set_camera_model) of one stream, or of all (stream < 0); between runs.  As mskfh_runner_set_fb_check.
+int mskfh_runner_set_camera_model(void *h, int stream, const mskf_fe_camera_model *cfg) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setCameraModel(*cfg); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
+// the camera models of a camchain yaml (camera_models_from_yaml): out[2], extended[2]; 0 on success
+int mskfh_load_camera_models(const char *yaml_path, mskf_fe_camera_model *out, int *extended) {
+    try {
+        const YAML::Node n = YAML::LoadFile(yaml_path);
+        (void)calib_from_yaml(n);
+        const CamchainModels m = camera_models_from_yaml(n);
+        for (int c = 0; c < 2; ++c) { out[c] = m.cam[c]; extended[c] = m.extended[c] ? 1 : 0; }
+        return 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "mskfh_load_camera_models: %s\n", e.what());
+        return -1;
+    }
+}
 // ImageProcessor::setDescriptors of one stream, or of all (stream < 0); between runs, from the next frame on
 int mskfh_runner_set_descriptors(void *h, int stream, int on) {
     MultiRunner *r = (MultiRunner *)h;

@@ -15,20 +15,73 @@
 namespace cg {
 
 // config_io.h:13-81 conversions + image_processor.cpp:54-72 / msckf_vio.cpp:115-125 keys
+// One camera of a camchain: the base model, fx fy cx cy and four coefficients for mskf_calib, and the camera's model as
+// mskf_fe_set_camera_model takes it; returns whether that model is an extended one (image_processor.h: camera_models_from_yaml).
+static bool camchain_camera(const YAML::Node &cam, const char *name, int *base_model, double *K, double *D, mskf_fe_camera_model *out) {
+    const std::string who(name);
+    const auto refuse = [&](const std::string &what) -> bool {
+        throw YAML::Exception("yaml: " + who + ": " + what + " (accepted: distortion_model radtan with 4, 5 or 8 distortion_coeffs, equidistant with 4, fov with 1; "
+                              "camera_model ds with intrinsics [xi, alpha, fu, fv, pu, pv] and no distortion)");
+    };
+    const std::string cm = cam["camera_model"].IsDefined() ? cam["camera_model"].as<std::string>() : std::string("pinhole");
+    const std::string dm = cam["distortion_model"].IsDefined() ? cam["distortion_model"].as<std::string>() : std::string("none");
+    std::vector<double> k;
+    if (cam["distortion_coeffs"].IsDefined()) k = cam["distortion_coeffs"].as<std::vector<double>>();
+    const std::vector<double> in = cam["intrinsics"].as<std::vector<double>>();
+    std::memset(out, 0, sizeof(*out));
+    for (int i = 0; i < 4; ++i) D[i] = 0.0;
+    *base_model = MSKF_MODEL_RADTAN;
+    if (cm == "ds") {
+        if (in.size() != 6) refuse("camera_model ds takes six intrinsics");
+        if (dm != "none" || !k.empty()) refuse("camera_model ds takes no distortion");
+        for (int i = 0; i < 4; ++i) K[i] = in[2 + i];
+        out->model = MSKF_MODEL_DS; out->coeffs[0] = in[0]; out->coeffs[1] = in[1];
+        return true;
+    }
+    if (cm != "pinhole") refuse("unknown camera_model " + cm);
+    if (in.size() != 4) throw YAML::Exception("yaml: wrong length for " + who + ".intrinsics");
+    for (int i = 0; i < 4; ++i) K[i] = in[i];
+    if (dm == "radtan" && (k.size() == 5 || k.size() == 8)) {
+        out->model = MSKF_MODEL_RADTAN8;
+        for (size_t i = 0; i < k.size(); ++i) out->coeffs[i] = k[i];
+        for (int i = 0; i < 4; ++i) D[i] = k[i];
+        return true;
+    }
+    if (dm == "fov" && k.size() == 1) {
+        out->model = MSKF_MODEL_FOV; out->coeffs[0] = k[0];
+        return true;
+    }
+    if ((dm == "radtan" || dm == "equidistant") && k.size() == 4) {
+        *base_model = dm == "radtan" ? MSKF_MODEL_RADTAN : MSKF_MODEL_EQUIDISTANT;
+        out->model = *base_model;
+        for (int i = 0; i < 4; ++i) { D[i] = k[i]; out->coeffs[i] = k[i]; }
+        return false;
+    }
+    if (dm == "radtan" || dm == "equidistant" || dm == "fov") throw YAML::Exception("yaml: wrong length for " + who + ".distortion_coeffs");
+    return refuse("unknown distortion_model " + dm);
+}
+
+CamchainModels camera_models_from_yaml(const YAML::Node &n) {
+    CamchainModels m;
+    int base;
+    double K[4], D[4];
+    m.extended[0] = camchain_camera(n["cam0"], "cam0", &base, K, D, &m.cam[0]);
+    m.extended[1] = camchain_camera(n["cam1"], "cam1", &base, K, D, &m.cam[1]);
+    m.cam[0].cam = 0; m.cam[1].cam = 1;
+    return m;
+}
+
 mskf_calib calib_from_yaml(const YAML::Node &n) {
     mskf_calib c;
     std::memset(&c, 0, sizeof(c));
-    auto model = [](const std::string &s) { return s == "equidistant" ? MSKF_MODEL_EQUIDISTANT : MSKF_MODEL_RADTAN; };
     auto copy = [](const std::vector<double> &v, double *dst, size_t cnt, const char *what) {
         if (v.size() != cnt) throw YAML::Exception(std::string("yaml: wrong length for ") + what);
         for (size_t i = 0; i < cnt; ++i) dst[i] = v[i];
     };
-    c.cam0_model = model(n["cam0"]["distortion_model"].as<std::string>());
-    c.cam1_model = model(n["cam1"]["distortion_model"].as<std::string>());
-    copy(n["cam0"]["intrinsics"].as<std::vector<double>>(), c.cam0_intrinsics, 4, "cam0.intrinsics");
-    copy(n["cam1"]["intrinsics"].as<std::vector<double>>(), c.cam1_intrinsics, 4, "cam1.intrinsics");
-    copy(n["cam0"]["distortion_coeffs"].as<std::vector<double>>(), c.cam0_distortion, 4, "cam0.distortion_coeffs");
-    copy(n["cam1"]["distortion_coeffs"].as<std::vector<double>>(), c.cam1_distortion, 4, "cam1.distortion_coeffs");
+    // (a camera on an extended model gets fx fy cx cy and a zero radtan here: camera_models_from_yaml has its model)
+    mskf_fe_camera_model ext;
+    camchain_camera(n["cam0"], "cam0", &c.cam0_model, c.cam0_intrinsics, c.cam0_distortion, &ext);
+    camchain_camera(n["cam1"], "cam1", &c.cam1_model, c.cam1_intrinsics, c.cam1_distortion, &ext);
     copy(n["cam0"]["T_cam_imu"].as<std::vector<double>>(), c.T_cam0_imu, 16, "cam0.T_cam_imu");
     copy(n["cam1"]["T_cn_cnm1"].as<std::vector<double>>(), c.T_cam1_cam0, 16, "cam1.T_cn_cnm1");
     copy(n["T_imu_body"].as<std::vector<double>>(), c.T_imu_body, 16, "T_imu_body");
@@ -146,6 +199,27 @@ mskf_fe_fb_check fb_check_from_yaml(const YAML::Node &y) {
     pixels("fb_check_max_error_temporal", c.max_error_temporal);
     pixels("fb_check_max_error_stereo", c.max_error_stereo);
     return c;
+}
+
+int ImageProcessor::setCameraModel(const mskf_fe_camera_model &cfg) {
+    if (!initialized_ || !stream_) {      // deferred, as setFbCheck: initialize() / the stream's creation validates the rest
+        if (cfg.cam != 0 && cfg.cam != 1) { error_ = "mskf_fe_set_camera_model: cam must be 0 or 1"; return MSKF_ERR_INVALID; }
+        cam_kept_.cfg[cfg.cam] = cfg; cam_kept_.on[cfg.cam] = true;
+        return MSKF_OK;
+    }
+    const int rc = mskf_fe_set_camera_model(stream_, &cfg);
+    if (rc != MSKF_OK) fail("mskf_fe_set_camera_model", rc);
+    return rc;
+}
+
+int ImageProcessor::applyKeptCameraModels() {
+    for (int c = 0; c < 2; ++c) {
+        if (!cam_kept_.on[c]) continue;
+        const int rc = mskf_fe_set_camera_model(stream_, &cam_kept_.cfg[c]);
+        if (rc != MSKF_OK) { fail("mskf_fe_set_camera_model", rc); return rc; }
+        cam_kept_.on[c] = false;
+    }
+    return MSKF_OK;
 }
 
 int ImageProcessor::setFbCheck(const mskf_fe_fb_check &cfg) {
@@ -276,6 +350,8 @@ void ImageProcessor::fail(const char *what, int rc) {
 bool ImageProcessor::loadParameters() {
     if (have_yaml_) {
         calib_ = calib_from_yaml(cfg_cam_imu_);
+        const CamchainModels models = camera_models_from_yaml(cfg_cam_imu_);
+        for (int c = 0; c < 2; ++c) if (models.extended[c]) { cam_kept_.cfg[c] = models.cam[c]; cam_kept_.on[c] = true; }
         YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");   // Q16
         cfg_ = fe_cfg_from_yaml(cfg_imgproc);
         eq_cfg_ = equalize_from_yaml(cfg_imgproc);
@@ -322,6 +398,8 @@ bool ImageProcessor::initialize() {
     if (stream_ && patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
     // ... and the opt-in forward-backward check, likewise
     if (stream_ && fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return false;
+    // ... and the opt-in camera models (setCameraModel before this, or an extended model in the camchain), likewise
+    if (stream_ && applyKeptCameraModels() != MSKF_OK) return false;
     return true;
 }
 
@@ -368,6 +446,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if (applyKeptMask() != MSKF_OK) return;
         if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return;
         if (fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return;
+        if (applyKeptCameraModels() != MSKF_OK) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
     if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {

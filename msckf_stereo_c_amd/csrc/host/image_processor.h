@@ -21,6 +21,16 @@
 namespace cg {
 
 mskf_calib calib_from_yaml(const YAML::Node &cfg_cam_imu);
+// The camera models of a camchain beyond the two of mskf_calib (mskf_fe_set_camera_model), per camera:
+//   distortion_model: radtan with 5 or 8 distortion_coeffs (OpenCV's k1 k2 p1 p2 k3 [k4 k5 k6]) -> radtan8, five padded with zeros
+//                     (4 coefficients stay the base radtan of mskf_calib, 4 of equidistant the base equidistant);
+//   distortion_model: fov with 1 distortion_coeff (w);
+//   camera_model: ds with intrinsics: [xi, alpha, fu, fv, pu, pv] (Kalibr's order) and no distortion (distortion_model absent or
+//                     none, distortion_coeffs absent or empty).
+// extended[c] says whether camera c has one; calib_from_yaml then gives that camera fx fy cx cy and a zero radtan in its place.
+// Anything else throws YAML::Exception with a message that lists what is accepted.
+struct CamchainModels { mskf_fe_camera_model cam[2]; bool extended[2]; };
+CamchainModels camera_models_from_yaml(const YAML::Node &cfg_cam_imu);
 mskf_fe_cfg fe_cfg_from_yaml(const YAML::Node &cfg_imgproc);
 // optional keys of the same file (not keys of the reference): equalize: off | hist | clahe, clahe_clip_limit, clahe_tiles_x,
 // clahe_tiles_y (mskf_fe_set_equalize; absent = off, 40.0, 8, 8).  Throws YAML::Exception on an unknown equalize value.
@@ -131,6 +141,9 @@ class ImageProcessor {
     // opt-in forward-backward check of temporal tracks and stereo matches (mskf_fe_set_fb_check): kept and set like setPatchCheck.
     int setFbCheck(const mskf_fe_fb_check &cfg);
     const mskf_fe_fb_check &fbCheck() const { return fb_cfg_; }
+    // opt-in camera model of one camera (mskf_fe_set_camera_model): kept until the stream exists, then set; a refusal leaves the
+    // previous setting in force.  A camchain with an extended model sets it the same way.
+    int setCameraModel(const mskf_fe_camera_model &cfg);
     // opt-in 256-bit descriptors (mskf_fe_describe_batch; DESIGN.md section 3, "Descriptors") of the features a frame publishes:
     // frame k's cam0 level 0 at the cam0 pixels of the features of frame k's message, in message order.  Off by default; takes
     // effect with the next frame.  descriptorIds() / descriptors() (32 bytes each) / descriptorValid() are those of the last frame.
@@ -236,6 +249,8 @@ class ImageProcessor {
     mskf_fe_input_format px_cfg_{0, 0};
     mskf_fe_patch_check patch_cfg_{0, 4, 0.8f, 0.8f};
     mskf_fe_fb_check fb_cfg_{0, 1.0f, 1.0f};
+    struct CamModelKept { mskf_fe_camera_model cfg[2]; bool on[2] = {false, false}; } cam_kept_;      // setCameraModel before the stream exists
+    int applyKeptCameraModels();
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
     int applyKeptMask();
     bool descriptors_ = false;

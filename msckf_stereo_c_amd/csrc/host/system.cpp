@@ -8,6 +8,7 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
     try {
         cfg_cam_imu_ = YAML::LoadFile(file_cam_imu);
         mskf_calib calib = calib_from_yaml(cfg_cam_imu_);
+        camera_models_ = camera_models_from_yaml(cfg_cam_imu_);
         const YAML::Node cfg_imgproc = YAML::LoadFile("../config/app_imgproc.yaml");
         mskf_fe_cfg fe = fe_cfg_from_yaml(cfg_imgproc);
         equalize_ = equalize_from_yaml(cfg_imgproc);
@@ -49,6 +50,7 @@ void System::setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ek
     imgproc_ptr_->setInputFormat(input_format_);
     imgproc_ptr_->setPatchCheck(patch_check_);
     imgproc_ptr_->setFbCheck(fb_check_);
+    for (int c = 0; c < 2; ++c) if (camera_models_.extended[c]) imgproc_ptr_->setCameraModel(camera_models_.cam[c]);
     imgproc_ptr_->setDescriptors(descriptors_);
     if (!imgproc_ptr_->initialize()) { std::cerr << "Cannot initialize Image Processor..." << std::endl; return; }
     msckfvio_ptr_.reset(new cg::MsckfVio(calib, ekf));

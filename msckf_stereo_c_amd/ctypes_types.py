@@ -126,6 +126,29 @@ FB_CHECK_MODES = {"off": 0, "temporal": 1, "stereo": 2, "both": 3}
 FB_MAX_ERROR = 64.0          # FB_MAX_ERROR (csrc/hip/fe_fb.h)
 
 
+class FeCameraModel(C.Structure):
+    """mskf_fe_camera_model (include/mskf_hip.h): one camera's model and its coefficients (unused ones 0)."""
+    _fields_ = [("cam", C.c_int32), ("model", C.c_int32), ("coeffs", C.c_double * 8)]
+
+
+CAMERA_MODELS = {"radtan": 0, "equidistant": 1, "radtan8": 2, "fov": 3, "ds": 4}      # MSKF_MODEL_*
+CAMERA_MODEL_COEFFS = {0: (4,), 1: (4,), 2: (5, 8), 3: (1,), 4: (2,)}                  # how many coefficients a model may be given
+
+
+def camera_model_cfg(cam, model, coeffs):
+    """FeCameraModel of (cam, model name or number, coefficients): the coefficients are padded with zeros to eight (radtan8 takes
+    OpenCV's five or eight).  Raises ValueError on an unknown model name or a wrong count; the library checks the values."""
+    if isinstance(model, str) and model not in CAMERA_MODELS:
+        raise ValueError("unknown camera model %r (one of %s)" % (model, ", ".join(CAMERA_MODELS)))
+    m = int(CAMERA_MODELS.get(model, model))
+    k = [float(v) for v in coeffs]
+    if m in CAMERA_MODEL_COEFFS and len(k) not in CAMERA_MODEL_COEFFS[m]:
+        raise ValueError("camera model %r takes %s coefficients, not %d" % (model, " or ".join(map(str, CAMERA_MODEL_COEFFS[m])), len(k)))
+    if len(k) > 8:
+        raise ValueError("a camera model takes at most 8 coefficients")
+    return FeCameraModel(int(cam), m, (C.c_double * 8)(*(k + [0.0] * (8 - len(k)))))
+
+
 class FeDescribeArgs(C.Structure):
     """mskf_fe_describe_args (include/mskf_hip.h): n points of the image of `role` in, 32 n descriptor bytes and n validity bytes out."""
     _fields_ = [("role", C.c_int32), ("n", C.c_int32), ("pts", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p)]

@@ -9,7 +9,7 @@ import numpy as np
 
 from .capi import MskfError
 from .ctypes_types import (EQUALIZE_MODES, FEATURE_MEAS, INPUT_FORMATS, ODOM_COV, POINT2F, POSE, Calib, EkfCfg, FeCfg, FeEqualize, FeInputFormat, FeMask,
-                           FB_CHECK_MODES, FeFbCheck, FePatchCheck, ImuSample, PATCH_CHECK_MODES, TrackingInfo, raw_raster)
+                           FB_CHECK_MODES, FeCameraModel, FeFbCheck, FePatchCheck, ImuSample, PATCH_CHECK_MODES, TrackingInfo, camera_model_cfg, raw_raster)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -273,6 +273,20 @@ class Runner:
         cfg = FeFbCheck(int(FB_CHECK_MODES.get(mode, mode)), float(max_error_temporal), float(max_error_stereo))
         self.L.mskfh_runner_set_fb_check.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeFbCheck)]
         rc = self.L.mskfh_runner_set_fb_check(self.h, -1 if stream is None else int(stream), C.byref(cfg))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
+    def set_camera_model(self, cam, model, coeffs, stream=None):
+        """Opt-in camera model of camera `cam` (0 / 1) of one stream or of all (mskf_fe_set_camera_model): "radtan8" (OpenCV's 5 or 8
+        coefficients k1 k2 p1 p2 k3 [k4 k5 k6]), "fov" (w), "ds" (xi, alpha), or "radtan" / "equidistant" with four coefficients,
+        which put the camera back on the base path.  The intrinsics stay the calibration's.  Call between runs."""
+        try:
+            cfg = camera_model_cfg(cam, model, coeffs)
+        except ValueError as e:
+            raise MskfError(str(e), -1)
+        self.L.mskfh_runner_set_camera_model.argtypes = [C.c_void_p, C.c_int, C.POINTER(FeCameraModel)]
+        rc = self.L.mskfh_runner_set_camera_model(self.h, -1 if stream is None else int(stream), C.byref(cfg))
         if rc != 0:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
