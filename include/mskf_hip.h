@@ -51,7 +51,8 @@ int mskf_abi_version(void);   /* 2: update args carry diag_out, mskf_ekf_cfg.com
                                  mskf_fe_verify, _batch, _batch_begin, _batch_end (with their own mskf_fe_verify_args);
                                  mskf_fe_set_patch_check, mskf_fe_get_patch_check (with their own mskf_fe_patch_check) and the alias MSKF_K_FE_PATCH of
                                  the timing slot the mask gate borrowed;
-                                 mskf_fe_set_fb_check, mskf_fe_get_fb_check (with their own mskf_fe_fb_check) and the alias MSKF_K_FE_FB of the same slot */
+                                 mskf_fe_set_fb_check, mskf_fe_get_fb_check (with their own mskf_fe_fb_check) and the alias MSKF_K_FE_FB of the same slot;
+                                 mskf_fe_set_lk_levels, mskf_fe_get_lk_levels and the alias MSKF_K_PYR_DEEP of the same slot */
 
 int mskf_ctx_create(int device, mskf_ctx **out);
 /* Same, with the context's HIP stream created at the device's most urgent priority when high_priority != 0.
@@ -73,7 +74,7 @@ void *mskf_ctx_hip_stream(mskf_ctx *ctx);
 
 /* Optional per-kernel timing with HIP events recorded on the context's own stream (bench / roofline).
  * `units` are the algorithmic work units of a launch (LK: point tracks, temporal + stereo of one track call in one launch — MSKF_K_PT_GEOM
- * is kept for ABI stability, counts no geometry since that moved into that launch, and carries the point gates behind a track launch instead (MSKF_K_FE_MASK, MSKF_K_FE_PATCH, MSKF_K_FE_FB); pyramid: output pixels;
+ * is kept for ABI stability, counts no geometry since that moved into that launch, and carries the point gates behind a track launch instead (MSKF_K_FE_MASK, MSKF_K_FE_PATCH, MSKF_K_FE_FB) and the deep pyramid launch (MSKF_K_PYR_DEEP); pyramid: output pixels;
  * EKF feature / GEMM / Cholesky / TRSM kernels: algorithmic FP64 flops; others: streams).  Disabled by default.
  * `enable` = n > 1 times every n-th launch of each kind only and scales the sums to all launches: two event records per launch cost
  * 7 % of the throughput at the C2 bench shape and 36 % at C5 (one stream per launch), measured.  MSKF_K_EKF_AUGMENT is kept for ABI
@@ -92,7 +93,11 @@ enum {
     MSKF_K_FE_PATCH = MSKF_K_PT_GEOM,
     /* k_fb_points, the point gate of the forward-backward check (mskf_fe_set_fb_check), launched behind a track launch only when a
        stream of that batch checks; units: streams.  The same slot again: with the three features off its counts are exactly as before. */
-    MSKF_K_FE_FB = MSKF_K_PT_GEOM
+    MSKF_K_FE_FB = MSKF_K_PT_GEOM,
+    /* k_pyr_down_deep, the pyramid levels 4 and up of the streams that track over more than four levels (mskf_fe_set_lk_levels), launched
+       behind the pyramid launch of a push only when a stream of that batch is deep; units: output pixels.  The same slot once more (so
+       that MSKF_K_PYR keeps meaning k_pyr_down3): with the four features off its counts are exactly as before. */
+    MSKF_K_PYR_DEEP = MSKF_K_PT_GEOM
 };
 int mskf_ctx_set_timing(mskf_ctx *ctx, int enable);
 /* Accounting gate (default on): while it is off, launches are not timed and host seconds not accumulated.  Unlike
@@ -401,7 +406,25 @@ typedef struct mskf_fe_camera_model { int32_t cam, model; double coeffs[8]; } ms
 int mskf_fe_set_camera_model(mskf_stream *s, const mskf_fe_camera_model *cfg);
 int mskf_fe_get_camera_model(mskf_stream *s, int cam, mskf_fe_camera_model *out);      /* a stream never set: what mskf_calib gave it */
 
-/* download pyramid level `level` (0..3) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
+/* ---- opt-in deeper LK pyramids: a stream may run every pyramidal LK over L = 5 .. 8 levels instead of 4, which widens the capture range
+ * of the temporal track, of both stereo matches and of the backward tracks of the forward-backward check ("Deeper LK
+ * pyramids").  4 is the default, and then nothing new runs or is allocated.  Deeper is not better: top levels without structure send the
+ * guess astray, so the depth is a per-stream choice (README has measured counts).
+ *   pyramid   level l (4 <= l < L) is pyr_down of level l - 1, ((w + 1) / 2, (h + 1) / 2), the function that makes the levels 1 .. 3; the
+ *             three pyramids' extra planes live in an arena of the stream's own (3 x sum of w_l h_l bytes, rounded up per level), allocated
+ *             by this call, freed with the stream, rotated by mskf_fe_swap and by the device frame as the levels 0 .. 3 are;
+ *   LK        the arithmetic of the four-level track with 4 replaced by L: sc = 2^-l, the guess scaled once at level L - 1 and doubled per
+ *             level, status 0 set by level 0 only, a level that fails its bounds or minEig test passes the guess on unchanged;
+ *   launches  one more launch (k_pyr_down_deep, MSKF_K_PYR_DEEP) behind the pyramid launch of a push with a deep stream; a track or
+ *             device-frame batch with a deep stream launches k_track4_deep (timed as MSKF_K_LK) in place of k_track4 / k_track4_ext, and
+ *             k_fb_points_deep in place of k_fb_points; the other streams of such a batch get the bits they always got.
+ * mskf_fe_set_lk_levels validates before it touches anything: MSKF_ERR_INVALID for levels outside 4 .. 8, for an L whose level L - 1 has a
+ * side below 15 pixels at the stream's calibrated size (752 x 480 allows up to 6, 3840 x 2160 allows 8; mskf_last_error names the largest L
+ * the size allows), after the stream's first push, and while a track or device-frame batch of the stream's context is pending. */
+int mskf_fe_set_lk_levels(mskf_stream *s, int levels);
+int mskf_fe_get_lk_levels(mskf_stream *s, int *levels);      /* a stream never set: 4 */
+
+/* download pyramid level `level` (0..3; up to L - 1 for a stream with mskf_fe_set_lk_levels(L)) of image role 0: prev cam0, 1: curr cam0, 2: curr cam1 (parity tests) */
 int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h);
 
 /* ---- opt-in 256-bit binary descriptors of points of a resident level-0 image ("Descriptors")

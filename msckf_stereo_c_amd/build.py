@@ -29,6 +29,7 @@ HIP_SRCS = [
     "hip/fe_verify.hip",
     "hip/fe_patch.hip",
     "hip/fe_fb.hip",
+    "hip/fe_deep.hip",
     "abi/mskf_capi_ctx.cpp",
     "abi/mskf_capi_fe.cpp",
     "abi/mskf_capi_kf.cpp",

@@ -65,7 +65,7 @@ EXPORTS = [
     "mskf_fe_set_equalize", "mskf_fe_get_equalize", "mskf_fe_set_input_format", "mskf_fe_get_input_format",
     "mskf_ekf_update_direct", "mskf_ekf_update_direct_batch", "mskf_ekf_update_direct_batch_begin", "mskf_ekf_update_direct_batch_end",
     "mskf_fe_set_mask", "mskf_fe_get_mask", "mskf_fe_set_patch_check", "mskf_fe_get_patch_check",
-    "mskf_fe_set_fb_check", "mskf_fe_get_fb_check", "mskf_fe_set_camera_model", "mskf_fe_get_camera_model",
+    "mskf_fe_set_fb_check", "mskf_fe_get_fb_check", "mskf_fe_set_lk_levels", "mskf_fe_get_lk_levels", "mskf_fe_set_camera_model", "mskf_fe_get_camera_model",
     "mskf_fe_describe", "mskf_fe_describe_batch", "mskf_fe_describe_batch_begin", "mskf_fe_describe_batch_end", "mskf_fe_descriptor_pattern",
     "mskf_fe_match", "mskf_fe_match_batch", "mskf_fe_match_batch_begin", "mskf_fe_match_batch_end",
     "mskf_fe_verify", "mskf_fe_verify_batch", "mskf_fe_verify_batch_begin", "mskf_fe_verify_batch_end",
@@ -685,6 +685,20 @@ class Stream:
         self.L.mskf_fe_get_fb_check.argtypes = [C.c_void_p, C.POINTER(FeFbCheck)]
         _chk(self.L.mskf_fe_get_fb_check(self.h, C.byref(cfg)))
         return cfg.mode, cfg.max_error_temporal, cfg.max_error_stereo
+
+    def set_lk_levels(self, levels):
+        """mskf_fe_set_lk_levels: every pyramidal LK of the stream (temporal track, both stereo matches, the backward tracks of the
+        forward-backward check) runs over `levels` = 4 .. 8 pyramid levels; 4 is the default.  Refused for a depth whose top level
+        has a side below 15 pixels at the stream's size, and after the stream's first push."""
+        self.L.mskf_fe_set_lk_levels.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.mskf_fe_set_lk_levels(self.h, int(levels)))
+
+    def get_lk_levels(self):
+        """The number of LK pyramid levels as the stream holds it (a stream never set: 4)."""
+        n = C.c_int(0)
+        self.L.mskf_fe_get_lk_levels.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        _chk(self.L.mskf_fe_get_lk_levels(self.h, C.byref(n)))
+        return n.value
 
     def set_camera_model(self, cam, model, coeffs):
         """mskf_fe_set_camera_model: camera `cam` (0 / 1) takes the model "radtan" | "equidistant" (4 coefficients: back on the base

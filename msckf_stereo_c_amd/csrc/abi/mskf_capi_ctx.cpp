@@ -66,6 +66,7 @@ extern "C" void mskf_ctx_destroy(mskf_ctx *c) {
     c->patch_desc.release();
     c->fb_desc.release();
     c->cam_desc.release();
+    c->deep_desc.release(); c->deep_jobs.release();
     c->cell_arena.release(); c->trk_in.release(); c->trk_out.release(); c->upd_in.release(); c->upd_out.release();
     c->jobs.release(); c->eq_jobs.release(); c->px_jobs.release();
     c->book_desc.release(); c->book_out.release(); c->grid_in.release();
@@ -478,6 +479,7 @@ extern "C" void mskf_stream_destroy(mskf_stream *s) {
     if (s->book.mem) (void)hipFree(s->book.mem);
     if (s->eq.mem) (void)hipFree(s->eq.mem);
     if (s->px.raw) (void)hipFree(s->px.raw);
+    if (s->deep.mem) (void)hipFree(s->deep.mem);
     for (int c = 0; c < 2; ++c) if (s->mask.dev[c]) (void)hipFree(s->mask.dev[c]);
     mskf_ekf_stream_free(s);
     auto &v = s->home_ctx->streams;

@@ -308,9 +308,10 @@ static int stage_fb(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy 
 
 // The forward-backward gate behind a track launch over `desc_dev` (the checks staged in fb_desc), behind the other two gates,
 // whose survivors it sees; timed as MSKF_K_FE_FB.
-static void fb_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
+static void fb_gate(mskf_ctx *ctx, bool deep, const FeStreamDev *desc_dev, int n, int max_pts) {
     const int ts = mskf_t_begin(ctx, MSKF_K_FE_FB);
-    fe_launch_fb_points(desc_dev, ctx->fb_desc.d, n, max_pts, ctx->stream);
+    if (deep) fe_launch_fb_points_deep(desc_dev, ctx->fb_desc.d, ctx->deep_desc.d, n, max_pts, ctx->stream);      // (a backward track has its forward track's depth)
+    else fe_launch_fb_points(desc_dev, ctx->fb_desc.d, n, max_pts, ctx->stream);
     mskf_t_end(ctx, ts, n);
 }
 
@@ -346,9 +347,10 @@ extern "C" int mskf_fe_get_camera_model(mskf_stream *s, int cam, mskf_fe_camera_
 }
 
 // The camera models of the streams of a track launch, element for element beside its descriptors: 0 when no stream has an
-// extended model and nothing was touched, else the array is staged in cam_desc and *cp is its copy.
-static int stage_cams(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
-    *any = false;
+// extended model and nothing was touched, else the array is staged in cam_desc and *cp is its copy.  `deep`: the batch has a deep
+// stream, whose instantiation of the track kernel reads the models too, so they are staged whatever they are.
+static int stage_cams(mskf_ctx *ctx, int n, mskf_stream *const *streams, bool deep, MskfCopy *cp, bool *any) {
+    *any = deep;
     for (int i = 0; i < n; ++i) *any = *any || streams[i]->cam_ext.any();
     if (!*any) return MSKF_OK;
     PinnedDev<FeCamExtDev> &A = ctx->cam_desc;
@@ -362,10 +364,76 @@ static int stage_cams(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCop
     return MSKF_OK;
 }
 
-// A track launch over `desc_dev`: k_track4, or its extended instantiation over the models staged in cam_desc.
-static void track_launch(mskf_ctx *ctx, bool extended, const FeStreamDev *desc_dev, int n, int max_pts) {
-    if (extended) fe_launch_track_ext(desc_dev, ctx->cam_desc.d, n, max_pts, ctx->stream);
+// A track launch over `desc_dev`: k_track4, or its extended instantiation over the models staged in cam_desc, or its deep
+// instantiation over those and the levels staged in deep_desc.
+static void track_launch(mskf_ctx *ctx, bool cams_staged, bool deep, const FeStreamDev *desc_dev, int n, int max_pts) {
+    if (deep) fe_launch_track_deep(desc_dev, ctx->cam_desc.d, ctx->deep_desc.d, n, max_pts, ctx->stream);
+    else if (cams_staged) fe_launch_track_ext(desc_dev, ctx->cam_desc.d, n, max_pts, ctx->stream);
     else fe_launch_track(desc_dev, n, max_pts, ctx->stream);
+}
+
+// ---- opt-in deeper LK pyramids (include/mskf_hip.h; the size chain and the validity rule: fe_deep.h, the pyramid kernel: fe_deep.hip)
+static int deep_validate(const mskf_stream *s, int levels) {
+    if (!s) return MSKF_ERR_INVALID;
+    const int bad = fd_validate(s->w, s->h, levels);
+    if (bad == 1) { mskf_set_error("lk levels: must be 4 .. 8"); return MSKF_ERR_INVALID; }
+    if (bad == 2) {
+        mskf_set_error("lk levels: " + std::to_string(levels) + " levels need a top level of at least 15 x 15 pixels; a " + std::to_string(s->w) + " x " +
+                       std::to_string(s->h) + " image allows at most " + std::to_string(fd_max_levels(s->w, s->h)));
+        return MSKF_ERR_INVALID;
+    }
+    if (s->push_gen != 0) { mskf_set_error("lk levels: can be set only before the stream's first push"); return MSKF_ERR_INVALID; }
+    return mskf_refuse_if_owned(s->ctx, MSKF_ARENAS_FE);
+}
+
+extern "C" int mskf_fe_set_lk_levels(mskf_stream *s, int levels) {
+    if (const int rc = deep_validate(s, levels)) return rc;    // no HIP call before this
+    mskf_stream::Deep D;                                       // everything is decided here, the stream changes at the end
+    D.levels = levels;
+    int w = s->lw[MSKF_LEVELS - 1], h = s->lh[MSKF_LEVELS - 1];
+    for (int l = MSKF_LEVELS; l < levels; ++l) {
+        w = fd_half(w); h = fd_half(h);
+        const int k = l - MSKF_LEVELS;
+        D.w[k] = w; D.h[k] = h; D.off[k] = D.plane_bytes;
+        D.plane_bytes += round_up((size_t)w * h, 64);
+    }
+    MSKF_HIPCHK(hipSetDevice(s->ctx->device));
+    if (D.plane_bytes) MSKF_HIPCHK(hipMalloc((void **)&D.mem, 3 * D.plane_bytes));
+    if (const int rc = replace_blocks({s->deep.mem}, {D.mem})) return rc;
+    s->deep = D;
+    return MSKF_OK;
+}
+
+extern "C" int mskf_fe_get_lk_levels(mskf_stream *s, int *levels) {
+    if (!s || !levels) return MSKF_ERR_INVALID;
+    *levels = s->deep.levels;
+    return MSKF_OK;
+}
+
+static void fill_deep_pyr(const mskf_stream *s, int idx, PyrDeepDev &p) {
+    for (int l = MSKF_LEVELS; l < s->deep.levels; ++l) {
+        const int k = l - MSKF_LEVELS;
+        p.lvl[k] = s->deep.level(idx, l); p.w[k] = s->deep.w[k]; p.h[k] = s->deep.h[k];
+    }
+}
+
+// The deeper pyramid levels of the streams of a track launch, element for element beside its descriptors: 0 when no stream is deep
+// and nothing was touched, else the array is staged in deep_desc and *cp is its copy.
+static int stage_deep(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
+    *any = false;
+    for (int i = 0; i < n; ++i) *any = *any || streams[i]->deep.any();
+    if (!*any) return MSKF_OK;
+    PinnedDev<FeDeepDev> &A = ctx->deep_desc;
+    if (const int rc = A.ensure(n)) return rc;
+    for (int i = 0; i < n; ++i) {
+        const mskf_stream *s = streams[i];
+        FeDeepDev &d = A.h[i];
+        std::memset(&d, 0, sizeof(d));
+        d.levels = s->deep.levels;
+        fill_deep_pyr(s, s->i_prev0, d.prev0); fill_deep_pyr(s, s->i_curr0, d.curr0); fill_deep_pyr(s, s->i_curr1, d.curr1);
+    }
+    *cp = MskfCopy{A.d, A.h, sizeof(FeDeepDev) * (size_t)n};
+    return MSKF_OK;
 }
 
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
@@ -442,6 +510,10 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     int n_px = 0;
     for (int i = 0; i < n; ++i) n_px += streams[i]->px.raw ? 2 : 0;
     if (n_px && (rc = ctx->px_jobs.ensure((size_t)n_px)) != MSKF_OK) return rc;
+    // ... and the streams that track over more than four levels (mskf_fe_set_lk_levels): the same holds
+    int n_deep = 0;
+    for (int i = 0; i < n; ++i) n_deep += streams[i]->deep.any() ? 2 : 0;
+    if (n_deep && (rc = ctx->deep_jobs.ensure((size_t)n_deep)) != MSKF_OK) return rc;
     // ... and the streams with a cam0 mask (mskf_fe_set_mask): the same holds
     MskfCopy mask_cp{};
     bool masked = false;
@@ -514,6 +586,31 @@ static int push_accepted(mskf_ctx *ctx, int n, mskf_stream *const *streams, cons
     int ts = mskf_t_begin(ctx, MSKF_K_PYR);
     fe_launch_pyr_down3(ctx->jobs.d, 2 * n, P.max_w, P.max_h, st);
     mskf_t_end(ctx, ts, P.px_pyr);
+    if (n_deep) {
+        // the levels 4 and up of the deep streams' images, from the level 3 that launch has just written (fe_deep.hip)
+        long long px_deep = 0;
+        int k = 0;
+        for (int i = 0; i < n; ++i) {
+            const mskf_stream *s = streams[i];
+            if (!s->deep.any()) continue;
+            for (int c = 0; c < 2; ++c) {
+                const int pi = pyr_of_role(s, 1 + c);
+                DeepPyrJob &j = ctx->deep_jobs.h[k++];
+                std::memset(&j, 0, sizeof(j));
+                j.src = s->pyr[pi] + s->lvl_off[MSKF_LEVELS - 1];
+                j.w = s->lw[MSKF_LEVELS - 1]; j.h = s->lh[MSKF_LEVELS - 1]; j.levels = s->deep.levels;
+                for (int l = MSKF_LEVELS; l < s->deep.levels; ++l) {
+                    j.dst[l - MSKF_LEVELS] = s->deep.level(pi, l);
+                    px_deep += (long long)s->deep.w[l - MSKF_LEVELS] * s->deep.h[l - MSKF_LEVELS];
+                }
+            }
+        }
+        const MskfCopy dcp = {ctx->deep_jobs.d, ctx->deep_jobs.h, sizeof(DeepPyrJob) * (size_t)n_deep};
+        if ((rc = mskf_copy_async(ctx, &dcp, 1)) != MSKF_OK) return rc;
+        ts = mskf_t_begin(ctx, MSKF_K_PYR_DEEP);
+        fe_launch_pyr_down_deep(ctx->deep_jobs.d, n_deep, st);
+        mskf_t_end(ctx, ts, px_deep);
+    }
     // detector per-cell maxima on cam0 level 0.  The keys carry the push generation in their top byte: a newer push wins every
     // atomicMax, so the key array is cleared only when it is fresh or the 8-bit generation wraps (not once per frame)
     const unsigned int gen = push_gen_tag(ctx->push_gen);
@@ -699,9 +796,12 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy fb_cp{};
     bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
     if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
+    MskfCopy deep_cp{};
+    bool deep = false;                      // ... or more than four LK levels: the deep instantiations of the track kernel and of that gate run
+    if ((rc = stage_deep(ctx, n, streams, &deep_cp, &deep)) != MSKF_OK) return rc;
     MskfCopy cam_cp{};
-    bool extended = false;                  // ... or an extended camera model: the extended instantiation of the track kernel runs
-    if ((rc = stage_cams(ctx, n, streams, &cam_cp, &extended)) != MSKF_OK) return rc;
+    bool cams_staged = false;               // ... or an extended camera model (or a deep stream): the camera models ride along, the extended instantiation runs
+    if ((rc = stage_cams(ctx, n, streams, deep, &cam_cp, &cams_staged)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -717,22 +817,23 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    MskfCopy cp[MSKF_COPY_SEGS] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
+    MskfCopy cp[MSKF_COPY_SEGS + 1] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
     int n_cp = 2;
     if (masked) cp[n_cp++] = mask_cp;
     if (checked) cp[n_cp++] = patch_cp;
     if (fb_checked) cp[n_cp++] = fb_cp;
-    if (extended) cp[n_cp++] = cam_cp;
+    if (cams_staged) cp[n_cp++] = cam_cp;
+    if (deep) cp[n_cp++] = deep_cp;          // (a seventh segment goes in a second copy launch: mskf_copy_async)
     mskf_ctx::PendingTrack &T = ctx->pend_trk;
     T.n = n; T.args = args;
     rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] {
         // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
         T.ts = mskf_t_begin(ctx, MSKF_K_LK);
-        track_launch(ctx, extended, ctx->desc[1].d, n, max_pts);
+        track_launch(ctx, cams_staged, deep, ctx->desc[1].d, n, max_pts);
         mskf_t_end(ctx, T.ts, 0);
         if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
         if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_pts);
-        if (fb_checked) fb_gate(ctx, ctx->desc[1].d, n, max_pts);
+        if (fb_checked) fb_gate(ctx, deep, ctx->desc[1].d, n, max_pts);
     }, MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
     if (rc != MSKF_OK) return rc;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
@@ -880,9 +981,12 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     MskfCopy fb_cp{};
     bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
     if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
+    MskfCopy deep_cp{};
+    bool deep = false;                      // ... or more than four LK levels: both track launches and that gate run their deep instantiations
+    if ((rc = stage_deep(ctx, n, streams, &deep_cp, &deep)) != MSKF_OK) return rc;
     MskfCopy cam_cp{};
-    bool extended = false;                  // ... or an extended camera model: both track launches run the extended instantiation
-    if ((rc = stage_cams(ctx, n, streams, &cam_cp, &extended)) != MSKF_OK) return rc;
+    bool cams_staged = false;               // ... or an extended camera model (or a deep stream): the camera models ride along, both launches run the extended instantiation
+    if ((rc = stage_cams(ctx, n, streams, deep, &cam_cp, &cams_staged)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -920,23 +1024,24 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         if (checked) cp[n_cp++] = patch_cp;
         if (fb_checked) cp[n_cp++] = fb_cp;
         if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
-        if (extended && (rc = mskf_copy_async(ctx, &cam_cp, 1)) != MSKF_OK) return rc;      // (a copy of its own: cp may already hold MSKF_COPY_SEGS segments)
+        if (cams_staged && (rc = mskf_copy_async(ctx, &cam_cp, 1)) != MSKF_OK) return rc;      // (a copy of its own: cp may already hold MSKF_COPY_SEGS segments)
+        if (deep && (rc = mskf_copy_async(ctx, &deep_cp, 1)) != MSKF_OK) return rc;
     }
     const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
-    track_launch(ctx, extended, ctx->desc[1].d, n, max_prev);
+    track_launch(ctx, cams_staged, deep, ctx->desc[1].d, n, max_prev);
     mskf_t_end(ctx, ts1, 0);
     if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
     if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_prev);
-    if (fb_checked) fb_gate(ctx, ctx->desc[1].d, n, max_prev);
+    if (fb_checked) fb_gate(ctx, deep, ctx->desc[1].d, n, max_prev);
     int tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
     const int ts2 = mskf_t_begin(ctx, MSKF_K_LK);
-    track_launch(ctx, extended, ctx->desc[2].d, n, std::max(max_cand_est, 4));
+    track_launch(ctx, cams_staged, deep, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     mskf_t_end(ctx, ts2, 0);
     if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     if (checked) patch_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
-    if (fb_checked) fb_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
+    if (fb_checked) fb_gate(ctx, deep, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 1, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
@@ -995,15 +1100,17 @@ extern "C" int mskf_fe_frame_batch_end(mskf_ctx *ctx) {
 }
 
 extern "C" int mskf_fe_get_level(mskf_stream *s, int role, int level, uint8_t *out, int capacity, int *w, int *h) {
-    if (!s || !out || role < 0 || role > 2 || level < 0 || level >= MSKF_LEVELS) return MSKF_ERR_INVALID;
+    if (!s || !out || role < 0 || role > 2 || level < 0 || level >= s->deep.levels) return MSKF_ERR_INVALID;      // (4 unless mskf_fe_set_lk_levels)
     const int idx = pyr_of_role(s, role);
-    const size_t bytes = (size_t)s->lw[level] * s->lh[level];
+    const bool hi = level >= MSKF_LEVELS;
+    const int lw = hi ? s->deep.w[level - MSKF_LEVELS] : s->lw[level], lh = hi ? s->deep.h[level - MSKF_LEVELS] : s->lh[level];
+    const size_t bytes = (size_t)lw * lh;
     if ((size_t)capacity < bytes) return MSKF_ERR_CAPACITY;
     MSKF_HIPCHK(hipSetDevice(s->ctx->device));
     MSKF_HIPCHK(hipStreamSynchronize(s->ctx->stream));
-    const uint8_t *src = level == 0 ? level0(s, idx) : s->pyr[idx] + s->lvl_off[level];
+    const uint8_t *src = level == 0 ? level0(s, idx) : hi ? s->deep.level(idx, level) : s->pyr[idx] + s->lvl_off[level];
     MSKF_HIPCHK(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    if (w) *w = s->lw[level];
-    if (h) *h = s->lh[level];
+    if (w) *w = lw;
+    if (h) *h = lh;
     return MSKF_OK;
 }

@@ -13,6 +13,7 @@
 #include "../hip/fe_patch.h"
 #include "../hip/fe_fb.h"
 #include "../hip/fe_cam_models.h"
+#include "../hip/fe_deep.h"
 #include "../hip/fe_brief.h"
 #include "../hip/fe_match.h"
 #include "../hip/fe_verify.h"
@@ -31,6 +32,11 @@ void fe_launch_detect(const FeStreamDev *streams_dev, int n_streams, int max_w, 
 void fe_launch_track(const FeStreamDev *streams_dev, int n_streams, int max_pts, hipStream_t st);
 // extended camera models (fe_cam_models.h): cams_dev[i] goes with streams_dev[i]; the extended instantiation of the track kernel
 void fe_launch_track_ext(const FeStreamDev *streams_dev, const FeCamExtDev *cams_dev, int n_streams, int max_pts, hipStream_t st);
+// deeper LK pyramids (fe_deep.h): the levels 4 and up of the deep streams' images behind fe_launch_pyr_down3; the deep instantiations of
+// the track kernel and of the forward-backward gate, deep_dev[i] beside streams_dev[i]
+void fe_launch_pyr_down_deep(const DeepPyrJob *jobs_dev, int n_jobs, hipStream_t st);
+void fe_launch_track_deep(const FeStreamDev *streams_dev, const FeCamExtDev *cams_dev, const FeDeepDev *deep_dev, int n_streams, int max_pts, hipStream_t st);
+void fe_launch_fb_points_deep(const FeStreamDev *streams_dev, const FeFbDev *fb_dev, const FeDeepDev *deep_dev, int n_streams, int max_pts, hipStream_t st);
 // image masks (fe_mask.h): masks_dev[i] goes with streams_dev[i]
 void fe_launch_detect_masked(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_w, int max_h, unsigned int gen, hipStream_t st);
 void fe_launch_mask_points(const FeStreamDev *streams_dev, const FeMaskDev *masks_dev, int n_streams, int max_pts, hipStream_t st);
@@ -141,7 +147,7 @@ struct StagedBatch : PendingBatch {
 };
 
 // Which pending batch owns which arenas of the context (mskf_ctx::pending lists the records):
-//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, cam_desc, jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
+//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, cam_desc, deep_desc, jobs, deep_jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
 //   pend_upd               ekf_desc, upd_in, upd_out (a feature update or a direct update: one record for both kinds);
 //   pend_ro                pred_arena, whose host side its kernel reads and writes (position variances or odometry covariance: one record);
 //   pend_dsc, pend_mch,    the jobs / in / out arenas inside the record itself (StagedBatch), which nothing else touches: only a call
@@ -197,6 +203,8 @@ struct mskf_ctx {
     PinnedDev<FePatchDev> patch_desc;    // the streams' patch checks, element for element beside desc[1] / desc[2]; empty until a stream checks
     PinnedDev<FeFbDev> fb_desc;          // the streams' forward-backward checks, likewise
     PinnedDev<FeCamExtDev> cam_desc;     // the streams' camera models, likewise; empty until a stream has an extended model
+    PinnedDev<FeDeepDev> deep_desc;      // the streams' deeper pyramid levels, likewise; empty until a stream tracks over more than four levels
+    PinnedDev<DeepPyrJob> deep_jobs;     // the deep streams' images of a push (a front-end arena like jobs; empty likewise)
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid
     PinnedDev<char> grid_in;          // staging of mskf_fe_set_grid (synchronous: no batch owns it)
@@ -347,6 +355,17 @@ struct mskf_stream {
         double coef[2][FCM_COEFFS] = {{0}, {0}};
         bool any() const { return model[0] >= FCM_RADTAN8 || model[1] >= FCM_RADTAN8; }
     } cam_ext;
+    // ---- opt-in deeper LK pyramids (mskf_fe_set_lk_levels; fe_deep.h): the levels 4 .. levels - 1 of the three pyramids in an arena of
+    // its own, pyramid i's planes at mem + i * plane_bytes (the roles rotate with i_prev0 / i_curr0 as the levels 0 .. 3 do)
+    struct Deep {
+        int levels = FD_BASE_LEVELS;
+        uint8_t *mem = nullptr;
+        int w[FD_EXTRA] = {0, 0, 0, 0}, h[FD_EXTRA] = {0, 0, 0, 0};
+        size_t off[FD_EXTRA] = {0, 0, 0, 0};       // of level 4 + k inside a pyramid's planes
+        size_t plane_bytes = 0;
+        bool any() const { return levels > FD_BASE_LEVELS; }
+        uint8_t *level(int pyr_idx, int l) const { return mem + (size_t)pyr_idx * plane_bytes + off[l - FD_BASE_LEVELS]; }
+    } deep;
     // ---- device-side bookkeeping (fe_book.h): grids, candidate lists and track results of the stream, one allocation
     struct Book {
         char *mem = nullptr;

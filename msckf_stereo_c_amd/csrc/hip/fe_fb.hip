@@ -20,7 +20,12 @@
 // `alive` = this row's point needs this trip's comparison; a trip no row of the wave needs is skipped, and only the results of
 // alive rows are used.  Whatever the wave branches on around l4_track (which holds workgroup barriers) is uniform in the wave.
 // Lane 0 of a row writes, and only what changes.
-__global__ __launch_bounds__(64) void k_fb_points(const FeStreamDev *streams, const FeFbDev *fb, int n_streams, int groups_per_stream) {
+// The body is written once: k_fb_points is the DEEP = false instantiation; k_fb_points_deep (opt-in deeper LK pyramids, fe_deep.h)
+// runs behind k_track4_deep, so that a backward track has its forward track's depth.  Each kernel owns its staging, as the track
+// kernels do.
+template <bool DEEP>
+__device__ __forceinline__ void fb_body(const FeStreamDev *streams, const FeFbDev *fb, const FeDeepDev *deeps, int n_streams, int groups_per_stream,
+                                        uint32_t (*s_T)[L4_TROWS * L4_DW + 2], uint32_t (*s_S)[L4_SROWS * L4_DW + 4]) {
     const int x = blockIdx.x & 7, qb = blockIdx.x >> 3;
     const int si = x + 8 * (qb / groups_per_stream), gi = qb - (qb / groups_per_stream) * groups_per_stream;
     if (si >= n_streams) return;
@@ -29,8 +34,6 @@ __global__ __launch_bounds__(64) void k_fb_points(const FeStreamDev *streams, co
     const FeStreamDev &S = streams[si];
     const int n_pts = S.n_pts_dev ? *S.n_pts_dev : S.n_pts;
     const int lane = threadIdx.x & 63, g = lane >> 4, r = lane & 15;
-    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
-    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
     uint32_t *sT = s_T[g], *sS = s_S[g];
     const bool temporal = (F.mode & FB_TEMPORAL) && S.do_temporal, stereo = (F.mode & FB_STEREO) != 0;
 #pragma nounroll
@@ -54,7 +57,13 @@ __global__ __launch_bounds__(64) void k_fb_points(const FeStreamDev *streams, co
             float bx = 0.f, by = 0.f;
             int bst = 0;
             unsigned int dbg_iters = 0;
-            if (__any(alive)) l4_track(ph ? S.curr1 : S.curr0, ph ? S.curr0 : S.prev0, alive, tx, ty, ox, oy, sT, sS, r, bx, by, bst, dbg_iters);
+            if (__any(alive)) {
+                if (DEEP) {
+                    const FeDeepDev &P = deeps[si];
+                    l4_track<true>(ph ? S.curr1 : S.curr0, ph ? S.curr0 : S.prev0, alive, tx, ty, ox, oy, sT, sS, r, bx, by, bst, dbg_iters,
+                                   ph ? &P.curr1 : &P.curr0, ph ? &P.curr0 : &P.prev0, P.levels);
+                } else l4_track(ph ? S.curr1 : S.curr0, ph ? S.curr0 : S.prev0, alive, tx, ty, ox, oy, sT, sS, r, bx, by, bst, dbg_iters);
+            }
             if (alive && !fb_pass(bx, by, ox, oy, bst, ph ? F.thr2_s : F.thr2_t)) {
                 if (ph == 0) { ns = 0; lost = true; }
                 else ns &= ~2;
@@ -69,9 +78,26 @@ __global__ __launch_bounds__(64) void k_fb_points(const FeStreamDev *streams, co
     }
 }
 
+__global__ __launch_bounds__(64) void k_fb_points(const FeStreamDev *streams, const FeFbDev *fb, int n_streams, int groups_per_stream) {
+    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
+    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
+    fb_body<false>(streams, fb, nullptr, n_streams, groups_per_stream, s_T, s_S);
+}
+__global__ __launch_bounds__(64) void k_fb_points_deep(const FeStreamDev *streams, const FeFbDev *fb, const FeDeepDev *deeps, int n_streams, int groups_per_stream) {
+    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
+    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
+    fb_body<true>(streams, fb, deeps, n_streams, groups_per_stream, s_T, s_S);
+}
+
 // fb_dev[i] goes with streams_dev[i] (mode 0 = that stream is not checked); the grid of fe_launch_track
 extern "C" void fe_launch_fb_points(const FeStreamDev *streams_dev, const FeFbDev *fb_dev, int n_streams, int max_pts, hipStream_t st) {
     if (max_pts <= 0 || n_streams <= 0 || !fb_dev) return;
     const int gps = (max_pts + 3) / 4;
     hipLaunchKernelGGL(k_fb_points, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, fb_dev, n_streams, gps);
+}
+// the deep instantiation over the same grid: deep_dev[i] goes with streams_dev[i] too
+extern "C" void fe_launch_fb_points_deep(const FeStreamDev *streams_dev, const FeFbDev *fb_dev, const FeDeepDev *deep_dev, int n_streams, int max_pts, hipStream_t st) {
+    if (max_pts <= 0 || n_streams <= 0 || !fb_dev || !deep_dev) return;
+    const int gps = (max_pts + 3) / 4;
+    hipLaunchKernelGGL(k_fb_points_deep, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, fb_dev, deep_dev, n_streams, gps);
 }

@@ -7,6 +7,8 @@
 //                   the epipolar gate (:587-617): one launch per track call, four points per wavefront.
 //  k_track4_ext   : — (opt-in camera models radtan8 / fov / ds, fe_cam_models.h): the second instantiation of k_track4's body,
 //                   launched in its place for a batch in which a stream has an extended model.
+//  k_track4_deep  : — (opt-in deeper LK pyramids, fe_deep.h): the third instantiation, launched for a batch in which a stream
+//                   tracks over more than four levels; the extra levels come from k_pyr_down_deep (fe_deep.hip).
 //  k_mask_points  : — (opt-in image masks, fe_mask.h): the point gate behind a track launch; k_detect_cells<true> is the
 //                   detector of a push that has a masked stream.
 //
@@ -620,8 +622,11 @@ __device__ __forceinline__ bool distort_pt_ext(const CamDev &cam, int model, con
 // a batch in which a stream has an extended model).  Under EXT a point outside a model's domain takes no stereo trip (out1 = 0,
 // stereo status 0) when its guess cannot be formed, and loses status bit 1 when und0 or und1 cannot; what could not be computed
 // is written as 0.
-template <bool EXT>
-__device__ __forceinline__ void track4_body(const FeStreamDev *streams, const FeCamExtDev *exts, int n_streams, int groups_per_stream,
+// A third instantiation, k_track4_deep (EXT = DEEP = true; opt-in deeper LK pyramids, fe_deep.h), is launched only for a batch in
+// which a stream tracks over more than four levels: every l4_track of a stream then starts at that stream's top level
+// (FeDeepDev::levels; 4 for the other streams of the batch, which get the bits they always got).
+template <bool EXT, bool DEEP>
+__device__ __forceinline__ void track4_body(const FeStreamDev *streams, const FeCamExtDev *exts, const FeDeepDev *deeps, int n_streams, int groups_per_stream,
                                             uint32_t (*s_T)[L4_TROWS * L4_DW + 2], uint32_t (*s_S)[L4_SROWS * L4_DW + 4]) {
     const int x = blockIdx.x & 7, qb = blockIdx.x >> 3;
     const int si = x + 8 * (qb / groups_per_stream), gi = qb - (qb / groups_per_stream) * groups_per_stream;
@@ -680,7 +685,13 @@ __device__ __forceinline__ void track4_body(const FeStreamDev *streams, const Fe
         }
         float nx = 0.f, ny = 0.f;
         int st = 0;
-        if (__any(alive)) l4_track(ph ? S.curr0 : S.prev0, ph ? S.curr1 : S.curr0, alive, tx, ty, gx, gy, sT, sS, r, nx, ny, st, dbg_iters);
+        if (__any(alive)) {
+            if (DEEP) {
+                const FeDeepDev &P = deeps[si];
+                l4_track<true>(ph ? S.curr0 : S.prev0, ph ? S.curr1 : S.curr0, alive, tx, ty, gx, gy, sT, sS, r, nx, ny, st, dbg_iters,
+                               ph ? &P.curr0 : &P.prev0, ph ? &P.curr1 : &P.curr0, P.levels);
+            } else l4_track(ph ? S.curr0 : S.prev0, ph ? S.curr1 : S.curr0, alive, tx, ty, gx, gy, sT, sS, r, nx, ny, st, dbg_iters);
+        }
         if (ph == 0) {
             // temporal result and its image-bounds gate (:416-424)
             const int W = S.curr0.w[0], H = S.curr0.h[0];
@@ -733,12 +744,17 @@ __device__ __forceinline__ void track4_body(const FeStreamDev *streams, const Fe
 __global__ __launch_bounds__(64) void k_track4(const FeStreamDev *streams, int n_streams, int groups_per_stream) {
     __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
     __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
-    track4_body<false>(streams, nullptr, n_streams, groups_per_stream, s_T, s_S);
+    track4_body<false, false>(streams, nullptr, nullptr, n_streams, groups_per_stream, s_T, s_S);
 }
 __global__ __launch_bounds__(64) void k_track4_ext(const FeStreamDev *streams, const FeCamExtDev *exts, int n_streams, int groups_per_stream) {
     __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];      // (each kernel owns its staging: an array two kernels share is laid out by
     __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];      // another rule, and k_track4's code object would no longer be the parent's)
-    track4_body<true>(streams, exts, n_streams, groups_per_stream, s_T, s_S);
+    track4_body<true, false>(streams, exts, nullptr, n_streams, groups_per_stream, s_T, s_S);
+}
+__global__ __launch_bounds__(64) void k_track4_deep(const FeStreamDev *streams, const FeCamExtDev *exts, const FeDeepDev *deeps, int n_streams, int groups_per_stream) {
+    __shared__ uint32_t s_T[4][L4_TROWS * L4_DW + 2];
+    __shared__ uint32_t s_S[4][L4_SROWS * L4_DW + 4];
+    track4_body<true, true>(streams, exts, deeps, n_streams, groups_per_stream, s_T, s_S);
 }
 
 // ------------------------------------------------------------------------------------------ bookkeeping (fe_book.h)
@@ -1112,6 +1128,12 @@ extern "C" void fe_launch_track_ext(const FeStreamDev *streams_dev, const FeCamE
     if (max_pts <= 0) return;
     const int gps = (max_pts + 3) / 4;
     hipLaunchKernelGGL(k_track4_ext, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, cams_dev, n_streams, gps);
+}
+// the deep instantiation over the same grid: cams_dev[i] and deep_dev[i] go with streams_dev[i]
+extern "C" void fe_launch_track_deep(const FeStreamDev *streams_dev, const FeCamExtDev *cams_dev, const FeDeepDev *deep_dev, int n_streams, int max_pts, hipStream_t st) {
+    if (max_pts <= 0) return;
+    const int gps = (max_pts + 3) / 4;
+    hipLaunchKernelGGL(k_track4_deep, dim3(8 * ((n_streams + 7) / 8) * gps), dim3(64), 0, st, streams_dev, cams_dev, deep_dev, n_streams, gps);
 }
 
 // ------------------------------------------------------------------------------------------ image masks: the point gate (fe_mask.h)

@@ -1,11 +1,13 @@
 // fe_lk.h — the pyramidal-LK device code of the front-end: l4_track (four points per wavefront, a 16-lane row per point, DPP row
 // sums, LDS staging) with everything it is made of.  ONE source for the two kernels that track: k_track4 (fe_kernels.hip) and
 // k_fb_points (fe_fb.hip, the forward-backward check), so that a backward track is the forward track's arithmetic by
-// construction.  Device code only (PyrDev and MSKF_LEVELS come from fe_device.h).
+// construction.  Device code only (PyrDev and MSKF_LEVELS come from fe_device.h, the deeper levels of an opt-in stream from
+// fe_deep.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "fe_device.h"
+#include "fe_deep.h"
 
 // ------------------------------------------------------------------------------------------ LK
 #define LK_HALF 7
@@ -185,18 +187,27 @@ __device__ __forceinline__ void l4_weights(float fa, float fb, int &wtop, int &w
 // from the initial guess (bx, by), both in level-0 pixels.  Every lane of the wavefront calls it (it stages through LDS and
 // uses the workgroup barrier of the one-wave workgroup); `alive` marks the 16-lane rows that carry a point.  Returns the
 // tracked position and the OpenCV status (0: lost).
+// DEEP (opt-in deeper pyramids, fe_deep.h): the walk starts at level `levels` - 1 (4 .. 8, uniform over the workgroup) instead
+// of 3 and takes the levels 4 and up from Ad / Bd; everything a level does is the same code.  DEEP = false is the function as
+// it was: the extra arguments are not looked at.  (Under -DLK_ITER_DBG the iteration counter packs 8 bits per level: it covers
+// the levels 0 .. 3, the iterations of deeper levels are not counted.)
+template <bool DEEP = false>
 __device__ __forceinline__ void l4_track(const PyrDev &A, const PyrDev &B, bool alive, float ax, float ay, float bx, float by,
-                                         uint32_t *sT, uint32_t *sS, int r, float &out_x, float &out_y, int &out_status, unsigned int &dbg_iters) {
+                                         uint32_t *sT, uint32_t *sS, int r, float &out_x, float &out_y, int &out_status, unsigned int &dbg_iters,
+                                         const PyrDeepDev *Ad = nullptr, const PyrDeepDev *Bd = nullptr, int levels = MSKF_LEVELS) {
     int status = 1;
     float ncx = 0.f, ncy = 0.f;
     const bool winrow = r < LK_WIN;                       // lane 15 only feeds the row below window row 14
-    for (int l = MSKF_LEVELS - 1; l >= 0; --l) {
-        const uint8_t *imA = A.lvl[l];
-        const uint8_t *imB = B.lvl[l];
-        const int aw = A.w[l], ah = A.h[l], bw = B.w[l], bh = B.h[l];
+    const int top = DEEP ? levels - 1 : MSKF_LEVELS - 1;
+    for (int l = top; l >= 0; --l) {
+        const bool hi = DEEP && l >= MSKF_LEVELS;
+        const uint8_t *imA = hi ? Ad->lvl[l - MSKF_LEVELS] : A.lvl[l];
+        const uint8_t *imB = hi ? Bd->lvl[l - MSKF_LEVELS] : B.lvl[l];
+        const int aw = hi ? Ad->w[l - MSKF_LEVELS] : A.w[l], ah = hi ? Ad->h[l - MSKF_LEVELS] : A.h[l];
+        const int bw = hi ? Bd->w[l - MSKF_LEVELS] : B.w[l], bh = hi ? Bd->h[l - MSKF_LEVELS] : B.h[l];
         const float sc = __int_as_float((127 - l) << 23);        // 2^-l exactly
         const float pwx = ax * sc - (float)LK_HALF, pwy = ay * sc - (float)LK_HALF;
-        if (l == MSKF_LEVELS - 1) { ncx = bx * sc; ncy = by * sc; }
+        if (l == top) { ncx = bx * sc; ncy = by * sc; }
         else { ncx = ncx * 2.0f; ncy = ncy * 2.0f; }
         int ipx = (int)floorf(pwx), ipy = (int)floorf(pwy);
         bool lvl_on = alive && !(ipx < -LK_WIN || ipx >= aw || ipy < -LK_WIN || ipy >= ah);
@@ -297,7 +308,7 @@ __device__ __forceinline__ void l4_track(const PyrDev &A, const PyrDev &B, bool 
         for (int it = 0; it < LK_ITERS; ++it) {
             if (!__any(run)) break;
 #ifdef LK_ITER_DBG
-            if (run) dbg_iters += 1u << (8 * l);
+            if (run && !hi) dbg_iters += 1u << (8 * l);
 #endif
             int inx = (int)floorf(wx), iny = (int)floorf(wy);
             if (run && (inx < -LK_WIN || inx >= bw || iny < -LK_WIN || iny >= bh)) {

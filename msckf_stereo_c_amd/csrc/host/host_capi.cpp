@@ -282,6 +282,28 @@ int mskfh_load_fb_check(const char *yaml_path, mskf_fe_fb_check *out) {
         return -1;
     }
 }
+// ImageProcessor::setLkLevels (mskf_fe_set_lk_levels) of one stream, or of all (stream < 0); before the streams' first frame.
+int mskfh_runner_set_lk_levels(void *h, int stream, int levels) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setLkLevels(levels); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
+// the optional lk_pyramid_levels key of an app_imgproc.yaml, for a width x height image (lk_levels_from_yaml); 0 on success, and the
+// reason of a refusal is kept, per thread, for mskfh_load_lk_levels_error
+static thread_local std::string g_lk_levels_error;      // (per thread: loaders may run side by side)
+int mskfh_load_lk_levels(const char *yaml_path, int width, int height, int *out) {
+    try {
+        *out = lk_levels_from_yaml(YAML::LoadFile(yaml_path), width, height);
+        return 0;
+    } catch (const std::exception &e) {
+        g_lk_levels_error = e.what();
+        std::fprintf(stderr, "mskfh_load_lk_levels: %s\n", e.what());
+        return -1;
+    }
+}
+const char *mskfh_load_lk_levels_error(void) { return g_lk_levels_error.c_str(); }
 // ImageProcessor::setCameraModel (mskf_fe_set_camera_model) of one stream, or of all (stream < 0); between runs.  As mskfh_runner_set_fb_check.
 int mskfh_runner_set_camera_model(void *h, int stream, const mskf_fe_camera_model *cfg) {
     MultiRunner *r = (MultiRunner *)h;

@@ -3,6 +3,7 @@
 #include "image_processor.h"
 #include "host_prof.h"
 #include "../hip/fe_pixfmt.h"
+#include "../hip/fe_deep.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -201,6 +202,28 @@ mskf_fe_fb_check fb_check_from_yaml(const YAML::Node &y) {
     return c;
 }
 
+int lk_levels_from_yaml(const YAML::Node &y, int width, int height) {
+    if (!y["lk_pyramid_levels"].IsDefined()) return FD_BASE_LEVELS;
+    // (as<int>() reads text that is no number as 0: the text itself is looked at)
+    const std::string v = y["lk_pyramid_levels"].as<std::string>();
+    char *end = nullptr;
+    const long L = std::strtol(v.c_str(), &end, 10);
+    if (end == v.c_str() || *end != '\0' || L < FD_BASE_LEVELS || L > FD_MAX_LEVELS)
+        throw YAML::Exception("yaml: lk_pyramid_levels must be an integer in 4 .. 8, not " + v);
+    if (fd_validate(width, height, (int)L) != 0)
+        throw YAML::Exception("yaml: lk_pyramid_levels " + v + " needs a top level of at least 15 x 15 pixels; a " + std::to_string(width) + " x " +
+                              std::to_string(height) + " image allows at most " + std::to_string(fd_max_levels(width, height)));
+    return (int)L;
+}
+
+int ImageProcessor::setLkLevels(int levels) {
+    if (!initialized_ || !stream_) { lk_levels_ = levels; return MSKF_OK; }      // deferred: initialize() / the stream's creation validates it
+    const int rc = mskf_fe_set_lk_levels(stream_, levels);
+    if (rc != MSKF_OK) { fail("mskf_fe_set_lk_levels", rc); return rc; }   // refused: lkLevels() keeps reporting what the stream holds
+    lk_levels_ = levels;
+    return rc;
+}
+
 int ImageProcessor::setCameraModel(const mskf_fe_camera_model &cfg) {
     if (!initialized_ || !stream_) {      // deferred, as setFbCheck: initialize() / the stream's creation validates the rest
         if (cfg.cam != 0 && cfg.cam != 1) { error_ = "mskf_fe_set_camera_model: cam must be 0 or 1"; return MSKF_ERR_INVALID; }
@@ -358,6 +381,7 @@ bool ImageProcessor::loadParameters() {
         px_cfg_ = input_format_from_yaml(cfg_imgproc);
         patch_cfg_ = patch_check_from_yaml(cfg_imgproc);
         fb_cfg_ = fb_check_from_yaml(cfg_imgproc);
+        lk_levels_ = lk_levels_from_yaml(cfg_imgproc, calib_.width, calib_.height);
         descriptors_ =descriptors_from_yaml(cfg_imgproc);
     }
     processor_config.grid_row = cfg_.grid_row;
@@ -398,6 +422,8 @@ bool ImageProcessor::initialize() {
     if (stream_ && patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
     // ... and the opt-in forward-backward check, likewise
     if (stream_ && fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return false;
+    // ... and the opt-in deeper LK pyramids, likewise
+    if (stream_ && lk_levels_ != FD_BASE_LEVELS && setLkLevels(lk_levels_) != MSKF_OK) return false;
     // ... and the opt-in camera models (setCameraModel before this, or an extended model in the camchain), likewise
     if (stream_ && applyKeptCameraModels() != MSKF_OK) return false;
     return true;
@@ -446,6 +472,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if (applyKeptMask() != MSKF_OK) return;
         if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return;
         if (fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return;
+        if (lk_levels_ != FD_BASE_LEVELS && setLkLevels(lk_levels_) != MSKF_OK) return;
         if (applyKeptCameraModels() != MSKF_OK) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)

@@ -51,6 +51,10 @@ mskf_fe_patch_check patch_check_from_yaml(const YAML::Node &cfg_imgproc);
 // fb_check_max_error_temporal, fb_check_max_error_stereo: level-0 pixels, 0 .. 64 (mskf_fe_set_fb_check; absent = off, 1.0, 1.0).
 // Throws YAML::Exception on an unknown fb_check value.
 mskf_fe_fb_check fb_check_from_yaml(const YAML::Node &cfg_imgproc);
+// ... and the depth of the LK pyramids: lk_pyramid_levels: 4 .. 8 (mskf_fe_set_lk_levels; absent = 4, today's four levels).  The
+// reference's own key pyramid_levels stays inert (Q6).  Throws YAML::Exception on a value that is no integer in 4 .. 8 or that a
+// width x height image does not allow (fe_deep.h has the rule; the message names the largest depth the size allows).
+int lk_levels_from_yaml(const YAML::Node &cfg_imgproc, int width, int height);
 // ... and descriptors: off | brief256 (absent = off): 256-bit binary descriptors of the published features (mskf_fe_describe_batch),
 // with descriptors_out: <file> for their text output (which turns them on).  Throws YAML::Exception on an unknown value.
 bool descriptors_from_yaml(const YAML::Node &cfg_imgproc);
@@ -141,6 +145,9 @@ class ImageProcessor {
     // opt-in forward-backward check of temporal tracks and stereo matches (mskf_fe_set_fb_check): kept and set like setPatchCheck.
     int setFbCheck(const mskf_fe_fb_check &cfg);
     const mskf_fe_fb_check &fbCheck() const { return fb_cfg_; }
+    // opt-in deeper LK pyramids (mskf_fe_set_lk_levels): kept and set like setFbCheck; only before the stream's first push.
+    int setLkLevels(int levels);
+    int lkLevels() const { return lk_levels_; }
     // opt-in camera model of one camera (mskf_fe_set_camera_model): kept until the stream exists, then set; a refusal leaves the
     // previous setting in force.  A camchain with an extended model sets it the same way.
     int setCameraModel(const mskf_fe_camera_model &cfg);
@@ -249,6 +256,7 @@ class ImageProcessor {
     mskf_fe_input_format px_cfg_{0, 0};
     mskf_fe_patch_check patch_cfg_{0, 4, 0.8f, 0.8f};
     mskf_fe_fb_check fb_cfg_{0, 1.0f, 1.0f};
+    int lk_levels_ = 4;
     struct CamModelKept { mskf_fe_camera_model cfg[2]; bool on[2] = {false, false}; } cam_kept_;      // setCameraModel before the stream exists
     int applyKeptCameraModels();
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists

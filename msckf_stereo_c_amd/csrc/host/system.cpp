@@ -16,6 +16,7 @@ System::System(std::string file_cam_imu) : feature_msg_ptr_(new CameraMeasuremen
         mask_files_ = mask_files_from_yaml(cfg_imgproc);
         patch_check_ = patch_check_from_yaml(cfg_imgproc);
         fb_check_ = fb_check_from_yaml(cfg_imgproc);
+        lk_levels_ = lk_levels_from_yaml(cfg_imgproc, calib.width, calib.height);
         descriptors_ = descriptors_from_yaml(cfg_imgproc);
         const YAML::Node cfg_msckfvio = YAML::LoadFile("../config/app_msckfvio.yaml");
         mskf_ekf_cfg ekf = ekf_cfg_from_yaml(cfg_msckfvio);
@@ -50,6 +51,7 @@ void System::setup(const mskf_calib &calib, const mskf_fe_cfg &fe, const mskf_ek
     imgproc_ptr_->setInputFormat(input_format_);
     imgproc_ptr_->setPatchCheck(patch_check_);
     imgproc_ptr_->setFbCheck(fb_check_);
+    imgproc_ptr_->setLkLevels(lk_levels_);
     for (int c = 0; c < 2; ++c) if (camera_models_.extended[c]) imgproc_ptr_->setCameraModel(camera_models_.cam[c]);
     imgproc_ptr_->setDescriptors(descriptors_);
     if (!imgproc_ptr_->initialize()) { std::cerr << "Cannot initialize Image Processor..." << std::endl; return; }

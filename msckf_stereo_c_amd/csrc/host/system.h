@@ -45,6 +45,7 @@ class System {
     MaskFiles mask_files_;
     mskf_fe_patch_check patch_check_{0, 4, 0.8f, 0.8f};  // likewise (patch_check_from_yaml)
     mskf_fe_fb_check fb_check_{0, 1.0f, 1.0f};          // likewise (fb_check_from_yaml)
+    int lk_levels_ = 4;                                 // likewise (lk_levels_from_yaml)
     CamchainModels camera_models_{{}, {false, false}};  // the camchain's extended camera models (camera_models_from_yaml); none by default
     bool descriptors_ = false;                         // likewise (descriptors_from_yaml)
     std::shared_ptr<CameraMeasurement> feature_msg_ptr_;

@@ -277,6 +277,15 @@ class Runner:
             from . import capi
             raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
 
+    def set_lk_levels(self, levels, stream=None):
+        """Opt-in deeper LK pyramids of one stream or of all (mskf_fe_set_lk_levels): every LK of the stream runs over `levels` = 4 .. 8
+        pyramid levels (4: the default).  Deeper reaches further and is not better: see README.  Call before the first frame."""
+        self.L.mskfh_runner_set_lk_levels.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        rc = self.L.mskfh_runner_set_lk_levels(self.h, -1 if stream is None else int(stream), int(levels))
+        if rc != 0:
+            from . import capi
+            raise MskfError("mskf status %d: %s" % (rc, capi.lib().mskf_last_error().decode()), rc)
+
     def set_camera_model(self, cam, model, coeffs, stream=None):
         """Opt-in camera model of camera `cam` (0 / 1) of one stream or of all (mskf_fe_set_camera_model): "radtan8" (OpenCV's 5 or 8
         coefficients k1 k2 p1 p2 k3 [k4 k5 k6]), "fov" (w), "ds" (xi, alpha), or "radtan" / "equidistant" with four coefficients,
