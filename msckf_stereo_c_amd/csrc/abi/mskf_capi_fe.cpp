@@ -199,27 +199,24 @@ extern "C" int mskf_fe_get_mask(mskf_stream *s, int cam, uint8_t *out, int capac
     return MSKF_OK;
 }
 
-// The masks of the streams of a launch, element for element beside its descriptors: 0 when no stream has a mask the launch
-// looks at (cam0_only: the detector) and nothing was touched, else the array is staged in mask_desc[which] and *cp is its copy.
-static int stage_masks(mskf_ctx *ctx, int which, int n, mskf_stream *const *streams, bool cam0_only, MskfCopy *cp, bool *any) {
-    *any = false;
-    for (int i = 0; i < n; ++i) *any = *any || streams[i]->mask.dev[0] || (!cam0_only && streams[i]->mask.dev[1]);
+// One opt-in setting of the streams of a launch, element for element beside its descriptors.  *any comes in as what the caller
+// already knows (false, or true: stage it whatever the streams say) and goes out true when a stream wants(); while it is false
+// nothing is touched, else A is grown to n, fill() writes every stream's element and *cp is the array's staging copy.
+template <typename T, typename Wants, typename Fill>
+static int stage_beside(PinnedDev<T> &A, int n, mskf_stream *const *streams, Wants wants, Fill fill, MskfCopy *cp, bool *any) {
+    for (int i = 0; i < n && !*any; ++i) *any = wants(*streams[i]);
     if (!*any) return MSKF_OK;
-    PinnedDev<FeMaskDev> &A = ctx->mask_desc[which];
     if (const int rc = A.ensure(n)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const mskf_stream *s = streams[i];
-        A.h[i] = FeMaskDev{s->mask.dev[0], cam0_only ? nullptr : s->mask.dev[1], fm_pitch_words(s->w), 0};
-    }
-    *cp = MskfCopy{A.d, A.h, sizeof(FeMaskDev) * (size_t)n};
+    for (int i = 0; i < n; ++i) fill(*streams[i], A.h[i]);
+    *cp = MskfCopy{A.d, A.h, sizeof(T) * (size_t)n};
     return MSKF_OK;
 }
 
-// The point gate behind a track launch over `desc_dev` (the masks staged in mask_desc[1]), timed as MSKF_K_FE_MASK.
-static void mask_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
-    const int ts = mskf_t_begin(ctx, MSKF_K_FE_MASK);
-    fe_launch_mask_points(desc_dev, ctx->mask_desc[1].d, n, max_pts, ctx->stream);
-    mskf_t_end(ctx, ts, n);
+// The masks a launch looks at (cam0_only: the detector of a push, which = 0; else a track pass, which = 1), in mask_desc[which].
+static int stage_masks(mskf_ctx *ctx, int which, int n, mskf_stream *const *streams, bool cam0_only, MskfCopy *cp, bool *any) {
+    return stage_beside(ctx->mask_desc[which], n, streams,
+                        [&](const mskf_stream &s) { return s.mask.dev[0] || (!cam0_only && s.mask.dev[1]); },
+                        [&](const mskf_stream &s, FeMaskDev &d) { d = FeMaskDev{s.mask.dev[0], cam0_only ? nullptr : s.mask.dev[1], fm_pitch_words(s.w), 0}; }, cp, any);
 }
 
 // ---- opt-in ZNCC patch check of tracks and stereo matches (include/mskf_hip.h; arithmetic and the gate: fe_patch.h)
@@ -245,27 +242,10 @@ extern "C" int mskf_fe_get_patch_check(mskf_stream *s, mskf_fe_patch_check *out)
     return MSKF_OK;
 }
 
-// The patch checks of the streams of a track launch, element for element beside its descriptors: 0 when no stream checks and
-// nothing was touched, else the array is staged in patch_desc and *cp is its copy.
-static int stage_patch(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
-    *any = false;
-    for (int i = 0; i < n; ++i) *any = *any || streams[i]->patch.mode != 0;
-    if (!*any) return MSKF_OK;
-    PinnedDev<FePatchDev> &A = ctx->patch_desc;
-    if (const int rc = A.ensure(n)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_patch_check &c = streams[i]->patch;
-        A.h[i] = FePatchDev{fp_thr2(c.min_zncc_temporal), fp_thr2(c.min_zncc_stereo), c.half, c.mode};
-    }
-    *cp = MskfCopy{A.d, A.h, sizeof(FePatchDev) * (size_t)n};
-    return MSKF_OK;
-}
-
-// The patch gate behind a track launch over `desc_dev` (the checks staged in patch_desc), timed as MSKF_K_FE_PATCH.
-static void patch_gate(mskf_ctx *ctx, const FeStreamDev *desc_dev, int n, int max_pts) {
-    const int ts = mskf_t_begin(ctx, MSKF_K_FE_PATCH);
-    fe_launch_patch_points(desc_dev, ctx->patch_desc.d, n, max_pts, ctx->stream);
-    mskf_t_end(ctx, ts, n);
+// A stream's element of patch_desc (the track pass stages it).
+static void patch_fill(const mskf_stream &s, FePatchDev &d) {
+    const mskf_fe_patch_check &c = s.patch;
+    d = FePatchDev{fp_thr2(c.min_zncc_temporal), fp_thr2(c.min_zncc_stereo), c.half, c.mode};
 }
 
 // ---- opt-in forward-backward check of tracks and stereo matches (include/mskf_hip.h; the decision: fe_fb.h, the kernel: fe_fb.hip)
@@ -290,29 +270,10 @@ extern "C" int mskf_fe_get_fb_check(mskf_stream *s, mskf_fe_fb_check *out) {
     return MSKF_OK;
 }
 
-// The forward-backward checks of the streams of a track launch, element for element beside its descriptors: 0 when no stream
-// checks and nothing was touched, else the array is staged in fb_desc and *cp is its copy.
-static int stage_fb(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
-    *any = false;
-    for (int i = 0; i < n; ++i) *any = *any || streams[i]->fb.mode != 0;
-    if (!*any) return MSKF_OK;
-    PinnedDev<FeFbDev> &A = ctx->fb_desc;
-    if (const int rc = A.ensure(n)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const mskf_fe_fb_check &c = streams[i]->fb;
-        A.h[i] = FeFbDev{fb_thr2(c.max_error_temporal), fb_thr2(c.max_error_stereo), c.mode};
-    }
-    *cp = MskfCopy{A.d, A.h, sizeof(FeFbDev) * (size_t)n};
-    return MSKF_OK;
-}
-
-// The forward-backward gate behind a track launch over `desc_dev` (the checks staged in fb_desc), behind the other two gates,
-// whose survivors it sees; timed as MSKF_K_FE_FB.
-static void fb_gate(mskf_ctx *ctx, bool deep, const FeStreamDev *desc_dev, int n, int max_pts) {
-    const int ts = mskf_t_begin(ctx, MSKF_K_FE_FB);
-    if (deep) fe_launch_fb_points_deep(desc_dev, ctx->fb_desc.d, ctx->deep_desc.d, n, max_pts, ctx->stream);      // (a backward track has its forward track's depth)
-    else fe_launch_fb_points(desc_dev, ctx->fb_desc.d, n, max_pts, ctx->stream);
-    mskf_t_end(ctx, ts, n);
+// A stream's element of fb_desc (the track pass stages it).
+static void fb_fill(const mskf_stream &s, FeFbDev &d) {
+    const mskf_fe_fb_check &c = s.fb;
+    d = FeFbDev{fb_thr2(c.max_error_temporal), fb_thr2(c.max_error_stereo), c.mode};
 }
 
 // ---- opt-in camera models (include/mskf_hip.h; arithmetic, domains and the coefficient check: fe_cam_models.h)
@@ -346,30 +307,10 @@ extern "C" int mskf_fe_get_camera_model(mskf_stream *s, int cam, mskf_fe_camera_
     return MSKF_OK;
 }
 
-// The camera models of the streams of a track launch, element for element beside its descriptors: 0 when no stream has an
-// extended model and nothing was touched, else the array is staged in cam_desc and *cp is its copy.  `deep`: the batch has a deep
-// stream, whose instantiation of the track kernel reads the models too, so they are staged whatever they are.
-static int stage_cams(mskf_ctx *ctx, int n, mskf_stream *const *streams, bool deep, MskfCopy *cp, bool *any) {
-    *any = deep;
-    for (int i = 0; i < n; ++i) *any = *any || streams[i]->cam_ext.any();
-    if (!*any) return MSKF_OK;
-    PinnedDev<FeCamExtDev> &A = ctx->cam_desc;
-    if (const int rc = A.ensure(n)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const mskf_stream::CamExt &c = streams[i]->cam_ext;
-        A.h[i].model[0] = c.model[0]; A.h[i].model[1] = c.model[1];
-        std::memcpy(A.h[i].coef, c.coef, sizeof(c.coef));
-    }
-    *cp = MskfCopy{A.d, A.h, sizeof(FeCamExtDev) * (size_t)n};
-    return MSKF_OK;
-}
-
-// A track launch over `desc_dev`: k_track4, or its extended instantiation over the models staged in cam_desc, or its deep
-// instantiation over those and the levels staged in deep_desc.
-static void track_launch(mskf_ctx *ctx, bool cams_staged, bool deep, const FeStreamDev *desc_dev, int n, int max_pts) {
-    if (deep) fe_launch_track_deep(desc_dev, ctx->cam_desc.d, ctx->deep_desc.d, n, max_pts, ctx->stream);
-    else if (cams_staged) fe_launch_track_ext(desc_dev, ctx->cam_desc.d, n, max_pts, ctx->stream);
-    else fe_launch_track(desc_dev, n, max_pts, ctx->stream);
+// A stream's element of cam_desc (the track pass stages it).
+static void cam_fill(const mskf_stream &s, FeCamExtDev &d) {
+    d.model[0] = s.cam_ext.model[0]; d.model[1] = s.cam_ext.model[1];
+    std::memcpy(d.coef, s.cam_ext.coef, sizeof(s.cam_ext.coef));
 }
 
 // ---- opt-in deeper LK pyramids (include/mskf_hip.h; the size chain and the validity rule: fe_deep.h, the pyramid kernel: fe_deep.hip)
@@ -417,23 +358,70 @@ static void fill_deep_pyr(const mskf_stream *s, int idx, PyrDeepDev &p) {
     }
 }
 
-// The deeper pyramid levels of the streams of a track launch, element for element beside its descriptors: 0 when no stream is deep
-// and nothing was touched, else the array is staged in deep_desc and *cp is its copy.
-static int stage_deep(mskf_ctx *ctx, int n, mskf_stream *const *streams, MskfCopy *cp, bool *any) {
-    *any = false;
-    for (int i = 0; i < n; ++i) *any = *any || streams[i]->deep.any();
-    if (!*any) return MSKF_OK;
-    PinnedDev<FeDeepDev> &A = ctx->deep_desc;
-    if (const int rc = A.ensure(n)) return rc;
-    for (int i = 0; i < n; ++i) {
-        const mskf_stream *s = streams[i];
-        FeDeepDev &d = A.h[i];
-        std::memset(&d, 0, sizeof(d));
-        d.levels = s->deep.levels;
-        fill_deep_pyr(s, s->i_prev0, d.prev0); fill_deep_pyr(s, s->i_curr0, d.curr0); fill_deep_pyr(s, s->i_curr1, d.curr1);
-    }
-    *cp = MskfCopy{A.d, A.h, sizeof(FeDeepDev) * (size_t)n};
+// A stream's element of deep_desc (the track pass stages it).
+static void deep_fill(const mskf_stream &s, FeDeepDev &d) {
+    std::memset(&d, 0, sizeof(d));
+    d.levels = s.deep.levels;
+    fill_deep_pyr(&s, s.i_prev0, d.prev0); fill_deep_pyr(&s, s.i_curr0, d.curr0); fill_deep_pyr(&s, s.i_curr1, d.curr1);
+}
+
+// ---- the track pass: a track launch over the descriptors of a batch with everything the streams' opt-in settings add to it.
+// plan_track_pass stages the settings a stream of the batch has, run_track_pass enqueues the kernels; a track batch runs one
+// pass, a device frame two (both over the same staged arrays).  A new per-stream option of the track is a fill function beside
+// its setter, a flag here, a line in the plan and a line in the run.
+struct TrackPass {
+    bool masked = false;             // a stream has an image mask: the mask gate runs
+    bool patch_checked = false;      // ... a patch check: the patch gate runs
+    bool fb_checked = false;         // ... a forward-backward check: its gate runs
+    bool deep = false;               // ... more than four LK levels: the deep instantiations of the track kernel and of that gate run
+    bool cams_staged = false;        // ... an extended camera model, or the pass is deep: the extended instantiation runs (unless deep)
+    static constexpr int kMaxSegs = 5;
+    MskfCopy seg[kMaxSegs];          // the staging copies of what was staged: the caller appends them to its own segments
+    int n_seg = 0;
+};
+
+// No HIP call but the arenas' growth.  With no option on any stream of the batch nothing is touched and no segment is added.
+static int plan_track_pass(mskf_ctx *ctx, int n, mskf_stream *const *streams, TrackPass &P) {
+    int rc;
+    if ((rc = stage_masks(ctx, 1, n, streams, false, &P.seg[P.n_seg], &P.masked)) != MSKF_OK) return rc;
+    P.n_seg += P.masked;
+    if ((rc = stage_beside(ctx->patch_desc, n, streams, [](const mskf_stream &s) { return s.patch.mode != 0; }, patch_fill, &P.seg[P.n_seg], &P.patch_checked)) != MSKF_OK) return rc;
+    P.n_seg += P.patch_checked;
+    if ((rc = stage_beside(ctx->fb_desc, n, streams, [](const mskf_stream &s) { return s.fb.mode != 0; }, fb_fill, &P.seg[P.n_seg], &P.fb_checked)) != MSKF_OK) return rc;
+    P.n_seg += P.fb_checked;
+    if ((rc = stage_beside(ctx->deep_desc, n, streams, [](const mskf_stream &s) { return s.deep.any(); }, deep_fill, &P.seg[P.n_seg], &P.deep)) != MSKF_OK) return rc;
+    P.n_seg += P.deep;
+    // the deep instantiation of the track kernel reads the camera models too: a deep pass stages them whatever they are
+    P.cams_staged = P.deep;
+    if ((rc = stage_beside(ctx->cam_desc, n, streams, [](const mskf_stream &s) { return s.cam_ext.any(); }, cam_fill, &P.seg[P.n_seg], &P.cams_staged)) != MSKF_OK) return rc;
+    P.n_seg += P.cams_staged;
     return MSKF_OK;
+}
+
+// The pass over `desc_dev`: temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion in one launch
+// (k_track4; its extended instantiation over cam_desc; its deep one over cam_desc and deep_desc), timed as MSKF_K_LK with units 0
+// (the _end sets them); then the point gates in the order mask, patch, forward-backward, each over the survivors of those before
+// it and timed under its own kind.  Returns the track launch's timing slot.
+static int run_track_pass(mskf_ctx *ctx, const TrackPass &P, const FeStreamDev *desc_dev, int n, int max_pts) {
+    hipStream_t st = ctx->stream;
+    const int ts = mskf_t_begin(ctx, MSKF_K_LK);
+    if (P.deep) fe_launch_track_deep(desc_dev, ctx->cam_desc.d, ctx->deep_desc.d, n, max_pts, st);
+    else if (P.cams_staged) fe_launch_track_ext(desc_dev, ctx->cam_desc.d, n, max_pts, st);
+    else fe_launch_track(desc_dev, n, max_pts, st);
+    mskf_t_end(ctx, ts, 0);
+    const auto gate = [&](bool on, int kind, auto launch) {
+        if (!on) return;
+        const int t = mskf_t_begin(ctx, kind);
+        launch();
+        mskf_t_end(ctx, t, n);
+    };
+    gate(P.masked, MSKF_K_FE_MASK, [&] { fe_launch_mask_points(desc_dev, ctx->mask_desc[1].d, n, max_pts, st); });
+    gate(P.patch_checked, MSKF_K_FE_PATCH, [&] { fe_launch_patch_points(desc_dev, ctx->patch_desc.d, n, max_pts, st); });
+    gate(P.fb_checked, MSKF_K_FE_FB, [&] {
+        if (P.deep) fe_launch_fb_points_deep(desc_dev, ctx->fb_desc.d, ctx->deep_desc.d, n, max_pts, st);      // (a backward track has its forward track's depth)
+        else fe_launch_fb_points(desc_dev, ctx->fb_desc.d, n, max_pts, st);
+    });
+    return ts;
 }
 
 // What a push may ask of the raw images of a stream beyond "not null" (no HIP call): rows of at least w * bpp bytes, and
@@ -787,21 +775,8 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
     }
     if (max_pts <= 0) return MSKF_OK;      // nothing to track: no batch pending, _end is a no-op
     if ((rc = ctx->trk_in.ensure(in_bytes)) != MSKF_OK || (rc = ctx->trk_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    MskfCopy mask_cp{};
-    bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind the track
-    if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
-    MskfCopy patch_cp{};
-    bool checked = false;                   // ... or a patch check: its gate runs behind the track and the mask gate
-    if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
-    MskfCopy fb_cp{};
-    bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
-    if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
-    MskfCopy deep_cp{};
-    bool deep = false;                      // ... or more than four LK levels: the deep instantiations of the track kernel and of that gate run
-    if ((rc = stage_deep(ctx, n, streams, &deep_cp, &deep)) != MSKF_OK) return rc;
-    MskfCopy cam_cp{};
-    bool cams_staged = false;               // ... or an extended camera model (or a deep stream): the camera models ride along, the extended instantiation runs
-    if ((rc = stage_cams(ctx, n, streams, deep, &cam_cp, &cams_staged)) != MSKF_OK) return rc;
+    TrackPass pass;
+    if ((rc = plan_track_pass(ctx, n, streams, pass)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         mskf_stream *s = streams[i];
         const mskf_fe_track_args &a = args[i];
@@ -817,24 +792,13 @@ extern "C" int mskf_fe_track_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         track_out_block(ctx->trk_out.d + out_off[i], np, o);
         d.out0 = o.out0; d.out1 = o.out1; d.und0 = o.und0; d.und1 = o.und1; d.status = o.status;
     }
-    MskfCopy cp[MSKF_COPY_SEGS + 1] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
-    int n_cp = 2;
-    if (masked) cp[n_cp++] = mask_cp;
-    if (checked) cp[n_cp++] = patch_cp;
-    if (fb_checked) cp[n_cp++] = fb_cp;
-    if (cams_staged) cp[n_cp++] = cam_cp;
-    if (deep) cp[n_cp++] = deep_cp;          // (a seventh segment goes in a second copy launch: mskf_copy_async)
+    // one list: the batch's own segments, then the pass's (mskf_copy_async splits it at MSKF_COPY_SEGS)
+    MskfCopy cp[2 + TrackPass::kMaxSegs] = {{ctx->trk_in.d, ctx->trk_in.h, in_bytes}, {ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}};
+    const int n_cp = (int)(std::copy(pass.seg, pass.seg + pass.n_seg, cp + 2) - cp);
     mskf_ctx::PendingTrack &T = ctx->pend_trk;
     T.n = n; T.args = args;
-    rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] {
-        // temporal track -> bounds gate + stereo guess -> stereo track -> gates + undistortion: one launch (k_track4)
-        T.ts = mskf_t_begin(ctx, MSKF_K_LK);
-        track_launch(ctx, cams_staged, deep, ctx->desc[1].d, n, max_pts);
-        mskf_t_end(ctx, T.ts, 0);
-        if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_pts);
-        if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_pts);
-        if (fb_checked) fb_gate(ctx, deep, ctx->desc[1].d, n, max_pts);
-    }, MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
+    rc = mskf_enqueue_staged(ctx, T, cp, n_cp, [&] { T.ts = run_track_pass(ctx, pass, ctx->desc[1].d, n, max_pts); },
+                             MskfCopy{ctx->trk_out.h, ctx->trk_out.d, out_bytes});
     if (rc != MSKF_OK) return rc;
     if (ctx->t_gate) ctx->host_s[2] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_h0).count();
     return MSKF_OK;
@@ -972,21 +936,8 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         max_cand_est = std::max(max_cand_est, est);
     }
     if ((rc = ctx->book_out.ensure(out_bytes)) != MSKF_OK) return rc;
-    MskfCopy mask_cp{};
-    bool masked = false;                    // a stream of the batch has an image mask: the point gate runs behind both track launches
-    if ((rc = stage_masks(ctx, 1, n, streams, false, &mask_cp, &masked)) != MSKF_OK) return rc;
-    MskfCopy patch_cp{};
-    bool checked = false;                   // ... or a patch check: its gate runs behind both track launches, and the mask gate
-    if ((rc = stage_patch(ctx, n, streams, &patch_cp, &checked)) != MSKF_OK) return rc;
-    MskfCopy fb_cp{};
-    bool fb_checked = false;                // ... or a forward-backward check: its gate runs last, over the survivors of the others
-    if ((rc = stage_fb(ctx, n, streams, &fb_cp, &fb_checked)) != MSKF_OK) return rc;
-    MskfCopy deep_cp{};
-    bool deep = false;                      // ... or more than four LK levels: both track launches and that gate run their deep instantiations
-    if ((rc = stage_deep(ctx, n, streams, &deep_cp, &deep)) != MSKF_OK) return rc;
-    MskfCopy cam_cp{};
-    bool cams_staged = false;               // ... or an extended camera model (or a deep stream): the camera models ride along, both launches run the extended instantiation
-    if ((rc = stage_cams(ctx, n, streams, deep, &cam_cp, &cams_staged)) != MSKF_OK) return rc;
+    TrackPass pass;                         // (one plan serves both passes of the frame)
+    if ((rc = plan_track_pass(ctx, n, streams, pass)) != MSKF_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const mskf_stream *s = streams[i];
         const mskf_stream::Book &K = s->book;
@@ -1017,31 +968,17 @@ extern "C" int mskf_fe_frame_batch_begin(mskf_ctx *ctx, int n, mskf_stream *cons
         B.x_info = x.info; B.x_id = x.id; B.x_lifetime = x.lifetime; B.x_cam0 = x.cam0; B.x_cam1 = x.cam1; B.x_und0 = x.und0; B.x_und1 = x.und1;
     }
     {
-        MskfCopy cp[6] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
-                          {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}};
-        int n_cp = 3;
-        if (masked) cp[n_cp++] = mask_cp;
-        if (checked) cp[n_cp++] = patch_cp;
-        if (fb_checked) cp[n_cp++] = fb_cp;
+        // one list: the frame's own segments, then the pass's (mskf_copy_async splits it at MSKF_COPY_SEGS)
+        MskfCopy cp[3 + TrackPass::kMaxSegs] = {{ctx->desc[1].d, ctx->desc[1].h, sizeof(FeStreamDev) * (size_t)n}, {ctx->desc[2].d, ctx->desc[2].h, sizeof(FeStreamDev) * (size_t)n},
+                                                {ctx->book_desc.d, ctx->book_desc.h, sizeof(FeBookDev) * (size_t)n}};
+        const int n_cp = (int)(std::copy(pass.seg, pass.seg + pass.n_seg, cp + 3) - cp);
         if ((rc = mskf_copy_async(ctx, cp, n_cp)) != MSKF_OK) return rc;
-        if (cams_staged && (rc = mskf_copy_async(ctx, &cam_cp, 1)) != MSKF_OK) return rc;      // (a copy of its own: cp may already hold MSKF_COPY_SEGS segments)
-        if (deep && (rc = mskf_copy_async(ctx, &deep_cp, 1)) != MSKF_OK) return rc;
     }
-    const int ts1 = mskf_t_begin(ctx, MSKF_K_LK);
-    track_launch(ctx, cams_staged, deep, ctx->desc[1].d, n, max_prev);
-    mskf_t_end(ctx, ts1, 0);
-    if (masked) mask_gate(ctx, ctx->desc[1].d, n, max_prev);
-    if (checked) patch_gate(ctx, ctx->desc[1].d, n, max_prev);
-    if (fb_checked) fb_gate(ctx, deep, ctx->desc[1].d, n, max_prev);
+    const int ts1 = run_track_pass(ctx, pass, ctx->desc[1].d, n, max_prev);
     int tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 0, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);
-    const int ts2 = mskf_t_begin(ctx, MSKF_K_LK);
-    track_launch(ctx, cams_staged, deep, ctx->desc[2].d, n, std::max(max_cand_est, 4));
-    mskf_t_end(ctx, ts2, 0);
-    if (masked) mask_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
-    if (checked) patch_gate(ctx, ctx->desc[2].d, n, std::max(max_cand_est, 4));
-    if (fb_checked) fb_gate(ctx, deep, ctx->desc[2].d, n, std::max(max_cand_est, 4));
+    const int ts2 = run_track_pass(ctx, pass, ctx->desc[2].d, n, std::max(max_cand_est, 4));
     tb = mskf_t_begin(ctx, MSKF_K_FE_BOOK);
     fe_launch_book(ctx->book_desc.d, n, 1, scratch_bytes, st);
     mskf_t_end(ctx, tb, n);

@@ -147,7 +147,7 @@ struct StagedBatch : PendingBatch {
 };
 
 // Which pending batch owns which arenas of the context (mskf_ctx::pending lists the records):
-//   pend_trk, pend_frame   the front-end arenas: desc, mask_desc, patch_desc, fb_desc, cam_desc, deep_desc, jobs, deep_jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
+//   pend_trk, pend_frame   the front-end arenas: desc, what the track pass stages beside it (mask_desc .. deep_desc), jobs, deep_jobs, cell_arena, trk_in / trk_out, book_desc / book_out;
 //   pend_upd               ekf_desc, upd_in, upd_out (a feature update or a direct update: one record for both kinds);
 //   pend_ro                pred_arena, whose host side its kernel reads and writes (position variances or odometry covariance: one record);
 //   pend_dsc, pend_mch,    the jobs / in / out arenas inside the record itself (StagedBatch), which nothing else touches: only a call
@@ -198,12 +198,13 @@ struct mskf_ctx {
     hipStream_t stream = nullptr;
     bool owns_stream = true;          // false: created by mskf_ctx_create_shared on another context's stream
     PinnedDev<FeStreamDev> desc[3];   // 0: push/detect, 1: track (first track call of a device frame), 2: second track call of a device frame
-    PinnedDev<FeMaskDev> mask_desc[2];   // the streams' image masks, element for element beside desc[0] (push) and beside desc[1] / desc[2] (track calls:
-                                         // one array serves both launches of a device frame); front-end arenas, empty until a stream has a mask
-    PinnedDev<FePatchDev> patch_desc;    // the streams' patch checks, element for element beside desc[1] / desc[2]; empty until a stream checks
-    PinnedDev<FeFbDev> fb_desc;          // the streams' forward-backward checks, likewise
-    PinnedDev<FeCamExtDev> cam_desc;     // the streams' camera models, likewise; empty until a stream has an extended model
-    PinnedDev<FeDeepDev> deep_desc;      // the streams' deeper pyramid levels, likewise; empty until a stream tracks over more than four levels
+    // What the track pass stages (plan_track_pass, mskf_capi_fe.cpp): the streams' opt-in settings, element for element beside the
+    // descriptors the pass runs over (one array serves both passes of a device frame); each is empty until a stream has the setting.
+    PinnedDev<FeMaskDev> mask_desc[2];   // image masks: [0] beside desc[0], the push's (cam0 only, the detector), [1] the track pass's
+    PinnedDev<FePatchDev> patch_desc;    // patch checks
+    PinnedDev<FeFbDev> fb_desc;          // forward-backward checks
+    PinnedDev<FeCamExtDev> cam_desc;     // camera models: staged when a stream has an extended model, or the pass is deep
+    PinnedDev<FeDeepDev> deep_desc;      // deeper pyramid levels
     PinnedDev<DeepPyrJob> deep_jobs;     // the deep streams' images of a push (a front-end arena like jobs; empty likewise)
     PinnedDev<FeBookDev> book_desc;   // bookkeeping descriptors of a device frame batch
     PinnedDev<char> book_out;         // what a device frame batch returns: per stream 16 ints + the published grid

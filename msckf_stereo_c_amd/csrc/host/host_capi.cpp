@@ -8,6 +8,17 @@
 
 using namespace cg;
 
+// An ImageProcessor setter on one stream of the runner, or on all (stream < 0), in stream order: the first status that is not
+// MSKF_OK ends the call and is returned; the streams before it keep what they were given.
+template <typename Set>
+static int set_on_streams(void *h, int stream, Set set) {
+    MultiRunner *r = (MultiRunner *)h;
+    if (stream >= r->n_streams()) return MSKF_ERR_INVALID;
+    for (int i = 0; i < r->n_streams(); ++i)
+        if (stream < 0 || i == stream) { const int rc = set(*r->system(i).imgproc_ptr_); if (rc != MSKF_OK) return rc; }
+    return MSKF_OK;
+}
+
 extern "C" {
 
 void *mskfh_runner_create(int device, int n_groups, int per_group, const mskf_calib *calib, const mskf_fe_cfg *fe, const mskf_ekf_cfg *ekf,
@@ -208,11 +219,8 @@ void mskfh_get_poses(void *h, int stream, mskf_pose *out) {
 // ImageProcessor::setEqualize (mskf_fe_set_equalize) of one stream, or of all (stream < 0); call before the first frame.
 // Returns the first status that is not MSKF_OK (mskf_last_error has the text).
 int mskfh_runner_set_equalize(void *h, int stream, const mskf_fe_equalize *cfg) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setEqualize(*cfg); if (rc != MSKF_OK) return rc; }
-    return MSKF_OK;
+    if (!cfg) return MSKF_ERR_INVALID;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setEqualize(*cfg); });
 }
 // ImageProcessor::setInputFormat (mskf_fe_set_input_format) of one stream, or of all (stream < 0); call before the first frame.
 // The images of mskfh_runner_step and the frames of mskfh_runner_set_sequence are then raw byte rasters in that format.
@@ -236,23 +244,14 @@ int mskfh_runner_set_input_format(void *h, int stream, const mskf_fe_input_forma
 // ImageProcessor::setMask (mskf_fe_set_mask) of one stream, or of all (stream < 0); between runs.  Returns the first status that
 // is not MSKF_OK (mskf_last_error has the text): bad arguments refuse at the first stream, which then keeps its previous masks.
 int mskfh_runner_set_mask(void *h, int stream, const mskf_fe_mask *cfg) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) {
-            const int rc = r->system(i).imgproc_ptr_->setMask(cfg->cam0, cfg->cam1, cfg->width, cfg->height, cfg->pitch, cfg->margin);
-            if (rc != MSKF_OK) return rc;
-        }
-    return MSKF_OK;
+    if (!cfg) return MSKF_ERR_INVALID;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setMask(cfg->cam0, cfg->cam1, cfg->width, cfg->height, cfg->pitch, cfg->margin); });
 }
 // ImageProcessor::setPatchCheck (mskf_fe_set_patch_check) of one stream, or of all (stream < 0); between runs.  Returns the first
 // status that is not MSKF_OK (mskf_last_error has the text): bad arguments refuse at the first stream, which keeps its setting.
 int mskfh_runner_set_patch_check(void *h, int stream, const mskf_fe_patch_check *cfg) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setPatchCheck(*cfg); if (rc != MSKF_OK) return rc; }
-    return MSKF_OK;
+    if (!cfg) return MSKF_ERR_INVALID;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setPatchCheck(*cfg); });
 }
 // the optional patch_check keys of an app_imgproc.yaml (patch_check_from_yaml); 0 on success
 int mskfh_load_patch_check(const char *yaml_path, mskf_fe_patch_check *out) {
@@ -266,11 +265,8 @@ int mskfh_load_patch_check(const char *yaml_path, mskf_fe_patch_check *out) {
 }
 // ImageProcessor::setFbCheck (mskf_fe_set_fb_check) of one stream, or of all (stream < 0); between runs.  As mskfh_runner_set_patch_check.
 int mskfh_runner_set_fb_check(void *h, int stream, const mskf_fe_fb_check *cfg) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setFbCheck(*cfg); if (rc != MSKF_OK) return rc; }
-    return MSKF_OK;
+    if (!cfg) return MSKF_ERR_INVALID;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setFbCheck(*cfg); });
 }
 // the optional fb_check keys of an app_imgproc.yaml (fb_check_from_yaml); 0 on success
 int mskfh_load_fb_check(const char *yaml_path, mskf_fe_fb_check *out) {
@@ -284,11 +280,7 @@ int mskfh_load_fb_check(const char *yaml_path, mskf_fe_fb_check *out) {
 }
 // ImageProcessor::setLkLevels (mskf_fe_set_lk_levels) of one stream, or of all (stream < 0); before the streams' first frame.
 int mskfh_runner_set_lk_levels(void *h, int stream, int levels) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setLkLevels(levels); if (rc != MSKF_OK) return rc; }
-    return MSKF_OK;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setLkLevels(levels); });
 }
 // the optional lk_pyramid_levels key of an app_imgproc.yaml, for a width x height image (lk_levels_from_yaml); 0 on success, and the
 // reason of a refusal is kept, per thread, for mskfh_load_lk_levels_error
@@ -306,11 +298,8 @@ int mskfh_load_lk_levels(const char *yaml_path, int width, int height, int *out)
 const char *mskfh_load_lk_levels_error(void) { return g_lk_levels_error.c_str(); }
 // ImageProcessor::setCameraModel (mskf_fe_set_camera_model) of one stream, or of all (stream < 0); between runs.  As mskfh_runner_set_fb_check.
 int mskfh_runner_set_camera_model(void *h, int stream, const mskf_fe_camera_model *cfg) {
-    MultiRunner *r = (MultiRunner *)h;
-    if (!cfg || stream >= r->n_streams()) return MSKF_ERR_INVALID;
-    for (int i = 0; i < r->n_streams(); ++i)
-        if (stream < 0 || i == stream) { const int rc = r->system(i).imgproc_ptr_->setCameraModel(*cfg); if (rc != MSKF_OK) return rc; }
-    return MSKF_OK;
+    if (!cfg) return MSKF_ERR_INVALID;
+    return set_on_streams(h, stream, [&](ImageProcessor &ip) { return ip.setCameraModel(*cfg); });
 }
 // the camera models of a camchain yaml (camera_models_from_yaml): out[2], extended[2]; 0 on success
 int mskfh_load_camera_models(const char *yaml_path, mskf_fe_camera_model *out, int *extended) {

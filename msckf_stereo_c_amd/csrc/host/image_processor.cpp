@@ -412,21 +412,19 @@ bool ImageProcessor::initialize() {
     occupancy_.assign((size_t)cfg_.det_rows * cfg_.det_cols, 0);
     if (have_yaml_) debug_.open("debug_imageprocessor.txt");
     initialized_ = true;
-    // the opt-in equalisation of the pushed images; a stream that never asked for it is not touched
-    if (stream_ && eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return false;
-    // ... and the opt-in input pixel format, likewise
-    if (stream_ && (px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return false;
-    // ... and the opt-in image masks, likewise
-    if (stream_ && applyKeptMask() != MSKF_OK) return false;
-    // ... and the opt-in patch check, likewise
-    if (stream_ && patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
-    // ... and the opt-in forward-backward check, likewise
-    if (stream_ && fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return false;
-    // ... and the opt-in deeper LK pyramids, likewise
-    if (stream_ && lk_levels_ != FD_BASE_LEVELS && setLkLevels(lk_levels_) != MSKF_OK) return false;
-    // ... and the opt-in camera models (setCameraModel before this, or an extended model in the camchain), likewise
-    if (stream_ && applyKeptCameraModels() != MSKF_OK) return false;
-    return true;
+    return !stream_ || applyKeptSettings();
+}
+
+// The opt-in settings kept until the stream exists (the set* calls before it, the yaml keys), onto the fresh stream_, in this order;
+// a stream that never asked for one is not touched for it.
+bool ImageProcessor::applyKeptSettings() {
+    if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return false;
+    if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return false;
+    if (applyKeptMask() != MSKF_OK) return false;
+    if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return false;
+    if (fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return false;
+    if (lk_levels_ != FD_BASE_LEVELS && setLkLevels(lk_levels_) != MSKF_OK) return false;
+    return applyKeptCameraModels() == MSKF_OK;      // (setCameraModel before this, or an extended model in the camchain)
 }
 
 // :205-211
@@ -467,13 +465,7 @@ void ImageProcessor::stereoCallback(const cg::Image &cam0_img, const cg::Image &
         if (rc != MSKF_OK) { fail("mskf_stream_create", rc); return; }
         own_stream_ = true;
         mskf_fe_set_detect_floor(stream_, cfg_.fast_threshold * 256);
-        if (eq_cfg_.mode != 0 && setEqualize(eq_cfg_) != MSKF_OK) return;
-        if ((px_cfg_.format != 0 || px_cfg_.shift != 0) && setInputFormat(px_cfg_) != MSKF_OK) return;
-        if (applyKeptMask() != MSKF_OK) return;
-        if (patch_cfg_.mode != 0 && setPatchCheck(patch_cfg_) != MSKF_OK) return;
-        if (fb_cfg_.mode != 0 && setFbCheck(fb_cfg_) != MSKF_OK) return;
-        if (lk_levels_ != FD_BASE_LEVELS && setLkLevels(lk_levels_) != MSKF_OK) return;
-        if (applyKeptCameraModels() != MSKF_OK) return;
+        if (!applyKeptSettings()) return;
     }
     // (cam1 is held to the same size: the push reads w * h * bpp bytes of it, whatever the image holds)
     if (w != calib_.width || h != calib_.height || cam0_img.image.cols() != w * bpp || cam1_img.image.cols() != w * bpp || cam1_img.image.rows() != h) {

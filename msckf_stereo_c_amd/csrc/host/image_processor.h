@@ -261,6 +261,7 @@ class ImageProcessor {
     int applyKeptCameraModels();
     struct MaskKept { std::vector<uint8_t> plane[2]; int w = 0, h = 0, margin = 0; bool on[2] = {false, false}; } mask_kept_;   // setMask before the stream exists
     int applyKeptMask();
+    bool applyKeptSettings();                    // every opt-in setting above, onto the fresh stream_; false: one was refused (error_)
     bool descriptors_ = false;
     std::vector<FeatureIDType> desc_ids_;
     std::vector<uint8_t> desc_, desc_valid_;
